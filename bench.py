@@ -199,6 +199,41 @@ def cpu_baseline_port(prob, target_seconds=12.0):
                       f"projection, M-step, E-step) in literal mode in {dt:.1f} s"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20261015   # the fixed sample of a volume too large for the budget
+
+
+def dump_outputs(out_dir, rec, drv, order, write):
+    """--dump-outputs: what the timed path's last step left for its caller -- the reconstructed volume (syncCPU) and the host
+    object's EM state (state(): per-slice / per-patch vectors in the reference's order, whatever the sharding, and the scalars)
+    -> out_dir/<name>.npy, float32 / float64.  A volume that does not fit the budget is written as a fixed, seeded sample of its
+    voxels (reconstructed_sample + reconstructed_sample_index).  state() is collective on a sharded run: every rank calls this,
+    `write` (rank 0) writes."""
+    st = drv.state()                                   # (flushes the vectors the other ranks still owe)
+    vol = rec.syncCPU()
+    out = {}
+    for k, v in st.items():
+        if isinstance(v, np.ndarray):
+            ref = np.empty_like(v)
+            ref[np.asarray(order)] = v                 # order[k] = the reference's index of unit k of this run's numbering
+            out[k] = ref.astype(np.float32)
+        else:
+            out[k] = np.array(v, np.float64)           # the EM scalars (sigma, mix, ...), one 0-d array each
+    left = DUMP_BUDGET_BYTES - sum(a.nbytes for a in out.values()) - 128 * (len(out) + 2)      # (+ a .npy header per file)
+    if vol.nbytes <= left:
+        out["reconstructed"] = vol
+    else:
+        n = max(1, left // (4 + 8))                    # float32 value + float64 index per voxel
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(vol.size, size=min(n, vol.size), replace=False))
+        out["reconstructed_sample"] = vol[idx]
+        out["reconstructed_sample_index"] = idx.astype(np.float64)
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -214,6 +249,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--workload", default="P4", choices=["P4", "P4s", "S8", "S8h", "tiny", "PVR4", "PVR8spx"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (the reconstructed volume, the EM state) to DIR/<name>.npy")
     ap.add_argument("--no-coeff-table", action="store_true", help="skip the second measurement with the coefficient table")
     ap.add_argument("--no-s8", action="store_true", help="skip the S8 record (BASELINE configs[3], measured after the default workload in the same launch)")
     ap.add_argument("--layout", choices=["spatial", "contiguous"], default=None,
@@ -296,9 +333,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def measure(workload, with_table):
+    def measure(workload, with_table, dump_dir=None):
         """one workload through the steps of the contract on this launch's ranks and communicator: W untimed steps, K timed ones between
-        barriers -> everything the line reports about it"""
+        barriers -> everything the line reports about it; dump_dir: the outputs of the last timed step of the headline mode go there"""
         comm, rccl_world = state["comm"], state["rccl_world"]
         # ---- the workload: fixed, whatever the world size --------------------------------------------------------------
         prob = workloads.get(workload) if workload != "tiny" else phantom.problem_tiny()
@@ -429,7 +466,7 @@ def main():
             barrier()
             return time.perf_counter() - t_
 
-        def run_mode(table_on):
+        def run_mode(table_on, dump=False):
             """W untimed steps, then K timed ones with the kernel timers OFF (the figure the line reports), then the same K steps once more
             with HIP events around each hot kernel for `kernel_ms` (the events cost 4-8 us of stream time apiece, a dozen per SR iteration:
             ~1 % of a P4 step on one GPU, several per cent of a rank's share of it) -- the schedule restarted from the same position"""
@@ -444,6 +481,8 @@ def main():
             for i in range(args.warmup):
                 step()
             d_ = timed(args.steps)
+            if dump:                     # outside the timed region, before the steps below move the state on
+                dump_outputs(dump_dir, rec, drv, order, rank == 0)
             fits = pvr or (not table_on) or rec.get_option("coeff_table") == 1     # the table switches itself off when it does not fit the free memory
             rec.timer_enable(True)       # HIP events on the engine's own stream around each hot kernel (svr_timer_*)
             done[0] = 0
@@ -459,7 +498,7 @@ def main():
             return d_, d_t, tm_, fits
 
         table_default = (not pvr) and rec.get_option("coeff_table") == 1
-        dt, dt_timers, timers, table_fits = run_mode(table_default)
+        dt, dt_timers, timers, table_fits = run_mode(table_default, dump=dump_dir is not None)
         table_used = table_default and table_fits and rec.get_option("coeff_table") == 1
         cnt = rec.counters()
 
@@ -570,7 +609,7 @@ def main():
         return dict(prob=prob, pvr=pvr, rec=rec, drv=drv, local=local, lo=lo, hi=hi, dt=dt, dt_timers=dt_timers, timers=timers, cnt=cnt, ranks=ranks, va=va, tuned=tuned,
                     tab=tab, alt=alt, table_used=table_used, order=order, unit_counts=uc, cell_order=rec.get_option("cell_order"), fallbacks=fb, device=probe)
 
-    m = measure(args.workload, not args.no_coeff_table)
+    m = measure(args.workload, not args.no_coeff_table, args.dump_outputs)
     prob, pvr, rec, dt, timers, cnt, ranks, va, tuned, tab = (m[k] for k in ("prob", "pvr", "rec", "dt", "timers", "cnt", "ranks", "va", "tuned", "tab"))
     alt, table_used, dt_timers = m["alt"], m["table_used"], m["dt_timers"]
     unit_counts, cell_order, fallbacks, device = m["unit_counts"], m["cell_order"], m["fallbacks"], m["device"]

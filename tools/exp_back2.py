@@ -1,6 +1,6 @@
 """dev tool: scatter / gather timings on a workload for a list of option sets.
 usage: python tools/exp_back2.py [workload] -- "opt=v opt=v" "opt=v" ..."""
-import os, sys; sys.path.insert(0, '/root/repo')
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from fetalreconstruction_amd import workloads, engine
 from tests.twins.reconstruction import irtkReconstruction

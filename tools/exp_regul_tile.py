@@ -1,5 +1,5 @@
 import json, os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from fetalreconstruction_amd import workloads, engine, host
 for wl in sys.argv[1:]:

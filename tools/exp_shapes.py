@@ -1,6 +1,6 @@
 """dev tool: the gather and the scatter on P4 for explicit tile shapes (timers of the engine, last of 4 launches).
 usage: python tools/exp_shapes.py [workload]"""
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fetalreconstruction_amd import workloads, engine
 from tests.twins.reconstruction import irtkReconstruction
 wl = sys.argv[1] if len(sys.argv) > 1 else 'P4'

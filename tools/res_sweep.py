@@ -1,6 +1,6 @@
 """per-pixel kernel times over reconstruction resolutions (voxels per pixel from 0.67 to 2.9): looks for cliffs where a tile's
 volume box stops fitting LDS.  4 stacks of 128x128x32, 1.0 mm pixels."""
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from fetalreconstruction_amd import phantom, engine
 from tests.twins.reconstruction import irtkReconstruction

@@ -3,7 +3,7 @@
 (--spxSize 32 --spxExtend 2).  Writes the stacks as NIfTI, runs bin/PVRreconstructionGPU, reports wall time and the
 correlation with the analytic phantom.  usage: run_cli_config5.py [superpixel|square] [recon mm]"""
 import subprocess, sys, time, os
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from fetalreconstruction_amd import phantom, nifti, build, geometry as geo
 mode = sys.argv[1] if len(sys.argv) > 1 else "superpixel"

@@ -1,9 +1,10 @@
 """P4-scale run of the default (IRTK schedule) slice-to-volume registration with every similarity on the GPU: reconstruct,
 mask, register the 280 slices in lock step; prints wall time and evaluation counts.  usage: run_irtk_reg.py [tiny|p4]"""
+import os
 import sys
 import time
 
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 from fetalreconstruction_amd import engine, geometry as geo, host, phantom  # noqa: E402

@@ -1,7 +1,7 @@
 """P4-scale run of the GPU slice-to-volume registration: reconstruct, prepare, register; prints time and
 counters, with the batched gradient and one evaluation at a time.  usage: run_reg.py [tiny|p4]"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from fetalreconstruction_amd import phantom, engine
 from tests.twins import registration as R
