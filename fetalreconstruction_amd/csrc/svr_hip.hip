@@ -2933,7 +2933,7 @@ __global__ void k_mstep_scalars(const double *s5, int iter, float step, int pvr,
   em[0] = sigma; em[1] = mix; em[2] = m;
 }
 // ... of a sharded run: all[world][8] = every rank's five sums (an all-gather on the device), added up in rank order exactly like
-// the hosts do after their exchange (svr::irtkReconstruction::mstep_exchange) -- the same bits on every rank
+// the hosts do after their exchange (csrc/svr_unit_em.h UnitState::mstep_now) -- the same bits on every rank
 __global__ void k_mstep_scalars_ranks(const double *all, int world, int iter, float step, int pvr, float sigma, float mix, float *em) {
   double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int r = 0; r < world; ++r) {

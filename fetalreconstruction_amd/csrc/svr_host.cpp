@@ -10,43 +10,42 @@
 #include <vector>
 
 #include "../../include/svr_host.h"
-#include "svr_shard.h"
+#include "svr_unit_em.h"
 
 namespace svr {
 
 class irtkReconstruction {
  public:
-  // engine + sharding
+  // engine + the unit-level state (svr_unit_em.h: the slices' vectors and EM scalars, the numbering, the device EM, the exchanges)
   svr_ctx *reconstructionGPU;          // RG.h: Reconstruction* reconstructionGPU
   int ns, lo, hi;
-  Shard sh;                            // this rank's slice range, the collectives, the one exchange per step (svr_shard.h)
-  std::string err;
+  UnitState em;
+  Shard &sh = em.sh;                   // this rank's slice range, the collectives, the one exchange per step (svr_shard.h)
+  std::string &err = em.err;
 
   // members named as in RG.h / RG.cc:159-221
   double _step;
   int _quality_factor;
   float _sigma_bias;
-  float _sigma_gpu, _mix_gpu, _m_gpu;
-  float _mean_s_gpu, _mean_s2_gpu, _sigma_s_gpu, _sigma_s2_gpu, _mix_s_gpu;
   double _delta, _lambda, _alpha;
   float _low_intensity_cutoff;
   bool _global_bias_correction, _adaptive, _disableBiasC;
   bool _intensity_matching;            // reconstruction.cc:114,183: false skips Bias / Scale / NormaliseBias in every SR iteration
   double _max_intensity, _min_intensity;
   std::vector<int> _force_excluded, _small_slices;
-  std::vector<float> _scale_gpu, _slice_weight_gpu, _slice_potential_gpu;
-  std::vector<unsigned char> _slice_inside_gpu;
 
   irtkReconstruction(svr_ctx *engine, int n_global, int lo_, int hi_, const svr_collectives *c)
       : reconstructionGPU(engine), ns(n_global), lo(lo_), hi(hi_) {
-    sh.init(engine, n_global, lo_, hi_, c);
+    em.init(engine, n_global, lo_, hi_, c, true);
     _step = 0.0001;
+    em.step = _step;
+    em.var_floor = _step * _step / 6.28;
     _quality_factor = 2;
     _sigma_bias = 12;
-    _sigma_s_gpu = 0.025f;
-    _sigma_s2_gpu = 0.025f;
-    _mix_s_gpu = 0.9f;
-    _mix_gpu = 0.9f;
+    em.cls.var = 0.025f;
+    em.cls.var2 = 0.025f;
+    em.cls.mix = 0.9f;
+    em.mix = 0.9f;
     _delta = 1;
     _lambda = 0.1f;
     _alpha = (0.05f / _lambda) * _delta * _delta;
@@ -56,134 +55,17 @@ class irtkReconstruction {
     _disableBiasC = true;   // reconstruction.cc:121,202
     _intensity_matching = true;
     _max_intensity = 1; _min_intensity = 0;
-    _sigma_gpu = 0; _m_gpu = 0; _mean_s_gpu = 0; _mean_s2_gpu = 0;
-    _scale_gpu.assign(ns, 1.0f);
-    _slice_weight_gpu.assign(ns, 1.0f);
-    _slice_potential_gpu.assign(ns, 0.0f);
-    _slice_inside_gpu.assign(ns, 1);
   }
 
-  int fail(int rc, const char *what) {
-    err = std::string(what) + ": " + (rc >= 10000 || rc < 0 ? "" : "hip error ") + std::to_string(rc) + " " +
-          svr_last_error(reconstructionGPU);
-    return rc;
-  }
-#define ENG(call) do { int rc_ = (call); if (rc_) return fail(rc_, #call); } while (0)
-
-  // -- sharding helpers ------------------------------------------------------------------
+#define ENG(call) do { int rc_ = (call); if (rc_) return em.fail(rc_, #call); } while (0)
   const float *local(const std::vector<float> &v) const { return v.data() + lo; }
-  // The numbering of a sharded run need not be the reference's (svrh_set_unit_order): a launcher that deals the r-th part of EVERY
-  // stack to rank r (spatially compact shards, sharding.shard_units / csrc/svr_shard.h spatial_order) uploads the slices rank after
-  // rank.  order[k] = the reference's index of slice k of this object's numbering; empty = the same numbering.  Everything per slice is
-  // indifferent to the numbering; what the reference does ACROSS slices in slice order -- the sums of the slice-level EM -- is done in
-  // the reference's order (to_ref / from_ref), so a permuted run adds the same numbers in the same order as an unpermuted one.
-  std::vector<int> order;
-  template <class T> std::vector<T> to_ref(const std::vector<T> &v) const {
-    if (order.empty()) return v;
-    std::vector<T> r(v.size());
-    for (size_t k = 0; k < v.size(); ++k) r[order[k]] = v[k];
-    return r;
-  }
-  template <class T> std::vector<T> from_ref(const std::vector<T> &r) const {
-    if (order.empty()) return r;
-    std::vector<T> v(r.size());
-    for (size_t k = 0; k < r.size(); ++k) v[k] = r[order[k]];
-    return v;
-  }
-  int ref_index(int k) const { return order.empty() ? k : order[k]; }
 
-  // ---- the slice-level EM on the device (round 5; csrc/svr_em.inc) --------------------------------------------------------------
-  // The host half of EStepGPU below -- potentials down, a two-class EM over the slices, slice weights up -- was the one wait of an SR
-  // iteration and, sharded, its one host exchange.  With SVR_DEVICE_SLICE_EM (default on; sharded: when the launcher supplies
-  // allgather_device) the E-step's potentials, the scale vector and slice_inside of every rank meet on the device (one all-gather of
-  // 3 x maxn floats) and the EM runs there as one workgroup: an SR iteration only queues launches.  `_em_on_host` says whose copy of
-  // the slice-level state (_scale_gpu, _slice_weight_gpu, _slice_potential_gpu, _slice_inside_gpu, the eight scalars) is current;
-  // pull_state() brings the device's over in one wait when somebody reads it, push_state() sends the host's when it changed it.
-  bool dev_slice_em = getenv("SVR_DEVICE_SLICE_EM") ? atoi(getenv("SVR_DEVICE_SLICE_EM")) != 0 : true;
-  bool _sem_ready = false, _em_on_host = true;
-  bool use_device_slice_em() const { return dev_slice_em && device_em && (!sh.on || sh.coll.allgather_device); }
-  int push_state() {
-    if (!_sem_ready) {
-      const int W = sh.on ? sh.coll.world : 1, R = sh.on ? sh.coll.rank : 0;
-      std::vector<double> b((size_t)W + 1, 0.0);                       // every rank's range of this numbering: one small exchange, once
-      b[R] = lo;
-      if (R == W - 1) b[W] = hi;
-      if (sh.on && W > 1) ENG(sh.coll.allreduce_host(sh.coll.user, b.data(), W + 1, 0));
-      std::vector<int> rlo((size_t)W + 1);
-      for (int r = 0; r <= W; ++r) rlo[r] = (int)b[r];
-      ENG(svr_slice_em_setup(reconstructionGPU, ns, W, R, rlo.data(), order.empty() ? nullptr : order.data(), _step));
-      _sem_ready = true;
-      _em_on_host = true;
-    }
-    if (_em_on_host) {
-      std::vector<unsigned char> excl(ns, 0);
-      for (int i : _force_excluded) if (i >= 0 && i < ns) excl[i] = 1;
-      for (int i : _small_slices) if (i >= 0 && i < ns) excl[i] = 1;
-      const double s5[5] = {_mean_s_gpu, _mean_s2_gpu, _sigma_s_gpu, _sigma_s2_gpu, _mix_s_gpu};
-      const float em3[3] = {_sigma_gpu, _mix_gpu, _m_gpu};
-      ENG(svr_slice_em_set_state(reconstructionGPU, _slice_weight_gpu.data(), excl.data(), s5, em3));
-    }
-    return 0;
-  }
-  int pull_state() {
-    if (_em_on_host) return 0;
-    double s5[5];
-    float em3[3];
-    ENG(svr_slice_em_fetch(reconstructionGPU, _scale_gpu.data(), _slice_weight_gpu.data(), _slice_potential_gpu.data(), _slice_inside_gpu.data(), s5, em3));
-    _mean_s_gpu = (float)s5[0]; _mean_s2_gpu = (float)s5[1]; _sigma_s_gpu = (float)s5[2]; _sigma_s2_gpu = (float)s5[3]; _mix_s_gpu = (float)s5[4];
-    _sigma_gpu = em3[0]; _mix_gpu = em3[1]; _m_gpu = em3[2];
-    _em_on_host = true;
-    return 0;
-  }
-  // The ns-sized vectors a rank has only its own part of (`_scale_stale`, `_inside_stale`) ride along with the next exchange
-  // that every rank makes anyway (Shard::exchange: one collective): the M-step's sums, the E-step's potentials, the
-  // robust-statistics sums.
-  //   mine[n_mine] -> all[world][n_mine];  pot (or NULL): the slice potentials, this rank's range filled -> complete
-  bool _scale_stale = false, _inside_stale = false;
-  int exchange(const double *mine, int n_mine, std::vector<double> &all, std::vector<float> *pot) {
-    if (int rc = settle()) return rc;                  // this rank's own parts of the vectors that travel
-    std::vector<float> inside;
-    if (_inside_stale) inside.assign(_slice_inside_gpu.begin(), _slice_inside_gpu.end());
-    std::vector<float> *vec[3] = {_scale_stale ? &_scale_gpu : nullptr, _inside_stale ? &inside : nullptr, pot};
-    const int rc = sh.exchange(mine, n_mine, all, vec);
-    if (rc) { err = rc == SVR_E_STATE ? "exchange: the ranks are not in the same step of the reconstruction" : "exchange: the collective failed"; return rc; }
-    if (_inside_stale) for (int i = 0; i < ns; ++i) _slice_inside_gpu[i] = inside[i] > 0.5f;
-    _scale_stale = _inside_stale = false;
-    return 0;
-  }
-  // One rank, nothing to exchange: the scale vector, slice_inside and the M-step's scalars stay on the device until the
-  // E-step fetches them with its potentials in one wait (svr_mstep_estep) -- one wait per SR iteration instead of four.
-  // `settle` brings over whatever is still there when something else wants to read it.
-  bool _scale_pending = false, _inside_pending = false;
-  int _mstep_pending = 0;                            // iteration number of an M-step not yet run, or 0
-  int settle() {
-    if (int rc = pull_state()) return rc;              // (the device's slice-level state, if it is the current one)
-    if (_mstep_pending) {
-      const int iter = _mstep_pending;
-      _mstep_pending = 0;
-      if (sh.on) { if (int rc = mstep_exchange(iter)) return rc; }       // (collective: the ranks run the same operator sequence)
-      else ENG(svr_mstep(reconstructionGPU, iter, (float)_step, &_sigma_gpu, &_mix_gpu, &_m_gpu));
-    }
-    if (_scale_pending) {
-      std::vector<float> loc(hi - lo);
-      ENG(svr_get_scale_vector(reconstructionGPU, loc.data()));
-      std::copy(loc.begin(), loc.end(), _scale_gpu.begin() + lo);
-      _scale_pending = false;
-    }
-    if (_inside_pending) {
-      std::vector<unsigned char> inside(hi - lo);
-      ENG(svr_get_slice_inside(reconstructionGPU, inside.data()));
-      for (int i = 0; i < hi - lo; ++i) _slice_inside_gpu[lo + i] = inside[i] != 0;
-      _inside_pending = false;
-    }
-    return 0;
-  }
-  // completes the vectors of which a rank only holds its own part (collective: every rank calls it); svrh_get_state does
-  int flush() {
-    if (int rc = settle()) return rc;
-    if (!sh.on || (!_scale_stale && !_inside_stale)) return 0;
-    std::vector<double> none;
-    return exchange(nullptr, 0, none, nullptr);
+  // the slices the slice-level EM leaves out, in this object's numbering
+  std::vector<unsigned char> excluded() const {
+    std::vector<unsigned char> x(ns, 0);
+    for (int i : _force_excluded) if (i >= 0 && i < ns) x[i] = 1;
+    for (int i : _small_slices) if (i >= 0 && i < ns) x[i] = 1;
+    return x;
   }
 
   // RG.h:605-612
@@ -194,15 +76,7 @@ class irtkReconstruction {
     if (_alpha > 1) _alpha = 1;
   }
 
-  // RG.cc:2905-2919
-  int InitializeEMValuesGPU() {
-    if (int rc = settle()) return rc;
-    _slice_weight_gpu.assign(ns, 1);
-    _scale_gpu.assign(ns, 1);
-    ENG(svr_update_scale_vector(reconstructionGPU, local(_scale_gpu), local(_slice_weight_gpu)));
-    ENG(svr_initialize_em_values(reconstructionGPU));
-    return 0;
-  }
+  int InitializeEMValuesGPU() { return em.init_em_values(); }   // RG.cc:2905-2919
 
   // RG.cc:2695-2762.  voxel_num has one entry per device and its median indexes out of range for
   // one device (RG.cc:2714-2726), so no slice is ever "small" on the GPU path.
@@ -220,204 +94,54 @@ class irtkReconstruction {
     return 0;
   }
 
-  // RG.cc:1163-1175
+  // RG.cc:1163-1175.  Sharded: this rank's flags come over with the M-step's sums, the other ranks' with the exchange that follows.
   int SimulateSlicesGPU() {
-    if (!sh.on) {
-      ENG(svr_simulate_slices(reconstructionGPU, nullptr));
-      _inside_pending = true;
-      return 0;
-    }
-    ENG(svr_simulate_slices(reconstructionGPU, nullptr));   // sharded: this rank's flags come over with the M-step's sums,
-    _inside_pending = true;                                 // the other ranks' with the exchange that follows
-    _inside_stale = true;
+    ENG(svr_simulate_slices(reconstructionGPU, nullptr));
+    em.inside_pending = true;
+    if (sh.on) em.inside_stale = true;
     return 0;
   }
 
   // RG.cc:2988-3019
   int InitializeRobustStatisticsGPU() {
-    if (int rc = settle()) return rc;
+    if (int rc = em.settle()) return rc;
     if (!sh.on) {
-      ENG(svr_initialize_robust_statistics(reconstructionGPU, &_sigma_gpu));
+      ENG(svr_initialize_robust_statistics(reconstructionGPU, &em.sigma));
     } else {
       double s2[2], t[2] = {0, 0};
       ENG(svr_robust_statistics_sums(reconstructionGPU, s2));
       std::vector<double> all;
-      ENG(exchange(s2, 2, all, nullptr));         // (brings the other ranks' slice_inside along)
+      ENG(em.exchange(s2, 2, all, nullptr));      // (brings the other ranks' slice_inside along)
       for (int r = 0; r < sh.coll.world; ++r) { t[0] += all[2 * r]; t[1] += all[2 * r + 1]; }
-      _sigma_gpu = (float)t[0] / (float)t[1];
+      em.sigma = (float)t[0] / (float)t[1];
     }
     for (int i = 0; i < ns; ++i)
-      if (!_slice_inside_gpu[i]) _slice_weight_gpu[i] = 0;
-    for (size_t i = 0; i < _force_excluded.size(); i++) _slice_weight_gpu[_force_excluded[i]] = 0;
-    _sigma_s_gpu = 0.025f;
-    _mix_gpu = 0.9f;
-    _mix_s_gpu = 0.9f;
-    _m_gpu = (float)(1.0f / (2.1f * _max_intensity - 1.9f * _min_intensity));
-    ENG(svr_update_scale_vector(reconstructionGPU, local(_scale_gpu), local(_slice_weight_gpu)));
+      if (!em.inside[i]) em.weight[i] = 0;
+    for (size_t i = 0; i < _force_excluded.size(); i++) em.weight[_force_excluded[i]] = 0;
+    em.cls.var = 0.025f;
+    em.mix = 0.9f;
+    em.cls.mix = 0.9f;
+    em.m = (float)(1.0f / (2.1f * _max_intensity - 1.9f * _min_intensity));
+    ENG(svr_update_scale_vector(reconstructionGPU, local(em.scale), local(em.weight)));
     return 0;
   }
 
-  double G(double x, double s) { return _step * exp(-x * x / (2 * s)) / (sqrt(6.28 * s)); }   // RG.h:529-532
+  // RG.cc:3184-3440: voxel posteriors on the GPU, the slice-level EM on the device or on the host (svr_unit_em.h)
+  int EStepGPU() { return em.estep(SliceGauss{_step}, excluded()); }
 
-  // RG.cc:3184-3440: voxel posteriors on the GPU, slice-level EM on the host
-  int EStepGPU() {
-    if (use_device_slice_em()) {
-      // [M-step] + E-step + the slice-level EM without a wait and without a host exchange (csrc/svr_em.inc)
-      if (int rc = push_state()) return rc;
-      const int iter = _mstep_pending;
-      _mstep_pending = 0;
-      void *send = nullptr, *recv = nullptr;
-      if (iter > 0 && sh.on) {                         // the ranks' M-step sums meet on the device (round 4)
-        ENG(svr_mstep_partial(reconstructionGPU, sh.coll.world, &send, &recv));
-        if (int rc = sh.before_device_collective()) return fail(rc, "svr_stream_sync");
-        if (int rc = sh.coll.allgather_device(sh.coll.user, send, recv, 16)) return fail(rc, "allgather_device (M-step sums)");
-      }
-      size_t n = 0;
-      ENG(svr_mstep_estep_device(reconstructionGPU, iter, (float)_step, &send, &recv, &n));
-      if (sh.on) {                                     // every rank's potentials, scales and slice_inside: one all-gather of 3 x maxn floats
-        if (int rc = sh.before_device_collective()) return fail(rc, "svr_stream_sync");
-        if (int rc = sh.coll.allgather_device(sh.coll.user, send, recv, n)) return fail(rc, "allgather_device (slice potentials)");
-      }
-      ENG(svr_slice_em_run(reconstructionGPU));
-      _em_on_host = false;
-      _scale_pending = _inside_pending = _scale_stale = _inside_stale = false;   // (they travelled with the gather)
-      return 0;
-    }
-    std::vector<float> loc(hi - lo);
-    if (_mstep_pending && sh.on) {
-      // sharded (round 4): the M-step's five sums of every rank meet ON THE DEVICE (the launcher's all-gather on the engine's stream),
-      // are added up there in rank order, and the E-step runs on the result: one wait and one host exchange (the potentials') per SR
-      // iteration instead of two of each
-      const int iter = _mstep_pending;
-      _mstep_pending = 0;
-      void *send = nullptr, *recv = nullptr;
-      ENG(svr_mstep_partial(reconstructionGPU, sh.coll.world, &send, &recv));
-      if (int rc = sh.before_device_collective()) return fail(rc, "svr_stream_sync");
-      if (int rc = sh.coll.allgather_device(sh.coll.user, send, recv, 16)) return fail(rc, "allgather_device (M-step sums)");
-      float em3[3] = {_sigma_gpu, _mix_gpu, _m_gpu};
-      std::vector<float> sc(_scale_pending ? hi - lo : 0);
-      std::vector<unsigned char> inside(_inside_pending ? hi - lo : 0);
-      ENG(svr_mstep_estep_ranks(reconstructionGPU, sh.coll.world, iter, (float)_step, em3, loc.data(), _scale_pending ? sc.data() : nullptr,
-                                _inside_pending ? inside.data() : nullptr));
-      _sigma_gpu = em3[0]; _mix_gpu = em3[1]; _m_gpu = em3[2];
-      if (_scale_pending) std::copy(sc.begin(), sc.end(), _scale_gpu.begin() + lo);
-      if (_inside_pending) for (int i = 0; i < hi - lo; ++i) _slice_inside_gpu[lo + i] = inside[i] != 0;
-      _scale_pending = _inside_pending = false;
-    } else if (_mstep_pending) {                       // one rank: M-step + E-step + whatever is still on the device, one wait
-      const int iter = _mstep_pending;
-      _mstep_pending = 0;
-      float em3[3] = {_sigma_gpu, _mix_gpu, _m_gpu};
-      std::vector<float> sc(_scale_pending ? ns : 0);
-      std::vector<unsigned char> inside(_inside_pending ? ns : 0);
-      ENG(svr_mstep_estep(reconstructionGPU, iter, (float)_step, em3, loc.data(), _scale_pending ? sc.data() : nullptr,
-                          _inside_pending ? inside.data() : nullptr));
-      _sigma_gpu = em3[0]; _mix_gpu = em3[1]; _m_gpu = em3[2];
-      if (_scale_pending) _scale_gpu = sc;
-      if (_inside_pending) for (int i = 0; i < ns; ++i) _slice_inside_gpu[i] = inside[i] != 0;
-      _scale_pending = _inside_pending = false;
-    } else {
-      if (int rc = settle()) return rc;
-      ENG(svr_estep(reconstructionGPU, _m_gpu, _sigma_gpu, _mix_gpu, loc.data()));
-    }
-    _slice_potential_gpu.assign(ns, 0.0f);
-    std::copy(loc.begin(), loc.end(), _slice_potential_gpu.begin() + lo);
-    if (sh.on) { std::vector<double> none; ENG(exchange(nullptr, 0, none, &_slice_potential_gpu)); }   // (and the scale vector)
-    // from here on in the reference's slice order (identity unless svrh_set_unit_order): RG.cc:3282-3420 op for op
-    std::vector<float> slice_potential_gpu = to_ref(_slice_potential_gpu);
-    const std::vector<float> _scale_gpu = to_ref(this->_scale_gpu);
-    std::vector<float> _slice_weight_gpu = to_ref(this->_slice_weight_gpu);
-    int inputIndex;
-    for (size_t i = 0; i < _force_excluded.size(); i++) slice_potential_gpu[ref_index(_force_excluded[i])] = -1;
-    for (size_t i = 0; i < _small_slices.size(); i++) slice_potential_gpu[ref_index(_small_slices[i])] = -1;
-    for (inputIndex = 0; inputIndex < ns; inputIndex++)
-      if ((_scale_gpu[inputIndex] < 0.2) || (_scale_gpu[inputIndex] > 5)) slice_potential_gpu[inputIndex] = -1;
-
-    double sum = 0, den = 0, sum2 = 0, den2 = 0, maxs = 0, mins = 1;
-    for (inputIndex = 0; inputIndex < ns; inputIndex++)
-      if (slice_potential_gpu[inputIndex] >= 0) {
-        sum += slice_potential_gpu[inputIndex] * _slice_weight_gpu[inputIndex];
-        den += _slice_weight_gpu[inputIndex];
-        sum2 += slice_potential_gpu[inputIndex] * (1.0 - _slice_weight_gpu[inputIndex]);
-        den2 += (1.0 - _slice_weight_gpu[inputIndex]);
-        if (slice_potential_gpu[inputIndex] > maxs) maxs = slice_potential_gpu[inputIndex];
-        if (slice_potential_gpu[inputIndex] < mins) mins = slice_potential_gpu[inputIndex];
-      }
-    if (den > 0) _mean_s_gpu = (float)(sum / den);
-    else _mean_s_gpu = (float)mins;
-    if (den2 > 0) _mean_s2_gpu = (float)(sum2 / den2);
-    else _mean_s2_gpu = (float)((maxs + _mean_s_gpu) / 2.0);
-
-    sum = 0; den = 0; sum2 = 0; den2 = 0;
-    for (inputIndex = 0; inputIndex < ns; inputIndex++)
-      if (slice_potential_gpu[inputIndex] >= 0) {
-        sum += (slice_potential_gpu[inputIndex] - _mean_s_gpu) * (slice_potential_gpu[inputIndex] - _mean_s_gpu) *
-               _slice_weight_gpu[inputIndex];
-        den += _slice_weight_gpu[inputIndex];
-        sum2 += (slice_potential_gpu[inputIndex] - _mean_s2_gpu) * (slice_potential_gpu[inputIndex] - _mean_s2_gpu) *
-                (1 - _slice_weight_gpu[inputIndex]);
-        den2 += (1 - _slice_weight_gpu[inputIndex]);
-      }
-    if ((sum > 0) && (den > 0)) {
-      _sigma_s_gpu = (float)(sum / den);
-      if (_sigma_s_gpu < _step * _step / 6.28) _sigma_s_gpu = (float)(_step * _step / 6.28);
-    } else {
-      _sigma_s_gpu = 0.025f;
-    }
-    if ((sum2 > 0) && (den2 > 0)) {
-      _sigma_s2_gpu = (float)(sum2 / den2);
-      if (_sigma_s2_gpu < _step * _step / 6.28) _sigma_s2_gpu = (float)(_step * _step / 6.28);
-    } else {
-      _sigma_s2_gpu = (_mean_s2_gpu - _mean_s_gpu) * (_mean_s2_gpu - _mean_s_gpu) / 4;
-      if (_sigma_s2_gpu < _step * _step / 6.28) _sigma_s2_gpu = (float)(_step * _step / 6.28);
-    }
-
-    double gs1, gs2;
-    for (inputIndex = 0; inputIndex < ns; inputIndex++) {
-      if (slice_potential_gpu[inputIndex] == -1) { _slice_weight_gpu[inputIndex] = 0; continue; }
-      if ((den <= 0) || (_mean_s2_gpu <= _mean_s_gpu)) { _slice_weight_gpu[inputIndex] = 1; continue; }
-      if (slice_potential_gpu[inputIndex] < _mean_s2_gpu) gs1 = G(slice_potential_gpu[inputIndex] - _mean_s_gpu, _sigma_s_gpu);
-      else gs1 = 0;
-      if (slice_potential_gpu[inputIndex] > _mean_s_gpu) gs2 = G(slice_potential_gpu[inputIndex] - _mean_s2_gpu, _sigma_s2_gpu);
-      else gs2 = 0;
-      double likelihood = gs1 * _mix_s_gpu + gs2 * (1 - _mix_s_gpu);
-      if (likelihood > 0) _slice_weight_gpu[inputIndex] = (float)(gs1 * _mix_s_gpu / likelihood);
-      else {
-        if (slice_potential_gpu[inputIndex] <= _mean_s_gpu) _slice_weight_gpu[inputIndex] = 1;
-        if (slice_potential_gpu[inputIndex] >= _mean_s2_gpu) _slice_weight_gpu[inputIndex] = 0;
-        if ((slice_potential_gpu[inputIndex] < _mean_s2_gpu) && (slice_potential_gpu[inputIndex] > _mean_s_gpu))
-          _slice_weight_gpu[inputIndex] = 1;
-      }
-    }
-    sum = 0;
-    int num = 0;
-    for (inputIndex = 0; inputIndex < ns; inputIndex++)
-      if (slice_potential_gpu[inputIndex] >= 0) { sum += _slice_weight_gpu[inputIndex]; num++; }
-    if (num > 0) _mix_s_gpu = (float)(sum / num);
-    else _mix_s_gpu = 0.9f;
-    this->_slice_weight_gpu = from_ref(_slice_weight_gpu);
-    _slice_potential_gpu = from_ref(slice_potential_gpu);
-    ENG(svr_update_slice_weights(reconstructionGPU, local(this->_slice_weight_gpu)));
-    return 0;
-  }
-
-  // RG.cc:3751-3757
+  // RG.cc:3751-3757.  Fetched with the M-step's sums / the E-step's potentials, or by settle; sharded, read next in the E-step,
+  // whose exchange completes it.
   int ScaleGPU() {
-    if (!sh.on) {
-      ENG(svr_calculate_scale_vector(reconstructionGPU, nullptr));
-      _scale_pending = true;
-      return 0;
-    }
-    ENG(svr_calculate_scale_vector(reconstructionGPU, nullptr));   // sharded: fetched with the M-step's sums (or by settle)
-    _scale_pending = true;
-    _scale_stale = true;                               // read next in the E-step, whose exchange completes it
+    ENG(svr_calculate_scale_vector(reconstructionGPU, nullptr));
+    em.scale_pending = true;
+    if (sh.on) em.scale_stale = true;
     return 0;
   }
 
   // RG.cc:4024-4036
   int SuperresolutionGPU(int iter) {
-    // (the slice weights of a device-side EM are already where the scatter reads them: NULL = keep the device's)
-    const float *sw = _em_on_host ? local(_slice_weight_gpu) : nullptr;
-    if (!sw) ENG(svr_slice_em_apply_weights(reconstructionGPU));   // (whatever anybody sent the engine in between: the EM's weights, device to device)
+    const float *sw;
+    if (int rc = em.scatter_weights(&sw)) return rc;
     if (!sh.on) {
       ENG(svr_superresolution(reconstructionGPU, iter, sw, _adaptive, (float)_alpha,
                               (float)_min_intensity, (float)_max_intensity, (float)_delta, (float)_lambda,
@@ -430,54 +154,7 @@ class irtkReconstruction {
   }
 
   // RG.cc:4214-4223 + Reconstruction::MStep host part (reconstruction_cuda2.cu:3016-3071)
-  int MStepGPU(int iter) {
-    if (!sh.on) {
-      if (_mstep_pending) { if (int rc = settle()) return rc; }   // (an M-step after an M-step; the scale vector and slice_inside stay pending for the fused fetch)
-      if (iter > 0) {
-        _mstep_pending = iter;                         // runs with the E-step that follows (reconstruction.cc:1093-1108), or in settle
-        return 0;
-      }
-      if (int rc = settle()) return rc;                // iter == 0: the host's sigma / mix are the M-step's inputs -- what the device holds comes down first
-      ENG(svr_mstep(reconstructionGPU, iter, (float)_step, &_sigma_gpu, &_mix_gpu, &_m_gpu));
-      return 0;
-    }
-    if (device_em && sh.coll.allgather_device && iter > 0) {
-      if (_mstep_pending) { if (int rc = settle()) return rc; }
-      _mstep_pending = iter;                           // runs with the E-step that follows, its sums meeting on the device (EStepGPU), or in settle
-      return 0;
-    }
-    return mstep_exchange(iter);
-  }
-  // the M-step of a sharded run through the hosts: this rank's five sums, one exchange, the scalars on the host
-  bool device_em = getenv("SVR_DEVICE_EM") ? atoi(getenv("SVR_DEVICE_EM")) != 0 : true;
-  int mstep_exchange(int iter) {
-    double s5[5];
-    {
-      std::vector<float> sc(_scale_pending ? hi - lo : 0);
-      std::vector<unsigned char> inside(_inside_pending ? hi - lo : 0);
-      ENG(svr_mstep_sums_fetch(reconstructionGPU, s5, _scale_pending ? sc.data() : nullptr, _inside_pending ? inside.data() : nullptr));
-      if (_scale_pending) std::copy(sc.begin(), sc.end(), _scale_gpu.begin() + lo);
-      if (_inside_pending) for (int i = 0; i < hi - lo; ++i) _slice_inside_gpu[lo + i] = inside[i] != 0;
-      _scale_pending = _inside_pending = false;
-    }
-    std::vector<double> all;
-    ENG(exchange(s5, 5, all, nullptr));           // three sums, a minimum, a maximum: one collective
-    s5[0] = s5[1] = s5[2] = 0;
-    for (int r = 0; r < sh.coll.world; ++r) {
-      for (int k = 0; k < 3; ++k) s5[k] += all[5 * r + k];
-      s5[3] = r ? std::min(s5[3], all[5 * r + 3]) : all[3];
-      s5[4] = r ? std::max(s5[4], all[5 * r + 4]) : all[4];
-    }
-    float sigma = (float)s5[0], mix = (float)s5[1], num = (float)s5[2];
-    float min_ = std::min(3.402823466e+38f, (float)s5[3]);
-    float max_ = std::max(1.175494351e-38f, (float)s5[4]);
-    float step = (float)_step;
-    if (mix > 0) _sigma_gpu = sigma / mix;
-    if (_sigma_gpu < step * step / 6.28f) _sigma_gpu = step * step / 6.28f;
-    if (iter > 1) _mix_gpu = mix / num;
-    _m_gpu = 1.0f / (max_ - min_);
-    return 0;
-  }
+  int MStepGPU(int iter) { return em.mstep(iter); }
 
   // RG.cc:3904-3913, 4653-4655
   int BiasGPU() { ENG(svr_correct_bias(reconstructionGPU, _sigma_bias, _global_bias_correction)); return 0; }
@@ -684,7 +361,7 @@ void svrh_destroy(svrh_recon *r) { delete r; }
 const char *svrh_last_error(const svrh_recon *r) { return r ? r->impl.err.c_str() : "null"; }
 void svrh_set_intensity_range(svrh_recon *r, double mn, double mx) { r->impl._min_intensity = mn; r->impl._max_intensity = mx; }
 void svrh_set_smoothing_parameters(svrh_recon *r, double delta, double lambda) { r->impl.SetSmoothingParameters(delta, lambda); }
-void svrh_set_force_excluded(svrh_recon *r, const int *idx, int n) { (void)r->impl.settle(); r->impl._force_excluded.assign(idx, idx + n); }
+void svrh_set_force_excluded(svrh_recon *r, const int *idx, int n) { (void)r->impl.em.settle(); r->impl._force_excluded.assign(idx, idx + n); }
 int svrh_set_bias_correction(svrh_recon *r, int enable, double sigma_bias) {
   r->impl._disableBiasC = !enable;
   r->impl._sigma_bias = (float)sigma_bias;
@@ -723,36 +400,21 @@ int svrh_get_registration_slices(svrh_recon *r, int size3[3], float *data_or_nul
 }
 
 int svrh_set_unit_order(svrh_recon *r, const int *order_or_null) {
-  if (!r) return SVR_E_ARG;
-  svr::irtkReconstruction &m = r->impl;
-  if (int rc = m.settle()) return rc;                  // (the device's copy of the slice-level state, if it is the current one, in the old numbering)
-  m._sem_ready = false;                                // the device-side EM learns the new numbering at its next use
-  if (!order_or_null) { m.order.clear(); return SVR_OK; }
-  std::vector<char> seen(m.ns, 0);
-  for (int k = 0; k < m.ns; ++k) {
-    const int i = order_or_null[k];
-    if (i < 0 || i >= m.ns || seen[i]) { m.err = "svrh_set_unit_order: not a permutation of the slices"; return SVR_E_ARG; }
-    seen[i] = 1;
-  }
-  m.order.assign(order_or_null, order_or_null + m.ns);
-  return SVR_OK;
+  return r ? r->impl.em.set_order(order_or_null, "svrh_set_unit_order: not a permutation of the slices") : SVR_E_ARG;
 }
-void svrh_force_collectives(svrh_recon *r, int on) { if (r) { (void)r->impl.settle(); r->impl.sh.force(on != 0); } }
+void svrh_force_collectives(svrh_recon *r, int on) { if (r) { (void)r->impl.em.settle(); r->impl.sh.force(on != 0); } }
 void svrh_set_slab_update(svrh_recon *r, int on) { if (r) r->impl.sh.slabs = on != 0; }
 
 int svrh_get_state(svrh_recon *r, float *scale, float *slice_weight, float *slice_potential,
                    unsigned char *slice_inside, double s[8]) {
   if (!r) return SVR_E_ARG;
-  svr::irtkReconstruction &m = r->impl;
-  if (int rc = m.flush()) return rc;      // sharded: the scale vector / slice_inside of the other ranks may still be on their way
-  if (scale) std::copy(m._scale_gpu.begin(), m._scale_gpu.end(), scale);
-  if (slice_weight) std::copy(m._slice_weight_gpu.begin(), m._slice_weight_gpu.end(), slice_weight);
-  if (slice_potential) std::copy(m._slice_potential_gpu.begin(), m._slice_potential_gpu.end(), slice_potential);
-  if (slice_inside) std::copy(m._slice_inside_gpu.begin(), m._slice_inside_gpu.end(), slice_inside);
-  if (s) {
-    s[0] = m._sigma_gpu; s[1] = m._mix_gpu; s[2] = m._m_gpu; s[3] = m._mean_s_gpu; s[4] = m._mean_s2_gpu;
-    s[5] = m._sigma_s_gpu; s[6] = m._sigma_s2_gpu; s[7] = m._mix_s_gpu;
-  }
+  svr::UnitState &u = r->impl.em;
+  if (int rc = u.flush()) return rc;   // sharded: the scale vector / slice_inside of the other ranks may still be on their way
+  if (scale) std::copy(u.scale.begin(), u.scale.end(), scale);
+  if (slice_weight) std::copy(u.weight.begin(), u.weight.end(), slice_weight);
+  if (slice_potential) std::copy(u.potential.begin(), u.potential.end(), slice_potential);
+  if (slice_inside) std::copy(u.inside.begin(), u.inside.end(), slice_inside);
+  if (s) u.scalars(s);
   return SVR_OK;
 }
 

@@ -271,7 +271,7 @@ def test_slice_level_em_on_the_device_against_the_host_form(tiny, monkeypatch, t
 @pytest.mark.gpu
 def test_m_step_sums_meeting_on_the_device_give_the_host_exchanges_bits(tiny, monkeypatch):
     """A sharded SR iteration makes ONE host exchange since round 4: the M-step's five sums of every rank are all-gathered on the device,
-    added up there in rank order and fed to the E-step (svr_mstep_partial / svr_mstep_estep_ranks, csrc/svr_host.cpp EStepGPU) instead of
+    added up there in rank order and fed to the E-step (svr_mstep_partial / svr_mstep_estep_ranks, csrc/svr_unit_em.h UnitState::estep) instead of
     travelling through the hosts (SVR_DEVICE_EM=0: the round-3 form).  Same operations in the same order: the volume and the EM state are
     the same bits.  World 1 through the C library's RCCL communicator (the gpurun box has one GPU)."""
     import numpy as np
