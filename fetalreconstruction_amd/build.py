@@ -26,6 +26,7 @@ SRC_EM = os.path.join(HERE, "csrc", "svr_em.inc")         # the slice-level EM o
 SRC_REGUL = os.path.join(HERE, "csrc", "svr_regul.inc")     # the fused volume update (Prep + edge-preserving regulariser), #included by svr_hip.hip
 SRC_TILE = os.path.join(HERE, "csrc", "svr_tile.inc")     # the tile kernels of rounds 1-2 (fallbacks, the table's gather on coarse slices), #included by svr_hip.hip
 SRC_SMALL = os.path.join(HERE, "csrc", "svr_small.inc")   # list compaction, reductions, EM / volume / bias kernels, the NCC cost, #included by svr_hip.hip
+SRC_BIAS = os.path.join(HERE, "csrc", "svr_bias.inc")     # the bias path's Gaussians through the LDS, #included by svr_hip.hip
 SRC_RCCL_ABI = os.path.join(HERE, "csrc", "svr_rccl_abi.h")   # the hand-written slice of rccl.h (checked by tests/rccl_abi_check.cpp)
 SRC_SHARD = os.path.join(HERE, "csrc", "svr_shard.h")     # unit ranges + the one exchange per step, shared by the two host objects
 SRC_UNIT_EM = os.path.join(HERE, "csrc", "svr_unit_em.h")  # the unit-level EM and its state, shared by the two host objects
@@ -59,7 +60,7 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(f) > t for f in (SRC, SRC_REG, SRC_PYR, SRC_HOST, SRC_IO, SRC_PVR_HOST, SRC_IRTK, SRC_RCCL, SRC_PREP, SRC_SLIC, SRC_SHARD, SRC_UNIT_EM, SRC_REGUL, SRC_EM, SRC_CELL, SRC_TILE, SRC_SMALL, SRC_RCCL_ABI, SRC_SORT, SRC_CLI, SRC_PVR_CLI, INC, INC_HOST,
+    return any(os.path.getmtime(f) > t for f in (SRC, SRC_REG, SRC_PYR, SRC_HOST, SRC_IO, SRC_PVR_HOST, SRC_IRTK, SRC_RCCL, SRC_PREP, SRC_SLIC, SRC_SHARD, SRC_UNIT_EM, SRC_REGUL, SRC_EM, SRC_CELL, SRC_TILE, SRC_SMALL, SRC_BIAS, SRC_RCCL_ABI, SRC_SORT, SRC_CLI, SRC_PVR_CLI, INC, INC_HOST,
                                                __file__)) or not (os.path.exists(CLI) and os.path.exists(PVR_CLI))
 
 

@@ -373,7 +373,9 @@ __global__ void k_cell_entries(CellArgs ca, uint32_t nitems, const uint32_t *ite
 }
 
 // ---- per launch ------------------------------------------------------------------------------------------------------
-// the factors of every sorted pixel: what back_wave_kernel's "lane = pixel" part works out (RC.cu:439-447 / 278-282)
+// the factors of every sorted pixel: what back_wave_kernel's "lane = pixel" part works out (RC.cu:439-447 / 278-282).
+// gauss: 0 = the SR scatter, 1 = pass 2 of the Gaussian reconstruction, 2 = NormaliseBias (normalizeBiasKernel3D_tex RC.cu:544-550, 591:
+// weight psf / sume, value the pixel's log bias minus the log of its slice's scale)
 __global__ void k_cell_factors(PsfArgs a, int gauss, CellRec *recs, uint32_t n, unsigned char *act) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -388,7 +390,12 @@ __global__ void k_cell_factors(PsfArgs a, int gauss, CellRec *recs, uint32_t n, 
     const float sume = a.psf_sums[idx];
     const float ss = a.simslices[idx];
     float e = a.bias ? a.slices[idx] * expf(-a.bias[idx]) * a.scales[sl] : a.slices[idx] * a.scales[sl];
-    if (gauss) {
+    if (gauss == 2) {
+      e = a.bias[idx];
+      const float scale = a.scales[sl];
+      if (scale > 0) e -= logf(scale);
+      f1 = 1.0f / sume;
+    } else if (gauss) {
       f1 = 1.0f / sume;
     } else {
       e = (ss > 0.0f) ? (e - ss) : 0.0f;

@@ -16,7 +16,9 @@
 // stack-to-stack registration (StackRegistrations, before and after the other stacks are cropped, main.cc:661,711).
 // Slice-to-volume registration is the reference's default IRTK schedule (csrc/irtk_reg.cpp, every similarity evaluation
 // on the GPU) or, with --useGPUReg, the reference's GPU registration.  --no_registration (not a reference option) skips
-// both.  --packages runs PackageToVolume with the schedule of main.cc:832-864; --tfolder reads transformation<i>.dof per
+// both.  --enableBiasCorrection (not a reference option either: the reference hard-wires its bias correction off) runs
+// BiasGPU / NormaliseBiasGPU in every SR iteration with --sigma, --global_bias_correction and --low_intensity_cutoff as the
+// reference's main() would pass them.  --packages runs PackageToVolume with the schedule of main.cc:832-864; --tfolder reads transformation<i>.dof per
 // slice and --debug writes them next to the output.  Not built, refused loudly: patch/superpixel
 // modes, the CPU reconstruction path.
 #include <functional>
@@ -38,6 +40,8 @@ int main(int argc, char **argv) {
   int iterations = 4, levels = 3, rec_first = 4, rec_last = 13, num_stacks_tuner = 0;
   double resolution = 0.75, average = 700, delta = 150, lambda = 0.02, last_lambda = 0.01, smooth_mask = 4;
   bool no_matching = false, use_gpu_reg = false, no_registration = false;
+  double sigma = 12.0, low_intensity_cutoff = 0.01;                      // main.cc:172, 181
+  bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
   // ---- options (main.cc:164-211) ---------------------------------------------------------------------
   auto is_opt = [](const char *s) { return s[0] == '-' && !(s[1] >= '0' && s[1] <= '9') && s[1] != '.'; };
@@ -60,7 +64,7 @@ int main(int argc, char **argv) {
     else if (o == "-t" || o == "--transformation") multi(tspecs);
     else if (o == "--thickness") { std::vector<std::string> v; multi(v); for (auto &s : v) thickness.push_back(atof(s.c_str())); }
     else if (o == "--iterations") iterations = atoi(one().c_str());
-    else if (o == "--sigma") (void)one();                               // bias field stdev: bias correction stays disabled
+    else if (o == "--sigma") sigma = atof(one().c_str());              // bias field stdev (main.cc:172); used with --enableBiasCorrection
     else if (o == "--resolution") resolution = atof(one().c_str());
     else if (o == "--multires") levels = atoi(one().c_str());
     else if (o == "--average") average = atof(one().c_str());
@@ -70,8 +74,11 @@ int main(int argc, char **argv) {
     else if (o == "--smooth_mask") smooth_mask = atof(one().c_str());
     else if (o == "--no_intensity_matching") no_matching = !opt_bool(false);   // the value lands in `intensity_matching` (main.cc:186): 0 switches it off
     else if (o == "--num_stacks_tuner") num_stacks_tuner = atoi(one().c_str());
-    else if (o == "--log_prefix" || o == "--low_intensity_cutoff" || o == "--patchSize" || o == "--patchStride") (void)one();   // no log files; bias / patch modes are off
-    else if (o == "--no_log" || o == "--global_bias_correction") (void)opt_bool(true);
+    else if (o == "--low_intensity_cutoff") low_intensity_cutoff = atof(one().c_str());   // passed to SuperresolutionGPU, which does not use it (as in the reference)
+    else if (o == "--global_bias_correction") global_bias = opt_bool(true);
+    else if (o == "--enableBiasCorrection") enable_bias = true;          // not a reference option: the reference hard-wires disableBiasCorr (main.cc:121,202)
+    else if (o == "--log_prefix" || o == "--patchSize" || o == "--patchStride") (void)one();   // no log files; patch modes are off
+    else if (o == "--no_log") (void)opt_bool(true);
     else if (o == "--force_exclude") { std::vector<std::string> v; multi(v); for (auto &s : v) force_excluded.push_back(atoi(s.c_str())); }
     else if (o == "--rec_iterations_first") rec_first = atoi(one().c_str());
     else if (o == "--rec_iterations_last") rec_last = atoi(one().c_str());
@@ -93,7 +100,11 @@ int main(int argc, char **argv) {
              "       [--iterations 4] [--resolution 0.75] [--multires 3] [--average 700] [--delta 150] [--lambda 0.02]\n"
              "       [--lastIterLambda 0.01] [--smooth_mask 4] [--no_intensity_matching] [--force_exclude i ..]\n"
              "       [--rec_iterations_first 4] [--rec_iterations_last 13] [--packages p_1 ..] [--useGPUReg] [--no_registration] [--tfolder dir] [--sfolder dir]\n"
-             "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n");
+             "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n"
+             "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection]\n"
+             "  --enableBiasCorrection  deviation from the reference, whose bias correction cannot be switched on: run BiasGPU and\n"
+             "                          NormaliseBiasGPU in every SR iteration (bias field stdev --sigma mm; sigma <= 0: no bias step).\n"
+             "                          Without it bias correction is off, as in the reference; --disableBiasCorrection is accepted and changes nothing.\n");
       return 0;
     } else {
       die("option " + o + " is not supported by this build (see csrc/svr_cli.cpp)");
@@ -346,6 +357,10 @@ int main(int argc, char **argv) {
     if (!hosts[r]) die("svrh_create failed");
     svrh_set_intensity_range(hosts[r], vmin, vmax);                      // InitializeEMGPU RG.cc:2937-2951
     svrh_set_intensity_matching(hosts[r], no_matching ? 0 : 1);         // main.cc:1018, 1062
+    // SetSigma / GlobalBiasCorrectionOn / SetLowIntensityCutoff (main.cc:451, 764-778); the steps themselves are gated on the option
+    // sigma > 0 (main.cc:1025,1035,1069), so sigma <= 0 leaves the member at 20 and runs no bias step
+    HOSTR(r, svrh_set_bias_correction(hosts[r], enable_bias && sigma > 0, sigma > 0 ? sigma : 20.0));
+    HOSTR(r, svrh_set_bias_options(hosts[r], global_bias ? 1 : 0, low_intensity_cutoff));
     if (nr > 1 && svrh_set_unit_order(hosts[r], order.data())) die("svrh_set_unit_order failed");
     if (!force_excluded.empty()) svrh_set_force_excluded(hosts[r], force_excluded.data(), (int)force_excluded.size());
     if (use_gpu_reg) HOSTR(r, svrh_prepare_registration_slices(hosts[r], grid.data() + o * mx * my, mx, my, sattr.data() + o, resolution));
@@ -449,6 +464,12 @@ int main(int argc, char **argv) {
         if (svr_dof_write(("croppedSliceToVolumeTransformation" + std::to_string(i) + ".dof").c_str(), p6, e)) die(std::string("dof file: ") + e);
       }
     }
+  }
+  if (clk.on && enable_bias && sigma > 0) {                              // which bias stages ran (rank 0)
+    int nb = 0, nn = 0;
+    ENG(svr_get_option(ctx, "bias_corrections", &nb));
+    ENG(svr_get_option(ctx, "bias_normalisations", &nn));
+    fprintf(stderr, "[timing] bias correction: %d CorrectBias, %d NormaliseBias\n", nb, nn);
   }
   par([&](int r) {                                                       // main.cc:1189-1193
     ENGR(r, svr_restore_slice_intensities(ctxs[r], factors.data(), (int)factors.size(), stack_index.data() + rlo[r]));

@@ -1049,6 +1049,7 @@ __global__ __launch_bounds__(64) void k_probe_pixel(PsfArgs a, uint32_t idx, flo
 }
 
 #include "svr_small.inc"   // list compaction, reductions, the EM / scale / bias / volume kernels, the NCC cost of the IRTK registration
+#include "svr_bias.inc"    // the bias path's Gaussians through the LDS (bias_mode 1)
 
 }  // namespace
 
@@ -1219,6 +1220,13 @@ struct svr_ctx {
   float *d_bias = nullptr, *d_wb = nullptr, *d_wr = nullptr, *d_buffer = nullptr;       // slice grid
   float *d_bias_vol = nullptr, *d_volume_weights = nullptr, *d_maskC = nullptr, *d_mbuf = nullptr;   // volume
   float mask_sigma_bias = 12.0f;
+  // option "bias_mode": 1 (default) = NormaliseBias scatters on the cell kernels, CorrectBias on the LDS kernel of svr_bias.inc, the NormaliseBias
+  // tail on its LDS kernels from BIAS_LDS_TAIL_MIN voxels on (below, the stencils are as fast: P4 0.18 vs 0.20 ms); 2 = the same with the LDS
+  // tail at every size; 0 = round 1's kernels (psf_kernel<MODE_BIAS> with float atomics, the stencils of svr_small.inc).  The Gaussians give
+  // the same bits in every mode
+  int bias_mode = 1;
+  int bias_corrections = 0, bias_normalisations = 0;   // CorrectBias / NormaliseBias (finish) calls that ran (svr_get_option)
+  int bias_scatters = 0, bias_scatters_on_cells = 0;   // NormaliseBias scatters, and those of them that ran on the cell kernels
   bool maskC_valid = false;
 
   // registration cost (NCC)
@@ -1707,7 +1715,9 @@ int coeff_prepare(svr_ctx *ctx, const uint32_t **list) {
     const size_t bytes = npx * per_px * sizeof(float4);
     const char *cap_gb = getenv("SVR_COEFF_MAX_GB");     // optional ceiling on the table (GiB): a deployment knob, and how the tests reach the fallback
     const bool over = cap_gb && (double)bytes > atof(cap_gb) * 1073741824.0;
-    if (over || hipMemGetInfo(&fr, &tot) != hipSuccess || bytes + (size_t(2) << 30) > fr || hipMalloc(&ctx->d_coeff, bytes) != hipSuccess) {
+    // the bias buffers are allocated before the first pass (svr_set_flags / ready); any still missing count in the headroom
+    const size_t bias_later = ctx->disable_bias ? 0 : (ctx->d_bias ? 0 : 4 * ctx->np * sizeof(float)) + (ctx->d_bias_vol ? 0 : 4 * ctx->nv * sizeof(float));
+    if (over || hipMemGetInfo(&fr, &tot) != hipSuccess || bytes + bias_later + (size_t(2) << 30) > fr || hipMalloc(&ctx->d_coeff, bytes) != hipSuccess) {
       (void)hipGetLastError();
       ctx->d_coeff = nullptr;
       ctx->coeff_mode = 0;                                 // does not fit: evaluate on the fly (svr_get_option tells)
@@ -2117,6 +2127,7 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
     return SVR_OK;
   }
   if (!strcmp(name, "reg_batch")) { ctx->reg_batch = value ? 1 : 0; return SVR_OK; }
+  if (!strcmp(name, "bias_mode")) { if (value < 0 || value > 2) return fail(ctx, SVR_E_ARG, "bias_mode: 0, 1 or 2"); ctx->bias_mode = value; return SVR_OK; }
   if (!strcmp(name, "pvr_reg_levels")) { ctx->pvr_reg_levels = std::min(3, std::max(1, value)); return SVR_OK; }
   if (!strcmp(name, "pvr_reg_steps")) { ctx->pvr_reg_steps = std::max(1, value); return SVR_OK; }
   if (!strcmp(name, "pvr_reg_iterations")) { ctx->pvr_reg_iterations = std::max(1, value); return SVR_OK; }
@@ -2148,7 +2159,9 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value) {
   const struct { const char *n; int v; } tab[] = {
       {"back_mode", back_mode_eff(ctx)}, {"reg_mode", ctx->reg_mode}, {"fwd_mode", ctx->fwd_mode}, {"gauss_mode", ctx->gauss_mode}, {"pvr_mode", ctx->pvr_mode},
       {"pvr", ctx->pvr}, {"coeff_table", ctx->coeff_mode}, {"coeff_lazy", ctx->coeff_lazy}, {"coeff_valid", ctx->coeff_valid ? 1 : 0}, {"tile_w", ctx->tile_w}, {"tile_h", ctx->tile_h},
-      {"fwd_tile_w", ctx->fwd_tw}, {"fwd_tile_h", ctx->fwd_th}, {"wave_cap", ctx->wave_cap}, {"cell_w", csw}, {"cell_h", csh}, {"cell_gw", cgw}, {"cell_gh", cgh}, {"cell_split", ctx->cell_split}, {"cell_order", ctx->cell_order}, {"cell_balance", ctx->cell_balance}, {"cell_combine", ctx->cell_combine}, {"fwd_autotune", ctx->fwd_autotune}, {"cell_qx", ctx->cell_qx}, {"fwd_unit_cap", ctx->fwd_unit_cap}, {"reg_batch", ctx->reg_batch}, {"reg_blind", ctx->reg_blind}};
+      {"fwd_tile_w", ctx->fwd_tw}, {"fwd_tile_h", ctx->fwd_th}, {"wave_cap", ctx->wave_cap}, {"cell_w", csw}, {"cell_h", csh}, {"cell_gw", cgw}, {"cell_gh", cgh}, {"cell_split", ctx->cell_split}, {"cell_order", ctx->cell_order}, {"cell_balance", ctx->cell_balance}, {"cell_combine", ctx->cell_combine}, {"fwd_autotune", ctx->fwd_autotune}, {"cell_qx", ctx->cell_qx}, {"fwd_unit_cap", ctx->fwd_unit_cap}, {"reg_batch", ctx->reg_batch}, {"reg_blind", ctx->reg_blind},
+      {"bias_mode", ctx->bias_mode}, {"bias_corrections", ctx->bias_corrections}, {"bias_normalisations", ctx->bias_normalisations},
+      {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells}};
   for (const auto &e : tab)
     if (!strcmp(name, e.n)) { *value = e.v; return SVR_OK; }
   return fail(ctx, SVR_E_ARG, std::string("unknown option ") + name);
@@ -2195,6 +2208,8 @@ int svr_set_flags(svr_ctx *ctx, int disable_bias_correction, int debug_gpu) {
   if (!ctx) return SVR_E_ARG;
   ctx->disable_bias = disable_bias_correction != 0;
   ctx->debug_gpu = debug_gpu != 0;
+  // with the geometry known, the bias buffers come now, before a coefficient table sizes itself on the free memory
+  if (!ctx->disable_bias) { HIPCHK(hipSetDevice(ctx->device)); return ensure_bias_buffers(ctx); }
   return SVR_OK;
 }
 
@@ -3631,6 +3646,23 @@ int svr_correct_bias(svr_ctx *ctx, float sigma_bias, int global_bias_correction)
   if (r) return r;
   const size_t fb = ctx->np * sizeof(float);
   const int n2 = (int)(ctx->sx * ctx->sy);
+  ++ctx->bias_corrections;
+  // bias_mode 1: residual, the four passes and the update in one kernel, a strip of bx columns per workgroup (svr_bias.inc); the
+  // widest strip whose LDS fits 64 KiB, else the stencils.  The new field lands in d_buffer, which becomes d_bias.
+  int bx = 0, half = 0;
+  if (ctx->bias_mode >= 1) {
+    for (uint32_t sl = 0; sl < ctx->ns; ++sl) half = std::max(half, gauss_half_host(sigma_bias, ctx->slice_dims[3 * (size_t)sl]));
+    for (int b = 64; b >= 8 && !bx; b /= 2)
+      if (half <= BIAS_HMAX && bias_field_lds_bytes((int)ctx->sy, b, half) <= 65536) bx = b;
+  }
+  if (bx) {
+    const dim3 grid(((int)ctx->sx + bx - 1) / bx, ctx->ns);
+    hipLaunchKernelGGL(k_bias_field_lds, grid, dim3(256), bias_field_lds_bytes((int)ctx->sy, bx, half), ctx->stream,
+                       ctx->d_slices, ctx->d_bias, ctx->d_weights, ctx->d_simweights, ctx->d_simslices, ctx->d_scales, ctx->d_sc,
+                       (int)ctx->sx, (int)ctx->sy, sigma_bias, bx, ctx->d_buffer);
+    KCHK("k_bias_field_lds");
+    std::swap(ctx->d_bias, ctx->d_buffer);
+  } else {
   HIPCHK(hipMemsetAsync(ctx->d_wb, 0, fb, ctx->stream));       // RC.cu:1873-1875
   HIPCHK(hipMemsetAsync(ctx->d_wr, 0, fb, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_buffer, 0, fb, ctx->stream));
@@ -3650,6 +3682,7 @@ int svr_correct_bias(svr_ctx *ctx, float sigma_bias, int global_bias_correction)
   hipLaunchKernelGGL(k_bias_update, dim3(nblk(ctx->np)), dim3(256), 0, ctx->stream, ctx->d_slices, ctx->d_bias, ctx->d_wb,
                      ctx->d_wr, ctx->np);
   KCHK("k_bias_update");
+  }
   if (!global_bias_correction) {
     hipLaunchKernelGGL(k_bias_mean, dim3(ctx->chunks, ctx->ns), dim3(256), 0, ctx->stream, ctx->d_slices, ctx->d_bias, n2,
                        ctx->d_partial);
@@ -3674,10 +3707,28 @@ int svr_normalise_bias_local(svr_ctx *ctx) {
   if (r) return r;
   r = ensure_psf_list(ctx);
   if (r) return r;
-  HIPCHK(hipMemsetAsync(ctx->d_bias_vol, 0, ctx->nv * sizeof(float), ctx->stream));   // RC.cu:2621
+  ++ctx->bias_scatters;
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
+  // bias_mode >= 1: the SR scatter's cell kernels (no atomics: the same bits from run to run, with the coefficient table or without) --
+  // factors f1 = 1 / sume, f0 = f1 (bias - log scale) over the PSF pixels, back_cell_kernel (streaming the table when it is valid:
+  // NormaliseBias follows SuperresolutionGPU on the same geometry), the combine writes bias_vol and this call's weights, which are
+  // then added to the never-cleared dev_volume_weights_.  A sharded rank scatters its own slices through its own cell lists.
+  if (ctx->bias_mode >= 1 && a.n && !ctx->pvr && back_mode_eff(ctx) == 5) {
+    if ((r = cell_prepare(ctx))) return r;
+    if (ctx->cell->usable) {
+      if (ctx->coeff_mode && ctx->coeff_valid) give_coeff(ctx, a);
+      if ((r = launch_cell_scatter(ctx, a, 2, ctx->d_bias_vol, ctx->d_mbuf))) return r;
+      hipLaunchKernelGGL(k_add_to, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->d_volume_weights, ctx->d_mbuf, ctx->nv);
+      KCHK("k_add_to");
+      ++ctx->bias_scatters_on_cells;
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      return SVR_OK;
+    }
+    ctx->note_fallback(0, "the NormaliseBias scatter left the cell path (the cell lists cannot hold this geometry): float atomics, last bits depend on the run");
+  }
+  HIPCHK(hipMemsetAsync(ctx->d_bias_vol, 0, ctx->nv * sizeof(float), ctx->stream));   // RC.cu:2621
   a.recon = ctx->d_bias_vol;            // scattered value: psf/sume * (bias - log scale)
   a.volw = ctx->d_volume_weights;       // dev_volume_weights_: accumulates, never cleared (RC.cu:2633)
   if (a.n) {
@@ -3696,6 +3747,32 @@ int svr_normalise_bias_finish(svr_ctx *ctx, float sigma_bias) {
   if (!ctx) return SVR_E_ARG;
   NEED(!ctx->disable_bias && ctx->d_bias_vol && ctx->maskC_valid, "bias buffers not ready");
   const size_t nv = ctx->nv;
+  ++ctx->bias_normalisations;
+  if (ctx->bias_mode == 2 || (ctx->bias_mode == 1 && nv >= BIAS_LDS_TAIL_MIN)) {
+    // svr_bias.inc: x lines (with divS by the weights), y and z columns (with the copy, divS by maskC and divexp)
+    // through the LDS; the widest strips whose LDS fits 64 KiB, else the stencils below
+    const int vx = (int)ctx->vx, vy = (int)ctx->vy, vz = (int)ctx->vz;
+    int half = 0;
+    for (int d = 0; d < 3; ++d) half = std::max(half, gauss_half_host(sigma_bias, ctx->vdim[d]));
+    const size_t gb = (BIAS_HMAX + 1) * sizeof(float), cap = 65536;
+    int rows = 0, bxy = 0, bxz = 0;
+    for (int r = 16; r >= 1 && !rows; r /= 2) if (gb + (size_t)r * vx * 4 <= cap) rows = r;
+    for (int b = 64; b >= 4 && !bxy; b /= 2) if (gb + (size_t)vy * b * 4 <= cap) bxy = b;
+    for (int b = 64; b >= 4 && !bxz; b /= 2) if (gb + (size_t)vz * b * 4 <= cap) bxz = b;
+    if (half <= BIAS_HMAX && rows && bxy && bxz) {
+      const int nlines = vy * vz;
+      hipLaunchKernelGGL(k_gauss3d_x_lds, dim3((nlines + rows - 1) / rows), dim3(256), gb + (size_t)rows * vx * 4, ctx->stream,
+                         ctx->d_bias_vol, ctx->volw(), ctx->d_mbuf, sigma_bias, ctx->vdim[0], vx, nlines, rows);
+      hipLaunchKernelGGL(k_gauss3d_col_lds<false>, dim3((vx + bxy - 1) / bxy, vz), dim3(256), gb + (size_t)vy * bxy * 4, ctx->stream,
+                         ctx->d_mbuf, ctx->d_bias_vol, (const float *)nullptr, (const float *)nullptr, (float *)nullptr, sigma_bias,
+                         ctx->vdim[1], vx, vy, vz, bxy);
+      hipLaunchKernelGGL(k_gauss3d_col_lds<true>, dim3((vx + bxz - 1) / bxz, vy), dim3(256), gb + (size_t)vz * bxz * 4, ctx->stream,
+                         ctx->d_bias_vol, ctx->d_bias_vol, ctx->d_mbuf, ctx->d_maskC, ctx->recon(), sigma_bias, ctx->vdim[2], vx, vy, vz, bxz);
+      KCHK("k_gauss3d_*_lds");
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      return SVR_OK;
+    }
+  }
   const dim3 grid((ctx->vx + 63) / 64, (ctx->vy + 3) / 4, ctx->vz);
   hipLaunchKernelGGL(k_div_s, dim3(nblk(nv)), dim3(256), 0, ctx->stream, ctx->d_bias_vol, ctx->volw(), nv);   // RC.cu:2553-2556
   // the reference's mbuf is uninitialised device memory (RC.cu:2563-2564); zero it so a NaN result is defined

@@ -178,7 +178,7 @@ class irtkReconstruction {
     return 0;
   }
 
-  // reconstruction.cc:1013-1108 with bias correction off
+  // reconstruction.cc:1013-1108; the bias steps run when bias correction is enabled (svrh_set_bias_correction)
   int sr_iteration(int i) {
     int rc;
     if (_intensity_matching) {                                               // reconstruction.cc:1018-1045
@@ -366,6 +366,12 @@ int svrh_set_bias_correction(svrh_recon *r, int enable, double sigma_bias) {
   r->impl._disableBiasC = !enable;
   r->impl._sigma_bias = (float)sigma_bias;
   return svr_set_flags(r->impl.reconstructionGPU, !enable, 0);
+}
+int svrh_set_bias_options(svrh_recon *r, int global_bias_correction, double low_intensity_cutoff) {
+  if (!r) return SVR_E_ARG;
+  r->impl._global_bias_correction = global_bias_correction != 0;                      // GlobalBiasCorrectionOn/Off
+  r->impl._low_intensity_cutoff = (float)std::min(1.0, std::max(0.0, low_intensity_cutoff));   // SetLowIntensityCutoff RG.h:596-602
+  return SVR_OK;
 }
 int svrh_bias_gpu(svrh_recon *r) { return r->impl.BiasGPU(); }
 int svrh_normalise_bias_gpu(svrh_recon *r, int iter) { return r->impl.NormaliseBiasGPU(iter); }

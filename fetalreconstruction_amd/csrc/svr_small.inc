@@ -580,6 +580,11 @@ __global__ void k_div_s(float *a, const float *b, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { float d = b[i]; a[i] = (d != 0) ? a[i] / d : 0; }
 }
+// a += b (NormaliseBias on the cell path: dev_volume_weights_ accumulates over the calls, RC.cu:2633)
+__global__ void k_add_to(float *a, const float *b, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) a[i] += b[i];
+}
 // divexp RC.cu:2505-2516
 __global__ void k_divexp(float *recon, const float *bias, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -21,7 +21,7 @@ HOST_EXPORTS = [
     "svrh_set_force_excluded", "svrh_initialize_em_values_gpu", "svrh_gaussian_reconstruction_gpu",
     "svrh_simulate_slices_gpu", "svrh_initialize_robust_statistics_gpu", "svrh_estep_gpu", "svrh_scale_gpu",
     "svrh_superresolution_gpu", "svrh_mstep_gpu", "svrh_mask_volume_gpu", "svrh_scale_volume_gpu",
-    "svrh_sr_iteration", "svrh_reconstruct_iteration", "svrh_get_state", "svrh_set_bias_correction", "svrh_bias_gpu",
+    "svrh_sr_iteration", "svrh_reconstruct_iteration", "svrh_get_state", "svrh_set_bias_correction", "svrh_set_bias_options", "svrh_bias_gpu",
     "svrh_normalise_bias_gpu", "svrh_prepare_registration_slices", "svrh_slice_to_volume_registration_gpu",
     "svrh_get_registration_slices", "svrh_force_collectives", "svrh_set_slab_update", "svrh_set_unit_order",
 ]
@@ -272,6 +272,10 @@ class irtkReconstruction:
 
     def set_bias_correction(self, enable, sigma_bias=12.0):
         self._ck(self._lib.svrh_set_bias_correction(self._h, int(bool(enable)), C.c_double(sigma_bias)))
+
+    def set_bias_options(self, global_bias_correction=False, low_intensity_cutoff=0.01):
+        """GlobalBiasCorrectionOn/Off + SetLowIntensityCutoff (the cutoff is clamped to [0, 1])"""
+        self._ck(self._lib.svrh_set_bias_options(self._h, int(bool(global_bias_correction)), C.c_double(low_intensity_cutoff)))
 
     def BiasGPU(self):
         self._ck(self._lib.svrh_bias_gpu(self._h))

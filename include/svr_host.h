@@ -101,6 +101,10 @@ void svrh_set_intensity_matching(svrh_recon *r, int on);
 
 /* disableBiasCorrection() RG.cc:234-238 / SetSigma RG.h:376; BiasGPU RG.cc:3904-3913, NormaliseBiasGPU RG.cc:4653 */
 int svrh_set_bias_correction(svrh_recon *r, int enable, double sigma_bias);
+/* GlobalBiasCorrectionOn/Off and SetLowIntensityCutoff (RG.h:398-404, 596-602; reconstruction.cc:451, 775-778): global = 1
+ * makes CorrectBias skip the per-slice mean (the reference's GPU path has no global correction) and skips NormaliseBias;
+ * the cutoff (clamped to [0, 1]) reaches SuperresolutionGPU, which does not use it */
+int svrh_set_bias_options(svrh_recon *r, int global_bias_correction, double low_intensity_cutoff);
 int svrh_bias_gpu(svrh_recon *r);
 int svrh_normalise_bias_gpu(svrh_recon *r, int iter);
 
@@ -114,7 +118,7 @@ int svrh_superresolution_gpu(svrh_recon *r, int iter);
 int svrh_mstep_gpu(svrh_recon *r, int iter);
 int svrh_mask_volume_gpu(svrh_recon *r);
 int svrh_scale_volume_gpu(svrh_recon *r);
-/* one SR iteration of reconstruction.cc:1013-1108 (bias off) */
+/* one SR iteration of reconstruction.cc:1013-1108 (with BiasGPU / NormaliseBiasGPU when bias correction is enabled) */
 int svrh_sr_iteration(svrh_recon *r, int i);
 /* Gaussian init + robust-statistics init + rec_iterations SR iterations + MaskVolume
  * (reconstruction.cc:930-1140) */
