@@ -1227,6 +1227,11 @@ struct svr_ctx {
   int bias_mode = 1;
   int bias_corrections = 0, bias_normalisations = 0;   // CorrectBias / NormaliseBias (finish) calls that ran (svr_get_option)
   int bias_scatters = 0, bias_scatters_on_cells = 0;   // NormaliseBias scatters, and those of them that ran on the cell kernels
+  // what the last launches chose (read-only options, so a test can tell which branch it reached; -1 = not launched yet):
+  // CorrectBias's strip width (0 = the stencils), the NormaliseBias tail on the LDS kernels (0/1) with its x rows and y / z strip
+  // widths (0 when the stencils ran), the fused volume update's planes per z-chunk and chunks
+  int last_bias_bx = -1, last_tail_lds = -1, last_tail_rows = -1, last_tail_bxy = -1, last_tail_bxz = -1;
+  int last_reg_zc = -1, last_reg_chunks = -1;
   bool maskC_valid = false;
 
   // registration cost (NCC)
@@ -2161,7 +2166,9 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value) {
       {"pvr", ctx->pvr}, {"coeff_table", ctx->coeff_mode}, {"coeff_lazy", ctx->coeff_lazy}, {"coeff_valid", ctx->coeff_valid ? 1 : 0}, {"tile_w", ctx->tile_w}, {"tile_h", ctx->tile_h},
       {"fwd_tile_w", ctx->fwd_tw}, {"fwd_tile_h", ctx->fwd_th}, {"wave_cap", ctx->wave_cap}, {"cell_w", csw}, {"cell_h", csh}, {"cell_gw", cgw}, {"cell_gh", cgh}, {"cell_split", ctx->cell_split}, {"cell_order", ctx->cell_order}, {"cell_balance", ctx->cell_balance}, {"cell_combine", ctx->cell_combine}, {"fwd_autotune", ctx->fwd_autotune}, {"cell_qx", ctx->cell_qx}, {"fwd_unit_cap", ctx->fwd_unit_cap}, {"reg_batch", ctx->reg_batch}, {"reg_blind", ctx->reg_blind},
       {"bias_mode", ctx->bias_mode}, {"bias_corrections", ctx->bias_corrections}, {"bias_normalisations", ctx->bias_normalisations},
-      {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells}};
+      {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells},
+      {"bias_field_bx", ctx->last_bias_bx}, {"bias_tail_lds", ctx->last_tail_lds}, {"bias_tail_rows", ctx->last_tail_rows},
+      {"bias_tail_bxy", ctx->last_tail_bxy}, {"bias_tail_bxz", ctx->last_tail_bxz}, {"reg_zc", ctx->last_reg_zc}, {"reg_chunks", ctx->last_reg_chunks}};
   for (const auto &e : tab)
     if (!strcmp(name, e.n)) { *value = e.v; return SVR_OK; }
   return fail(ctx, SVR_E_ARG, std::string("unknown option ") + name);
@@ -3331,6 +3338,7 @@ static int superresolution_update_planes(svr_ctx *ctx, int adaptive, float alpha
   const int want = std::max(1, (2048 * 512 / (TW * TH) + tiles - 1) / tiles);   // chunks along z for >= 2048 workgroups of 512 lanes
   ra.zc = std::min(32, std::max(4, (nz + want - 1) / want));
   const int chunks = (nz + ra.zc - 1) / ra.zc;
+  ctx->last_reg_zc = ra.zc; ctx->last_reg_chunks = chunks;
   for (int k = 0; k < 3; ++k) { ra.blo[k] = 0; ra.bhi[k] = -1; }
   if (ctx->mbox_valid && ctx->cmap_from_scatter) {
     const int dims[3] = {ra.vx, ra.vy, ra.vz};
@@ -3655,6 +3663,7 @@ int svr_correct_bias(svr_ctx *ctx, float sigma_bias, int global_bias_correction)
     for (int b = 64; b >= 8 && !bx; b /= 2)
       if (half <= BIAS_HMAX && bias_field_lds_bytes((int)ctx->sy, b, half) <= 65536) bx = b;
   }
+  ctx->last_bias_bx = bx;
   if (bx) {
     const dim3 grid(((int)ctx->sx + bx - 1) / bx, ctx->ns);
     hipLaunchKernelGGL(k_bias_field_lds, grid, dim3(256), bias_field_lds_bytes((int)ctx->sy, bx, half), ctx->stream,
@@ -3760,6 +3769,7 @@ int svr_normalise_bias_finish(svr_ctx *ctx, float sigma_bias) {
     for (int b = 64; b >= 4 && !bxy; b /= 2) if (gb + (size_t)vy * b * 4 <= cap) bxy = b;
     for (int b = 64; b >= 4 && !bxz; b /= 2) if (gb + (size_t)vz * b * 4 <= cap) bxz = b;
     if (half <= BIAS_HMAX && rows && bxy && bxz) {
+      ctx->last_tail_lds = 1; ctx->last_tail_rows = rows; ctx->last_tail_bxy = bxy; ctx->last_tail_bxz = bxz;
       const int nlines = vy * vz;
       hipLaunchKernelGGL(k_gauss3d_x_lds, dim3((nlines + rows - 1) / rows), dim3(256), gb + (size_t)rows * vx * 4, ctx->stream,
                          ctx->d_bias_vol, ctx->volw(), ctx->d_mbuf, sigma_bias, ctx->vdim[0], vx, nlines, rows);
@@ -3773,6 +3783,7 @@ int svr_normalise_bias_finish(svr_ctx *ctx, float sigma_bias) {
       return SVR_OK;
     }
   }
+  ctx->last_tail_lds = 0; ctx->last_tail_rows = ctx->last_tail_bxy = ctx->last_tail_bxz = 0;
   const dim3 grid((ctx->vx + 63) / 64, (ctx->vy + 3) / 4, ctx->vz);
   hipLaunchKernelGGL(k_div_s, dim3(nblk(nv)), dim3(256), 0, ctx->stream, ctx->d_bias_vol, ctx->volw(), nv);   // RC.cu:2553-2556
   // the reference's mbuf is uninitialised device memory (RC.cu:2563-2564); zero it so a NaN result is defined
