@@ -101,7 +101,7 @@ struct CellState {
   unsigned char *d_act = nullptr;      // PSF-pixel flags of the sorted records for the scatter that writes the table (k_cell_factors)
   size_t cap_pid = 0, cap_act = 0;
   bool pid_valid = false;
-  bool gf_valid = false;               // d_gf matches v_PSF_sums (it changes with a Gaussian pass, not with an SR iteration: cell_gf_invalidate)
+  bool gf_valid = false;               // d_gf matches v_PSF_sums (it changes with a Gaussian pass, not with an SR iteration: CH_PSF_SUMS)
   void *d_tmp = nullptr;
   int *d_range = nullptr;              // [2][6] min / max of the centres, [12] dropped pixels
   size_t cap_px = 0, cap_runs = 0, cap_cells = 0, cap_tab = 0, cap_items = 0, cap_stage = 0, cap_tmp = 0;
@@ -110,20 +110,6 @@ struct CellState {
   int ns_support = 0;
 };
 
-void cell_invalidate(svr_ctx *ctx) {
-  if (ctx->cell) ctx->cell->valid = false;
-  if (ctx->cell_g) ctx->cell_g->valid = false;
-  ctx->cellc_valid = false;
-  ctx->coeff_ids_valid = false;                           // (the pixels' places in the coefficient table follow the scatter's lists)
-}
-void cell_gf_invalidate(svr_ctx *ctx) {
-  if (ctx->cell) ctx->cell->gf_valid = false;
-  if (ctx->cell_g) ctx->cell_g->gf_valid = false;
-}
-void cell_pids_invalidate(svr_ctx *ctx) {
-  if (ctx->cell) ctx->cell->pid_valid = false;
-  if (ctx->cell_g) ctx->cell_g->pid_valid = false;
-}
 void cell_free(CellState *c) {
   if (!c) return;
   free_dev(c->d_keys); free_dev(c->d_keys2); free_dev(c->d_head); free_dev(c->d_runid);
@@ -1478,8 +1464,8 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   for (int c = 0; c < 2; ++c) for (int k = 0; k < 3; ++k) { hr[6 * c + 2 * k] = INT_MAX; hr[6 * c + 2 * k + 1] = INT_MIN; }
   hr[12] = hr[13] = hr[14] = hr[15] = 0;
   HIPCHK(hipMemcpyAsync(cs.d_range, hr, sizeof(hr), hipMemcpyHostToDevice, ctx->stream));
-  // the centres and their ranges do not depend on the cell size: the scatter's and the gather's lists share one pass (cell_invalidate
-  // drops it with the geometry)
+  // the centres and their ranges do not depend on the cell size: the scatter's and the gather's lists share one pass (invalidate
+  // drops it with the lists)
   if (!ctx->cellc_valid || ctx->cellc_n != n) {
     if ((size_t)n > ctx->cellc_cap) {
       free_dev(ctx->d_cellc);

@@ -1058,6 +1058,9 @@ __global__ __launch_bounds__(64) void k_probe_pixel(PsfArgs a, uint32_t idx, flo
 // ==========================================================================================
 struct RegState;   // GPU slice-to-volume registration state (svr_reg.inc)
 namespace { struct CellState; struct SlabPlan; struct SliceEm; void slice_em_free(SliceEm *); void slice_em_invalidate(SliceEm *); }  // sorted pixels, runs, items and staging of the scatter without atomics (svr_cell.inc)
+// what the coefficient table holds (svr_ctx::coeff_state): nothing, the PSF pixels of the pass that wrote it (coeff_lazy: a gather or
+// scatter of the SR iterations, pass 2 of a Gaussian reconstruction), or every pixel with s != -1 (k_coeff_build)
+enum CoeffState { COEFF_NONE = 0, COEFF_PSF = 1, COEFF_FULL = 2 };
 
 struct svr_ctx {
   int device = 0;
@@ -1196,7 +1199,7 @@ struct svr_ctx {
   uint32_t *d_coeff_order = nullptr;   // the active pixels in the order of their places in the table (coeff_order)
   size_t coeff_order_cap = 0;
   size_t coeff_cap = 0;        // pixels the allocation holds
-  bool coeff_valid = false;
+  CoeffState coeff_state = COEFF_NONE;   // (table_holds)
   int coeff_mode = 1;          // option "coeff_table": 0 = evaluate on the fly, 1 = stream the table (falls back to 0 if it does not fit).  Round 6: ON by
                                // default for slice-to-volume runs (written by the first gather of the SR iterations, coeff_lazy: P4 +7 %, S8 +5 % with one
                                // table per four SR iterations INSIDE the timed region), off for the patch-based path (no gain there: DESIGN 5.1b)
@@ -1204,9 +1207,8 @@ struct svr_ctx {
   bool coeff_user = false;     // svr_set_option("coeff_table") was called: the "pvr" option leaves the mode alone
   int coeff_lazy = 1;          // option "coeff_lazy" (round 6): 1 = the table is written by the first gather of the SR iterations after a new slice geometry
                                // (fwd_cell_kernel<.., 3>: the evaluation that pass needs anyway) instead of by k_coeff_build; passes before it evaluate
-  bool coeff_full = false;     // the table holds every pixel with s != -1 (k_coeff_build), not only the PSF pixels of the gather that wrote it
   const uint32_t *coeff_list = nullptr;   // the active pixels in table order (d_coeff_order, or d_active), while coeff_ids_valid
-  bool coeff_ids_valid = false;   // d_coeff_order / d_coeff_id match the current cell lists (cell_invalidate resets): a table thrown away without a new
+  bool coeff_ids_valid = false;   // d_coeff_order / d_coeff_id match the current cell lists (dropped with them): a table thrown away without a new
                                   // geometry (svr_set_option coeff_invalidate) keeps its pixels' places
   int wave_groups = 1, wave_cap = 2096;      // back_wave_kernel: wavefronts per tile, box voxels of a wavefront's four planes (14 LDS granules of 1280 B with the static part: 9 wavefronts per CU)
 
@@ -1321,9 +1323,27 @@ int fail(svr_ctx *c, int code, const std::string &msg) {
 inline int back_mode_eff(const svr_ctx *ctx) { return ctx->back_mode; }
 void reg_free(RegState *r);
 void cell_free(CellState *c);
-void cell_invalidate(svr_ctx *ctx);
-void cell_pids_invalidate(svr_ctx *ctx);
-void cell_gf_invalidate(svr_ctx *ctx);
+
+// The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
+// of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.
+enum Change : unsigned {
+  CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
+  CH_TAPS = 1u << 1,              // new slice constants, generatePSFVolume: the table and the cell lists
+  CH_SLICE_PIXELS = 1u << 2,      // d_slices: the PSF list, the table and the cell lists (they cover the pixels with s != -1)
+  CH_PSF_SUMS = 1u << 3,          // v_PSF_sums: the PSF list, the gather's 1 / v_PSF_sums, a table that holds the PSF pixels of an earlier pass
+  CH_VOLUME_GRID = 1u << 4,       // a new volume: the table, the cell lists and what is known about the volume buffers
+  CH_MASK = 1u << 5,              // the mask: clean buffers, the slab plan, the mask box
+  CH_MASK_BLUR = 1u << 6,         // the inputs of the blurred mask maskC (svr_set_mask: the mask and sigma)
+  CH_VOLUME_VALUES = 1u << 7,     // the current volume was written whole: no longer known to be clean
+  CH_SCATTER_TARGETS = 1u << 8,   // addon | cmap hold something other than the scatter's result
+  CH_CELL_SHAPE = 1u << 9,        // the cell options: the cell lists
+  CH_TILE_SHAPE = 1u << 10,       // a tile shape: the PSF list, and with it the tile lists
+  CH_TABLE = 1u << 11,            // the table thrown away (option coeff_invalidate: what a new slice geometry does to it)
+  CH_TABLE_OFF = 1u << 12,        // the table's memory freed: the table and the cell lists
+  CH_TABLE_IDS = 1u << 13,        // the pixels got new places in the table: the records' table ids
+  CH_TILE_TIMING = 1u << 14,      // time the tile shapes again (with fwd_autotune)
+};
+void invalidate(svr_ctx *ctx, unsigned changes);
 
 template <class T>
 void free_dev(T *&p) {
@@ -1456,7 +1476,7 @@ int prepare_slice_consts(svr_ctx *ctx) {
   HIPCHK(hipMemcpyAsync(ctx->d_sc, h.data(), h.size() * sizeof(SliceConst), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->sc_dirty = false;
-  ctx->coeff_valid = false; cell_invalidate(ctx);                               // new slice geometry: new taps
+  invalidate(ctx, CH_TAPS);
   return SVR_OK;
 }
 
@@ -1593,7 +1613,6 @@ int ensure_bias_buffers(svr_ctx *ctx) {
     HIPCHK(hipMalloc(&ctx->d_maskC, vb)); HIPCHK(hipMalloc(&ctx->d_mbuf, vb));
     HIPCHK(hipMemsetAsync(ctx->d_bias_vol, 0, vb, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_volume_weights, 0, vb, ctx->stream));
-    ctx->maskC_valid = false;
   }
   if (ctx->nv && ctx->have_mask && !ctx->maskC_valid) {
     // maskC_ = mask blurred with sigma_bias: x into a zeroed buffer, y back, z into the buffer, copy (RC.cu:1129-1157)
@@ -1699,14 +1718,17 @@ struct TileSample {
 // volumes -- takes LDS atomics (SVR: back_tiled_kernel) or device atomics per tap (PVR: pvr_tiles_kernel).
 // level: 4 = start with the wave-owned kernel, 3 = with the workgroup kernel, 1 = the last resort for every tile.
 int coeff_order(svr_ctx *ctx, uint32_t n_active, const uint32_t **list);
-// (Re)build the coefficient table if the option is on and the table does not match the current PSF pixels / geometry.
-// Returns with ctx->coeff_valid set, or with the mode switched off when the table does not fit the free memory.
 __global__ void k_coeff_ids(const uint32_t *list, uint32_t n, uint32_t *coeff_id) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) coeff_id[list[i]] = i;
 }
-// Can the table be left to the first gather of the SR iterations (coeff_lazy)?  Support 16 on the cell gather.
+// Can the table be left to the first gather of the SR iterations (coeff_lazy)?  Support 16 on the cell gather.  Pending: wanted, not there,
+// and left to the evaluating pass that writes it -- every other pass evaluates meanwhile.
 bool coeff_lazy_ok(const svr_ctx *ctx) { return ctx->coeff_lazy && !ctx->pvr && ctx->fwd_mode == 2; }
+bool coeff_lazy_pending(const svr_ctx *ctx) { return ctx->coeff_mode && ctx->coeff_state == COEFF_NONE && coeff_lazy_ok(ctx); }
+// May a pass stream the table?  `need` = the pixels it reads: COEFF_PSF for the passes of the SR iterations (either written state holds
+// them), COEFF_FULL for the Gaussian pass (every pixel with s != -1).
+bool table_holds(const svr_ctx *ctx, CoeffState need) { return ctx->coeff_mode && ctx->coeff_state >= need; }
 // The table's memory and the pixels' places in it (*list = the active pixels in table order).  Returns with ctx->d_coeff set, or with the mode
 // switched off when the table does not fit the free memory.
 int coeff_prepare(svr_ctx *ctx, const uint32_t **list) {
@@ -1730,7 +1752,7 @@ int coeff_prepare(svr_ctx *ctx, const uint32_t **list) {
     }
     ctx->coeff_cap = npx;
   }
-  if (!ctx->d_coeff_id) { HIPCHK(hipMalloc(&ctx->d_coeff_id, ctx->np * sizeof(uint32_t))); ctx->coeff_ids_valid = false; }
+  if (!ctx->d_coeff_id) HIPCHK(hipMalloc(&ctx->d_coeff_id, ctx->np * sizeof(uint32_t)));   // (freed by svr_init_storage_volumes, whose changes drop the ids)
   if (ctx->coeff_ids_valid && ctx->coeff_list) { *list = ctx->coeff_list; return SVR_OK; }
   *list = ctx->d_active;
   // The pixels get their places in the table in the order of the scatter's cell lists (cell, slice, band, position): what a
@@ -1743,10 +1765,10 @@ int coeff_prepare(svr_ctx *ctx, const uint32_t **list) {
   ctx->coeff_list = *list;
   return SVR_OK;
 }
-// (Re)build the coefficient table if the option is on and the table does not match the current PSF pixels / geometry.
-// Returns with ctx->coeff_valid set, or with the mode switched off when the table does not fit the free memory.
+// (Re)build the coefficient table if the option is on and there is none.
+// Returns with ctx->coeff_state COEFF_FULL, or with the mode switched off when the table does not fit the free memory.
 int ensure_coeff(svr_ctx *ctx) {
-  if (!ctx->coeff_mode || ctx->coeff_valid) return SVR_OK;
+  if (!ctx->coeff_mode || ctx->coeff_state != COEFF_NONE) return SVR_OK;
   const size_t npx = ctx->n_active;
   if (!npx) return SVR_OK;
   PsfArgs a = make_args(ctx);
@@ -1764,16 +1786,15 @@ int ensure_coeff(svr_ctx *ctx) {
     if (rr) return rr;
   }
   tb.stop();
-  ctx->coeff_valid = true;
-  ctx->coeff_full = true;
-  if (!ctx->coeff_ids_valid) cell_pids_invalidate(ctx);    // (the records' table ids: svr_cell.inc cell_pids)
+  ctx->coeff_state = COEFF_FULL;
+  if (!ctx->coeff_ids_valid) invalidate(ctx, CH_TABLE_IDS);   // (k_coeff_build gave the pixels their places: svr_cell.inc cell_pids)
   ctx->coeff_ids_valid = true;
   return SVR_OK;
 }
 // The evaluating cell pass that is about to run writes the table (coeff_lazy): memory, the pixels' places and ids.  *store = the pass should store.
 int coeff_begin_store(svr_ctx *ctx, bool *store) {
   *store = false;
-  if (!(ctx->coeff_mode && !ctx->coeff_valid && coeff_lazy_ok(ctx) && ctx->n_active)) return SVR_OK;
+  if (!coeff_lazy_pending(ctx) || !ctx->n_active) return SVR_OK;
   const uint32_t *order = nullptr;
   int r = coeff_prepare(ctx, &order);
   if (r) return r;
@@ -1781,16 +1802,11 @@ int coeff_begin_store(svr_ctx *ctx, bool *store) {
   if (!ctx->coeff_ids_valid) {
     hipLaunchKernelGGL(k_coeff_ids, dim3(nblk(ctx->n_active)), dim3(256), 0, ctx->stream, order, (uint32_t)ctx->n_active, ctx->d_coeff_id);
     KCHK("k_coeff_ids");
-    cell_pids_invalidate(ctx);
+    invalidate(ctx, CH_TABLE_IDS);
     ctx->coeff_ids_valid = true;
   }
   *store = true;
   return SVR_OK;
-}
-// a pass other than the gather of the SR iterations: with coeff_lazy it does not build the table -- it evaluates until that gather has written it
-int ensure_coeff_unless_lazy(svr_ctx *ctx) {
-  if (ctx->coeff_mode && !ctx->coeff_valid && coeff_lazy_ok(ctx)) return SVR_OK;
-  return ensure_coeff(ctx);
 }
 
 int launch_slot(svr_ctx *ctx, bool pvr, const PsfArgs &a, const TileArgs &ta_, uint32_t *fb, uint32_t *cnt) {
@@ -1887,6 +1903,30 @@ int launch_scatter(svr_ctx *ctx, int level, const PsfArgs &a_, TileArgs ta, cons
 
 #include "svr_cell.inc"
 #include "svr_slab.inc"
+
+// What each Change leaves stale.  A table written by a pass of the SR iterations holds that pass's PSF pixels only: every change that can
+// add one drops it.  Rebuilt cell lists reset their gather factors and table ids (cell_prepare_state): the lists take them along.
+void invalidate(svr_ctx *ctx, unsigned ch) {
+  if (ch & CH_SLICE_GEOMETRY) ctx->sc_dirty = true;
+  if (ch & (CH_SLICE_PIXELS | CH_PSF_SUMS | CH_TILE_SHAPE)) ctx->psf_list_valid = false;
+  if (ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_TABLE | CH_TABLE_OFF)) ctx->coeff_state = COEFF_NONE;
+  if ((ch & CH_PSF_SUMS) && ctx->coeff_state == COEFF_PSF) ctx->coeff_state = COEFF_NONE;
+  if (ch & CH_TABLE_OFF) { free_dev(ctx->d_coeff); ctx->coeff_cap = 0; }
+  const bool cells = ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_CELL_SHAPE | CH_TABLE_OFF);
+  if (cells) ctx->cellc_valid = ctx->coeff_ids_valid = false;   // (the pixels' places in the table follow the scatter's lists)
+  for (CellState *cs : {ctx->cell, ctx->cell_g}) {
+    if (!cs) continue;
+    if (cells) cs->valid = false;
+    if (cells || (ch & CH_PSF_SUMS)) cs->gf_valid = false;
+    if (cells || (ch & CH_TABLE_IDS)) cs->pid_valid = false;
+  }
+  if (ch & (CH_VOLUME_GRID | CH_MASK)) { ctx->vol_clean[0] = ctx->vol_clean[1] = false; if (ctx->slab) ctx->slab->valid = false; }   // (zero outside the old mask)
+  if (ch & CH_MASK) ctx->mbox_valid = false;
+  if (ch & (CH_VOLUME_GRID | CH_MASK_BLUR)) ctx->maskC_valid = false;
+  if (ch & CH_VOLUME_VALUES) ctx->vol_clean[ctx->recon_cur == ctx->d_recon_new ? 1 : 0] = false;
+  if (ch & (CH_VOLUME_GRID | CH_SCATTER_TARGETS)) ctx->cmap_from_scatter = false;
+  if (ch & CH_TILE_TIMING) ctx->fwd_tune_pending = ctx->back_tune_pending = ctx->fwd_autotune != 0;
+}
 
 // reduce partial[ns*chunks][K] -> per_slice[ns][K] (+ optionally -> d_out[K])
 int reduce_partials(svr_ctx *ctx, int K, int mn, int mx, bool global) {
@@ -2064,60 +2104,41 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
   if (!strcmp(name, "fwd_tile_w") || !strcmp(name, "fwd_tile_h")) {
     int w = !strcmp(name, "fwd_tile_w") ? value : ctx->fwd_tw, h = !strcmp(name, "fwd_tile_h") ? value : ctx->fwd_th;
     if (w < 1 || h < 1 || w * h > 32) return fail(ctx, SVR_E_ARG, "fwd tile must hold 1..32 pixels");   // FWDU_MAXPIX: the gather's pixel tables
-    ctx->fwd_tw = w; ctx->fwd_th = h; ctx->psf_list_valid = false;
+    ctx->fwd_tw = w; ctx->fwd_th = h; invalidate(ctx, CH_TILE_SHAPE);
     ctx->fwd_tile_user = true;                           // an explicit shape switches the tuning off
     return SVR_OK;
   }
   if (!strcmp(name, "fwd_autotune")) {
     ctx->fwd_autotune = value ? 1 : 0;
-    ctx->fwd_tune_pending = ctx->back_tune_pending = value != 0;
+    invalidate(ctx, CH_TILE_TIMING);
     return SVR_OK;
   }
-  if (!strcmp(name, "pvr")) { ctx->pvr = value ? 1 : 0; if (!ctx->coeff_user) ctx->coeff_mode = value ? 0 : 1; ctx->sc_dirty = true; ctx->psf_list_valid = false; ctx->coeff_valid = false; cell_invalidate(ctx); free_dev(ctx->d_coeff); ctx->coeff_cap = 0; return SVR_OK; }
+  if (!strcmp(name, "pvr")) { ctx->pvr = value ? 1 : 0; if (!ctx->coeff_user) ctx->coeff_mode = value ? 0 : 1; invalidate(ctx, CH_SLICE_GEOMETRY | CH_TILE_SHAPE | CH_TABLE_OFF); return SVR_OK; }
   if (!strcmp(name, "coeff_lazy")) { ctx->coeff_lazy = value ? 1 : 0; return SVR_OK; }
-  if (!strcmp(name, "coeff_invalidate")) { ctx->coeff_valid = false; return SVR_OK; }   // (what a new slice geometry does to the table: bench.py's outer iterations)
+  if (!strcmp(name, "coeff_invalidate")) { invalidate(ctx, CH_TABLE); return SVR_OK; }   // (what a new slice geometry does to the table: bench.py's outer iterations)
   if (!strcmp(name, "coeff_table")) {
-    if ((value ? 1 : 0) != ctx->coeff_mode) ctx->fwd_tune_pending = ctx->back_tune_pending = ctx->fwd_autotune != 0;   // other shapes win
+    if ((value ? 1 : 0) != ctx->coeff_mode) invalidate(ctx, CH_TILE_TIMING);   // other shapes win
     ctx->coeff_mode = value ? 1 : 0;
     ctx->coeff_user = true;
-    if (!value) { free_dev(ctx->d_coeff); ctx->coeff_cap = 0; ctx->coeff_valid = false; cell_invalidate(ctx); }
-    return SVR_OK;
-  }
-  if (!strcmp(name, "cell_band")) {
-    if (value < 0 || value > 10) return fail(ctx, SVR_E_ARG, "cell_band: 0..10 (a run holds 2^cell_band centre planes)");
-    ctx->cell_band = value;
-    cell_invalidate(ctx);
-    return SVR_OK;
-  }
-  if (!strcmp(name, "cell_qx")) {
-    if (value != 1 && value != 2 && value != 4) return fail(ctx, SVR_E_ARG, "cell_qx: 1, 2 or 4");
-    ctx->cell_qx = value;
-    cell_invalidate(ctx);
-    return SVR_OK;
-  }
-  if (!strcmp(name, "cell_w") || !strcmp(name, "cell_h") || !strcmp(name, "cell_gw") || !strcmp(name, "cell_gh")) {
-    if (value < 0 || value > 32) return fail(ctx, SVR_E_ARG, "cell_w / cell_h / cell_gw / cell_gh: 1..32, 0 = by the pixel density");
-    (!strcmp(name, "cell_w") ? ctx->cell_w : !strcmp(name, "cell_h") ? ctx->cell_h : !strcmp(name, "cell_gw") ? ctx->cell_gw : ctx->cell_gh) = value;
-    cell_invalidate(ctx);
-    return SVR_OK;
-  }
-  if (!strcmp(name, "cell_order")) {
-    if (value < 0 || value > 20) return fail(ctx, SVR_E_ARG, "cell_order: 0..20");
-    ctx->cell_order = value;
-    cell_invalidate(ctx);
+    if (!value) invalidate(ctx, CH_TABLE_OFF);
     return SVR_OK;
   }
   if (!strcmp(name, "cell_combine")) { if (value < 0 || value > 2) return fail(ctx, SVR_E_ARG, "cell_combine: 0, 1 or 2"); ctx->cell_combine = value; return SVR_OK; }
-  if (!strcmp(name, "cell_balance")) {
-    if (value < 0 || value > 1024) return fail(ctx, SVR_E_ARG, "cell_balance: 0..1024");
-    ctx->cell_balance = value;
-    cell_invalidate(ctx);
-    return SVR_OK;
-  }
-  if (!strcmp(name, "cell_split")) {
-    if (value < 1 || value > 32) return fail(ctx, SVR_E_ARG, "cell_split: 1..32");
-    ctx->cell_split = value;
-    cell_invalidate(ctx);
+  // the options of the cell lists' layout: the lists are built again
+  static const char *cwh = "cell_w / cell_h / cell_gw / cell_gh: 1..32, 0 = by the pixel density";
+  static const struct { const char *n; int lo, hi; int svr_ctx::*f; const char *what; } cell_opts[] = {
+      {"cell_band", 0, 10, &svr_ctx::cell_band, "cell_band: 0..10 (a run holds 2^cell_band centre planes)"},
+      {"cell_qx", 1, 4, &svr_ctx::cell_qx, "cell_qx: 1, 2 or 4"},
+      {"cell_w", 0, 32, &svr_ctx::cell_w, cwh}, {"cell_h", 0, 32, &svr_ctx::cell_h, cwh},
+      {"cell_gw", 0, 32, &svr_ctx::cell_gw, cwh}, {"cell_gh", 0, 32, &svr_ctx::cell_gh, cwh},
+      {"cell_order", 0, 20, &svr_ctx::cell_order, "cell_order: 0..20"},
+      {"cell_balance", 0, 1024, &svr_ctx::cell_balance, "cell_balance: 0..1024"},
+      {"cell_split", 1, 32, &svr_ctx::cell_split, "cell_split: 1..32"}};
+  for (const auto &o : cell_opts) {
+    if (strcmp(name, o.n)) continue;
+    if (value < o.lo || value > o.hi || (o.f == &svr_ctx::cell_qx && value == 3)) return fail(ctx, SVR_E_ARG, o.what);
+    ctx->*o.f = value;
+    invalidate(ctx, CH_CELL_SHAPE);
     return SVR_OK;
   }
   if (!strcmp(name, "dbg_back")) { ctx->dbg_back = value; return SVR_OK; }
@@ -2149,7 +2170,7 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
       HIPCHK(hipMalloc(&ctx->d_tiles, nb));
       HIPCHK(hipMalloc(&ctx->d_tiles_fb, nb));
       HIPCHK(hipMalloc(&ctx->d_tiles_fb2, nb));
-      ctx->psf_list_valid = false;
+      invalidate(ctx, CH_TILE_SHAPE);
     }
     return SVR_OK;
   }
@@ -2161,14 +2182,16 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value) {
   if (!ctx || !name || !value) return SVR_E_ARG;
   int csw, csh, cgw, cgh;
   cell_sizes(ctx, csw, csh, cgw, cgh);                   // the cell sizes in effect (0 = automatic resolved)
+  const bool cells_valid = ctx->cell && ctx->cell->valid && ((cgw == csw && cgh == csh) || !ctx->cell_g || ctx->cell_g->valid);   // (+ the gather's own)
   const struct { const char *n; int v; } tab[] = {
       {"back_mode", back_mode_eff(ctx)}, {"reg_mode", ctx->reg_mode}, {"fwd_mode", ctx->fwd_mode}, {"gauss_mode", ctx->gauss_mode}, {"pvr_mode", ctx->pvr_mode},
-      {"pvr", ctx->pvr}, {"coeff_table", ctx->coeff_mode}, {"coeff_lazy", ctx->coeff_lazy}, {"coeff_valid", ctx->coeff_valid ? 1 : 0}, {"tile_w", ctx->tile_w}, {"tile_h", ctx->tile_h},
+      {"pvr", ctx->pvr}, {"coeff_table", ctx->coeff_mode}, {"coeff_lazy", ctx->coeff_lazy}, {"coeff_valid", ctx->coeff_state != COEFF_NONE}, {"coeff_state", ctx->coeff_state}, {"tile_w", ctx->tile_w}, {"tile_h", ctx->tile_h},
       {"fwd_tile_w", ctx->fwd_tw}, {"fwd_tile_h", ctx->fwd_th}, {"wave_cap", ctx->wave_cap}, {"cell_w", csw}, {"cell_h", csh}, {"cell_gw", cgw}, {"cell_gh", cgh}, {"cell_split", ctx->cell_split}, {"cell_order", ctx->cell_order}, {"cell_balance", ctx->cell_balance}, {"cell_combine", ctx->cell_combine}, {"fwd_autotune", ctx->fwd_autotune}, {"cell_qx", ctx->cell_qx}, {"fwd_unit_cap", ctx->fwd_unit_cap}, {"reg_batch", ctx->reg_batch}, {"reg_blind", ctx->reg_blind},
       {"bias_mode", ctx->bias_mode}, {"bias_corrections", ctx->bias_corrections}, {"bias_normalisations", ctx->bias_normalisations},
       {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells},
       {"bias_field_bx", ctx->last_bias_bx}, {"bias_tail_lds", ctx->last_tail_lds}, {"bias_tail_rows", ctx->last_tail_rows},
-      {"bias_tail_bxy", ctx->last_tail_bxy}, {"bias_tail_bxz", ctx->last_tail_bxz}, {"reg_zc", ctx->last_reg_zc}, {"reg_chunks", ctx->last_reg_chunks}};
+      {"bias_tail_bxy", ctx->last_tail_bxy}, {"bias_tail_bxz", ctx->last_tail_bxz}, {"reg_zc", ctx->last_reg_zc}, {"reg_chunks", ctx->last_reg_chunks},
+      {"psf_list_valid", ctx->psf_list_valid}, {"cells_valid", cells_valid}};
   for (const auto &e : tab)
     if (!strcmp(name, e.n)) { *value = e.v; return SVR_OK; }
   return fail(ctx, SVR_E_ARG, std::string("unknown option ") + name);
@@ -2256,14 +2279,12 @@ int svr_init_reconstruction_volume(svr_ctx *ctx, const uint32_t size[3], const f
   ctx->vx = size[0]; ctx->vy = size[1]; ctx->vz = size[2];
   memcpy(ctx->vdim, dim, 3 * sizeof(float));
   ctx->nv = nv;
-  ctx->coeff_valid = false; cell_invalidate(ctx);
+  invalidate(ctx, CH_VOLUME_GRID);
   HIPCHK(hipMalloc(&ctx->d_recon_volw, 2 * nv * sizeof(float)));
   HIPCHK(hipMalloc(&ctx->d_addon_cmap, 2 * nv * sizeof(float)));
   HIPCHK(hipMalloc(&ctx->d_recon_new, nv * sizeof(float)));
   ctx->recon_cur = ctx->d_recon_volw;
-  ctx->prep_pending = false; ctx->cmap_from_scatter = false;
-  ctx->vol_clean[0] = ctx->vol_clean[1] = false;
-  if (ctx->slab) ctx->slab->valid = false;
+  ctx->prep_pending = false;
   HIPCHK(hipMemsetAsync(ctx->d_recon_volw, 0, 2 * nv * sizeof(float), ctx->stream));   // RC.cu:1199-1229
   HIPCHK(hipMemsetAsync(ctx->d_addon_cmap, 0, 2 * nv * sizeof(float), ctx->stream));
   if (data) HIPCHK(hipMemcpyAsync(ctx->recon(), data, nv * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -2284,10 +2305,8 @@ int svr_set_mask(svr_ctx *ctx, const uint32_t size[3], const float dim[3], const
   HIPCHK(hipMemcpyAsync(ctx->d_mask, data, ctx->nv * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->have_mask = true;
-  if (ctx->slab) ctx->slab->valid = false;
-  ctx->vol_clean[0] = ctx->vol_clean[1] = false;      // "zero outside the dilated mask" was a statement about the old mask
   ctx->mask_sigma_bias = sigma_bias;
-  ctx->maskC_valid = false;
+  invalidate(ctx, CH_MASK | CH_MASK_BLUR);
   {
     int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
     const size_t sxy = (size_t)ctx->vx * ctx->vy;
@@ -2373,8 +2392,9 @@ int svr_init_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const float d
   ctx->sx = size[0]; ctx->sy = size[1]; ctx->ns = size[2];
   ctx->np = np;
   ctx->have_slices = false; ctx->have_scales = false; ctx->have_dims = false; ctx->have_mats = false;
-  ctx->sc_dirty = true; ctx->psf_list_valid = false; ctx->n_active = ctx->n_psf = 0;
-  ctx->coeff_valid = false; cell_invalidate(ctx); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff); ctx->coeff_cap = 0;
+  ctx->n_active = ctx->n_psf = 0;
+  invalidate(ctx, CH_SLICE_GEOMETRY | CH_SLICE_PIXELS | CH_TABLE_OFF);
+  free_dev(ctx->d_coeff_id);
   const size_t fb = np * sizeof(float);
   HIPCHK(hipMalloc(&ctx->d_slices, fb));
   HIPCHK(hipMalloc(&ctx->d_weights, fb));
@@ -2421,8 +2441,7 @@ int svr_fill_slices(svr_ctx *ctx, const float *sdata, const int *sizes_x, const 
   NEED(ctx->np > 0, "initStorageVolumes first");
   HIPCHK(hipMemcpyAsync(ctx->d_slices, sdata, ctx->np * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   ctx->have_slices = true;
-  ctx->psf_list_valid = false;
-  ctx->coeff_valid = false; cell_invalidate(ctx);
+  invalidate(ctx, CH_SLICE_PIXELS);
   return build_list(ctx, false);
 }
 
@@ -2432,9 +2451,8 @@ int svr_set_slice_dims(svr_ctx *ctx, const float *slice_dims, float quality_fact
   NEED(ctx->ns > 0, "initStorageVolumes first");
   ctx->slice_dims.assign(slice_dims, slice_dims + 3 * (size_t)ctx->ns);
   ctx->quality_factor = quality_factor;   // only sizes the (unused) finite-support dim, RC.cu:772-784
-  ctx->fwd_tune_pending = ctx->back_tune_pending = ctx->fwd_autotune != 0;   // new slice geometry: time the tile shapes again
   ctx->have_dims = true;
-  ctx->sc_dirty = true;
+  invalidate(ctx, CH_SLICE_GEOMETRY | CH_TILE_TIMING);   // (the pixel density: time the tile shapes again)
   return SVR_OK;
 }
 
@@ -2453,7 +2471,7 @@ int svr_set_slice_matrices(svr_ctx *ctx, const float *T, const float *Tinv, cons
   memcpy(ctx->reconI2W, recon_i2w, 16 * sizeof(float));
   memcpy(ctx->reconW2I, recon_w2i, 16 * sizeof(float));
   ctx->have_mats = true;
-  ctx->sc_dirty = true;
+  invalidate(ctx, CH_SLICE_GEOMETRY);
   return SVR_OK;
 }
 
@@ -2466,7 +2484,7 @@ int svr_generate_psf_volume(svr_ctx *ctx, const float *cpu_psf, const uint32_t p
   // d_PSFI2W * ((PSFsize - 1) * 0.5f)   RC.cu:172
   float v[3] = {((float)psf_size[0] - 1) * 0.5f, ((float)psf_size[1] - 1) * 0.5f, ((float)psf_size[2] - 1) * 0.5f};
   matvec3_host(psf_i2w, v, ctx->psf_c0);
-  ctx->coeff_valid = false; cell_invalidate(ctx);                               // the taps' residuals carry c0
+  invalidate(ctx, CH_TAPS);                                // the taps' residuals carry c0
   ctx->quality_factor = quality_factor;
   ctx->have_psf = true;
   return SVR_OK;
@@ -2564,13 +2582,13 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
   HIPCHK(hipMemsetAsync(ctx->d_recon_volw, 0, 2 * ctx->nv * sizeof(float), ctx->stream));
   const bool tiled = ctx->gauss_mode == 1 && (!ctx->pvr || ctx->pvr_mode == 1);
   if (tiled) {
-    r = ensure_coeff_unless_lazy(ctx);
+    r = coeff_lazy_pending(ctx) ? SVR_OK : ensure_coeff(ctx);   // (coeff_lazy: pass 2 writes the table below)
     if (r) return r;
   }
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_active;
   a.n = ctx->n_active;
-  if (tiled && ctx->coeff_mode && ctx->coeff_valid && ctx->coeff_full) give_coeff(ctx, a);   // (every pixel with s != -1: a table written by a gather does not hold them all)
+  if (tiled && table_holds(ctx, COEFF_FULL)) give_coeff(ctx, a);
   bool stored = false;
   ScopedTimer t(ctx, SVR_T_GAUSS);
   if (a.n && tiled) {
@@ -2655,10 +2673,8 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
       if (rr) return rr; }
   }
   t.stop();
-  ctx->psf_list_valid = false;
-  if (stored) { ctx->coeff_valid = true; ctx->coeff_full = false; }   // (written by pass 2 for the new v_PSF_sums)
-  else if (!ctx->coeff_full) ctx->coeff_valid = false;     // new v_PSF_sums: a table written by an earlier pass holds the PSF pixels of that pass
-  cell_gf_invalidate(ctx);                                 // ... and the gather's 1 / v_PSF_sums per sorted pixel
+  invalidate(ctx, CH_PSF_SUMS);
+  if (stored) ctx->coeff_state = COEFF_PSF;                // (written by pass 2 for the new v_PSF_sums)
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
@@ -2718,7 +2734,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   // (fwd_cell_kernel<.., 3>); needs the cell gather.  Otherwise k_coeff_build, as before.
   bool store = false;
   CellState *gcs = nullptr;
-  if (ctx->coeff_mode && !ctx->coeff_valid && coeff_lazy_ok(ctx) && ctx->n_psf && ctx->n_active) {
+  if (coeff_lazy_pending(ctx) && ctx->n_psf && ctx->n_active) {
     if ((r = cell_prepare_gather(ctx, gcs))) return r;
     if (gcs->usable && (r = coeff_begin_store(ctx, &store))) return r;
   }
@@ -2729,7 +2745,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
-  if (store || (ctx->coeff_mode && ctx->coeff_valid && (ctx->pvr ? ctx->pvr_mode == 1 : ctx->fwd_mode >= 1))) give_coeff(ctx, a);
+  if (store || ((ctx->pvr ? ctx->pvr_mode == 1 : ctx->fwd_mode >= 1) && table_holds(ctx, COEFF_PSF))) give_coeff(ctx, a);
   if (!ctx->pvr && ctx->fwd_mode >= 1 && a.n) {
     if (!ctx->d_volm) HIPCHK(hipMalloc(&ctx->d_volm, ctx->nv * sizeof(float2)));
     hipLaunchKernelGGL(k_pack_volm, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, ctx->nv);
@@ -2766,7 +2782,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
     if (cells) {
       const int rr = launch_cell_gather(ctx, *gcs, a, store);
       if (rr) return rr;
-      if (store) { ctx->coeff_valid = true; ctx->coeff_full = false; }   // (the PSF pixels' live units: what the SR iterations' passes read)
+      if (store) ctx->coeff_state = COEFF_PSF;             // (the PSF pixels' live units: what the SR iterations' passes read)
     } else if (a.n && tiled_) {
       { const int rr = ensure_tiles_fwd(ctx); if (rr) return rr; }
       TileArgs ta;
@@ -2796,7 +2812,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
     int w, h;
     tile_shape_rule(ctx, a.coeff != nullptr, w, h);
     if (w != ctx->fwd_tw || h != ctx->fwd_th) {
-      ctx->fwd_tw = w; ctx->fwd_th = h; ctx->psf_list_valid = false;
+      ctx->fwd_tw = w; ctx->fwd_th = h; invalidate(ctx, CH_TILE_SHAPE);
       r = ensure_psf_list(ctx);
       if (r) return r;
       a.list = ctx->d_psf_list; a.n = ctx->n_psf;
@@ -2811,7 +2827,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
     float best = 3.0e38f;
     int pick = 0;
     for (int c = 0; c < 6; ++c) {
-      ctx->fwd_tw = cand[c][0]; ctx->fwd_th = cand[c][1]; ctx->psf_list_valid = false;
+      ctx->fwd_tw = cand[c][0]; ctx->fwd_th = cand[c][1]; invalidate(ctx, CH_TILE_SHAPE);
       r = ensure_psf_list(ctx);
       if (r) return r;
       a.list = ctx->d_psf_list; a.n = ctx->n_psf;
@@ -2836,7 +2852,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    ctx->fwd_tw = cand[pick][0]; ctx->fwd_th = cand[pick][1]; ctx->psf_list_valid = false;
+    ctx->fwd_tw = cand[pick][0]; ctx->fwd_th = cand[pick][1]; invalidate(ctx, CH_TILE_SHAPE);
     r = ensure_psf_list(ctx);
     if (r) return r;
     a.list = ctx->d_psf_list; a.n = ctx->n_psf;
@@ -3231,7 +3247,7 @@ int svr_superresolution_backproject(svr_ctx *ctx, const float *slice_weight) {
   r = ensure_psf_list(ctx);
   if (r) return r;
   // (coeff_lazy: a scatter that finds no table evaluates -- and, on the cell path, writes it: whichever PSF pass comes first after a new geometry does)
-  r = ensure_coeff_unless_lazy(ctx);
+  r = coeff_lazy_pending(ctx) ? SVR_OK : ensure_coeff(ctx);
   if (r) return r;
   bool store = false;
   // RC.cu:2202-2203 -- not needed where the cell scatter runs: its combine writes EVERY voxel of addon | cmap (0 outside the mask); decided below
@@ -3241,7 +3257,7 @@ int svr_superresolution_backproject(svr_ctx *ctx, const float *slice_weight) {
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
-  if (ctx->coeff_mode && ctx->coeff_valid && (ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) >= 4)) give_coeff(ctx, a);
+  if ((ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) >= 4) && table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
   const bool tiled = ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) >= 1;
   if (!a.coeff && a.n && tiled && back_mode_eff(ctx) == 5 && !ctx->pvr) {
     if ((r = cell_prepare(ctx))) return r;
@@ -3267,7 +3283,7 @@ int svr_superresolution_backproject(svr_ctx *ctx, const float *slice_weight) {
     if (need_clear) { need_clear = false; HIPCHK(hipMemsetAsync(ctx->d_addon_cmap, 0, 2 * ctx->nv * sizeof(float), ctx->stream)); }
     if (cells) {
       r = launch_cell_scatter(ctx, a, 0, ctx->addon(), ctx->cmap(), store);
-      if (!r && store) { ctx->coeff_valid = true; ctx->coeff_full = false; }   // (the PSF pixels' live units: what the SR iterations' passes read)
+      if (!r && store) ctx->coeff_state = COEFF_PSF;       // (the PSF pixels' live units: what the SR iterations' passes read)
     }
     else if (!(r = ensure_tiles_back(ctx))) r = launch_scatter(ctx, ctx->pvr ? 4 : std::min(4, back_mode_eff(ctx)), a, ta, ctx->d_tiles, ctx->n_tiles, MODE_BACK);
     if (r) return r;
@@ -3375,7 +3391,7 @@ int svr_superresolution_update(svr_ctx *ctx, int adaptive, float alpha, float mi
   ctx->recon_cur = ctx->recon_cur == ctx->d_recon_volw ? ctx->d_recon_new : ctx->d_recon_volw;   // the update wrote the other buffer
   // a whole-volume update carries whatever the old volume held outside the dilated mask over into the buffer it wrote: the slab update
   // (svr_slab.inc), which only writes inside it, must clear that buffer before it uses it next
-  ctx->vol_clean[ctx->recon_cur == ctx->d_recon_new ? 1 : 0] = false;
+  invalidate(ctx, CH_VOLUME_VALUES);
   t.stop();
   if (!ctx->sr_no_wait) HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
@@ -3441,7 +3457,7 @@ int svr_slab_finish(svr_ctx *ctx) {
   KCHK("k_slab_ag_unpack");
   ctx->recon_cur = out;
   // addon | cmap now hold the sums of this rank's slab only: not a state a reader should see as "the scatter's result"
-  ctx->cmap_from_scatter = false;
+  invalidate(ctx, CH_SCATTER_TARGETS);
   ctx->prep_pending = false;
   if (!ctx->sr_no_wait) HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
@@ -3579,17 +3595,13 @@ int svr_debug_set(svr_ctx *ctx, int which, const void *host_in, size_t bytes) {
   if (bytes != b) return fail(ctx, SVR_E_ARG, "svr_debug_set: size mismatch");
   HIPCHK(hipMemcpyAsync(p, host_in, b, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (which == SVR_BUF_PSF_SUMS || which == SVR_BUF_SLICES) { ctx->psf_list_valid = false; if (!ctx->coeff_full) ctx->coeff_valid = false; cell_gf_invalidate(ctx); }
   if (which == SVR_BUF_SIMINSIDE) {                      // (the per-slice flags follow: the cell gather only ever raises them)
     hipLaunchKernelGGL(k_slice_inside, dim3(ctx->ns), dim3(256), 0, ctx->stream, ctx->d_siminside, (int)(ctx->sx * ctx->sy), ctx->d_slice_inside);
     KCHK("k_slice_inside");
   }
-  if (which == SVR_BUF_SLICES) { ctx->coeff_valid = false; cell_invalidate(ctx); }   // the table and the cell lists cover the pixels with s != -1
-  if (which == SVR_BUF_MASK) ctx->mbox_valid = false;                               // (a mask set behind svr_set_mask's back: the whole pair is exchanged)
-  if (which == SVR_BUF_MASK && ctx->slab) ctx->slab->valid = false;
-  if (which == SVR_BUF_MASK) ctx->vol_clean[0] = ctx->vol_clean[1] = false;
-  if (which == SVR_BUF_RECONSTRUCTED) ctx->vol_clean[ctx->recon_cur == ctx->d_recon_new ? 1 : 0] = false;
-  if (which == SVR_BUF_ADDON || which == SVR_BUF_CONFIDENCE_MAP) ctx->cmap_from_scatter = false;   // (no longer known to vanish outside the mask)
+  // (a mask set behind svr_set_mask's back: no mask box, the whole pair is exchanged; maskC stays as it was)
+  invalidate(ctx, which == SVR_BUF_SLICES ? CH_SLICE_PIXELS : which == SVR_BUF_PSF_SUMS ? CH_PSF_SUMS : which == SVR_BUF_MASK ? CH_MASK
+                  : which == SVR_BUF_RECONSTRUCTED ? CH_VOLUME_VALUES : which == SVR_BUF_ADDON || which == SVR_BUF_CONFIDENCE_MAP ? CH_SCATTER_TARGETS : 0u);
   if (which == SVR_BUF_SLICES) return build_list(ctx, false);
   return SVR_OK;
 }
@@ -3727,7 +3739,7 @@ int svr_normalise_bias_local(svr_ctx *ctx) {
   if (ctx->bias_mode >= 1 && a.n && !ctx->pvr && back_mode_eff(ctx) == 5) {
     if ((r = cell_prepare(ctx))) return r;
     if (ctx->cell->usable) {
-      if (ctx->coeff_mode && ctx->coeff_valid) give_coeff(ctx, a);
+      if (table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
       if ((r = launch_cell_scatter(ctx, a, 2, ctx->d_bias_vol, ctx->d_mbuf))) return r;
       hipLaunchKernelGGL(k_add_to, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->d_volume_weights, ctx->d_mbuf, ctx->nv);
       KCHK("k_add_to");
