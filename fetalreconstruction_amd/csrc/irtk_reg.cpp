@@ -16,7 +16,9 @@
 //   irtkReconstruction::SliceToVolumeRegistration (+ ParallelSliceToVolumeRegistration)                               RG.cc:1991-2059, 2291-2303
 // The similarity itself (irtkImageRigidRegistrationWithPadding::Evaluate + irtkCrossCorrelationSimilarityMetric) is the
 // engine's svr_ncc_evaluate: exact integer moments, so the accept / reject decisions of the optimiser do not depend on
-// where the cost is evaluated.  All targets that share a source are optimised in lock step: one optimiser step of every
+// where the cost is evaluated.  With SVRH_SIM_NMI (the reference's --useNMI) it is irtkNormalisedMutualInformationSimilarity-
+// Metric: the levels are binned (irtkCalculateNumberOfBins) and svr_nmi_evaluate returns integer joint histograms' entropy
+// sums added in the reference's order, equal to nmi_sums below bit for bit -- the same guarantee.  All targets that share a source are optimised in lock step: one optimiser step of every
 // target (its similarity, its 12 finite differences, or one line-search probe) is ONE batched evaluate call.  A 3-D target
 // (a stack) is handed to the engine as its z-planes, each with the start position the reference's iterator reaches by
 // repeated addition (irtkHomogeneousTransformationIterator.h:96-199), and the six moments are added up.
@@ -245,6 +247,54 @@ short guess_padding(const Vol<short> &v) {
   return (short)-32768;                                    // MIN_GREY
 }
 
+// irtkCalculateNumberOfBins (irtkUtil.cc:438-474) with GuessParameterSliceToVolume's _NumberOfBins = 64 (IRRWP.cc:316), which
+// Initialize(level) calls for NMI (IRWP.cc:239-246) with the range [mn, mx] of the level before its shift to 0: the smallest
+// width that puts range = mx - mn + 1 into at most 64 bins.  A level without a voxel above the padding (mx < mn) has no
+// samples; it gets one bin of width 1 (the reference would size its histogram by the negative range).
+int nmi_number_of_bins(int mn, int mx, int &width) {
+  const int range = mx - mn + 1;
+  width = 1;
+  if (range < 1) return 1;
+  while ((int)ceil(range / (double)width) > 64) width++;
+  return (int)ceil(range / (double)width);
+}
+void nmi_bin(short *d, size_t n, int width) {              // ... and its rescaling of the voxels
+  for (size_t i = 0; i < n; ++i)
+    if (d[i] > 0) d[i] = (short)(int)(d[i] / (double)width);
+}
+// The sums of irtkHistogram_2D::JointEntropy / EntropyX / EntropyY (H2D.cc:443-523) over h[source bin][target bin] (row pitch
+// 64): {n, S_xy, S_x, S_y}, each S the serial sum of c log c over the nonzero bins in the reference's visit order.  The
+// engine's entropy pass (csrc/svr_nmi.inc) adds the same terms, from a table of the same expression, in the same order.
+void nmi_sums(const uint32_t *h, int nbt, int nbs, double out[4]) {
+  auto term = [](uint64_t c) { return (double)c * log((double)c); };
+  double sxy = 0, sx = 0, sy = 0;
+  uint64_t n = 0;
+  for (int j = 0; j < nbs; ++j)
+    for (int i = 0; i < nbt; ++i) {
+      const uint32_t c = h[j * 64 + i];
+      if (c > 0) sxy += term(c);
+      n += c;
+    }
+  for (int i = 0; i < nbt; ++i) {
+    uint64_t m = 0;
+    for (int j = 0; j < nbs; ++j) m += h[j * 64 + i];
+    if (m > 0) sx += term(m);
+  }
+  for (int j = 0; j < nbs; ++j) {
+    uint64_t m = 0;
+    for (int i = 0; i < nbt; ++i) m += h[j * 64 + i];
+    if (m > 0) sy += term(m);
+  }
+  out[0] = (double)n; out[1] = sxy; out[2] = sx; out[3] = sy;
+}
+// irtkHistogram_2D::NormalizedMutualInformation, H2D.cc:617-624: (EntropyX + EntropyY) / JointEntropy, entropy = -S / n + log(n)
+double nmi_from_sums(const double s[4]) {
+  const double n = s[0];
+  if (n == 0) return 0;
+  const double ex = -s[2] / n + log(n), ey = -s[3] / n + log(n), exy = -s[1] / n + log(n);
+  return (ex + ey) / exy;
+}
+
 struct Schedule {                                          // GuessParameterThickSlices / GuessParameterSliceToVolume
   int levels = 3, iterations[3], steps[3];
   double epsilon = 0.0001, t_blur[3], s_blur[3], t_res[3][3], s_res[3][3], length[3], delta[3];
@@ -273,8 +323,9 @@ Schedule guess_parameters(const svr_image_attr &t, const svr_image_attr &s, int 
 }
 
 // irtkImageRegistrationWithPadding::Initialize(level) for one image: blur, resample, shift the range, pad with -1
+// (mn_out / mx_out: the range before the shift, max < min when no voxel is above the padding)
 int prepare_level(const Vol<short> &in, double blur, const double res[3], const double res0[3], int level, short pad, Vol<short> &out,
-                  std::string &err) {
+                  std::string &err, int *mn_out = nullptr, int *mx_out = nullptr) {
   out = in;
   if (blur > 0) blur_with_padding(out, blur, pad);
   const double temp = fabs(res0[0] - out.a.dx) + fabs(res0[1] - out.a.dy) + fabs(res0[2] - out.a.dz);
@@ -286,6 +337,8 @@ int prepare_level(const Vol<short> &in, double blur, const double res[3], const 
   }
   if (vmax - vmin > 32767.0) { err = "Initialize: dynamic range of an image is too large"; return 1; }
   for (short &v : out.d) v = v > pad ? (short)(v - (short)vmin) : (short)-1;
+  if (mn_out) *mn_out = (int)vmin;
+  if (mx_out) *mx_out = (int)vmax;
   return 0;
 }
 
@@ -321,14 +374,25 @@ void matrix_to_params(const M4 &m, double p[6]) {
 struct Backend {                                           // the engine, or whatever the caller supplies
   svr_ctx *ctx;
   const svr_ncc_backend *be;
+  const svr_nmi_backend *nbe = nullptr;                    // NMI: the caller's joint histograms instead of the engine's sums
+  bool external() const { return be || nbe; }
   int set_targets(int n, int tx, int ty, const int16_t *t) const {
-    return be ? be->set_targets(be->user, n, tx, ty, t) : svr_ncc_set_targets(ctx, n, tx, ty, t);
+    return nbe ? nbe->set_targets(nbe->user, n, tx, ty, t) : be ? be->set_targets(be->user, n, tx, ty, t) : svr_ncc_set_targets(ctx, n, tx, ty, t);
   }
   int set_source(const uint32_t size[3], const int16_t *s) const {
-    return be ? be->set_source(be->user, size, s) : svr_ncc_set_source(ctx, size, s);
+    return nbe ? nbe->set_source(nbe->user, size, s) : be ? be->set_source(be->user, size, s) : svr_ncc_set_source(ctx, size, s);
   }
   int evaluate(int n, const int *idx, const double *m, int64_t *sums) const {
     return be ? be->evaluate(be->user, n, idx, m, sums, nullptr) : svr_ncc_evaluate(ctx, n, idx, m, sums, nullptr);
+  }
+  // {n, S_xy, S_x, S_y} per evaluation: the engine's, or nmi_sums of the caller's histograms
+  int evaluate_nmi(int n, const int *ppe, const int *idx, const double *m, const int *width, const int *nbins, int source_nbins, double *out4,
+                   std::vector<uint32_t> &hist) const {
+    if (!nbe) return svr_nmi_evaluate(ctx, n, ppe, idx, m, width, nbins, source_nbins, out4, nullptr);
+    hist.assign((size_t)n * 4096, 0);
+    if (int rc = nbe->evaluate(nbe->user, n, ppe, idx, m, width, nbins, source_nbins, hist.data())) return rc;
+    for (int e = 0; e < n; ++e) nmi_sums(&hist[(size_t)e * 4096], nbins[e], source_nbins, out4 + 4 * (size_t)e);
+    return 0;
   }
 };
 
@@ -338,6 +402,7 @@ struct Target {                                            // one registration: 
   int first_plane = 0;                                     // index of its plane 0 among the backend's targets
   int own_padding = 0;                                     // 1: `padding` replaces the call's target padding (GuessParameter's corner rule)
   short padding = 0;
+  int bin_width = 1, nbins = 1;                            // NMI: irtkCalculateNumberOfBins of this level
   M4 matrix;                                               // irtkRigidTransformation::_matrix
   double p[6];                                             // ... and its parameters
   // optimiser state (irtkImageRegistration::Run + irtkGradientDescentOptimizer::Run)
@@ -359,7 +424,8 @@ double ncc_from_sums(const int64_t s[6]) {                 // irtkCrossCorrelati
 // `offset` of the upload slot: the attributes of the level come back in out[i], the voxels stay on the device as the NCC
 // source (slot 0) or as the target planes first_plane, first_plane + nz, ...
 int device_level(svr_ctx *ctx, int slot, size_t offset, int n, const svr_image_attr *const *in, const short *pads, double blur, const double res[3],
-                 const double res0[3], int level, int first_plane, svr_image_attr *out, std::string &err) {
+                 const double res0[3], int level, int first_plane, svr_image_attr *out, std::string &err, int *mn_out = nullptr,
+                 int *mx_out = nullptr) {
   const svr_image_attr &a0 = *in[0];
   std::vector<double> ker[3];
   if (blur > 0) {
@@ -383,8 +449,11 @@ int device_level(svr_ctx *ctx, int slot, size_t offset, int n, const svr_image_a
     err = std::string("svr_pyr_level: ") + svr_last_error(ctx);
     return 2;
   }
-  for (int i = 0; i < n; ++i)
+  for (int i = 0; i < n; ++i) {
     if ((double)mx[i] - (double)mn[i] > 32767.0) { err = "Initialize: dynamic range of an image is too large"; return 1; }
+    if (mn_out) mn_out[i] = mn[i];
+    if (mx_out) mx_out[i] = mx[i];
+  }
   return 0;
 }
 
@@ -395,9 +464,10 @@ struct GridKey {
 };
 struct GridGroup { std::vector<int> members; size_t offset = 0; };
 
-// irtkImageRegistration::Run for every target against one source, in lock step
+// irtkImageRegistration::Run for every target against one source, in lock step; nmi: the similarity is NMI instead of CC
+// (GuessParameterSliceToVolume(useNMI), IRRWP.cc:319-321: the schedule, the optimiser and epsilon are the same)
 int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol<short> &source, int slice_to_volume, short target_padding,
-                      long *n_eval, std::string &err) {
+                      int nmi, long *n_eval, std::string &err) {
   if (targets.empty()) return 0;
   const short source_padding = guess_padding(source);
   const bool timing = getenv("SVR_REG_TIMING") != nullptr;        // dev: where a registration pass spends its wall time
@@ -406,7 +476,7 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   // The engine makes the pyramids itself (csrc/svr_pyr.inc: the same arithmetic, no host pass over the voxels, no upload
   // per level); another backend (the oracle evaluator of the tests), or SVR_HOST_PYRAMID=1, takes the host code below.
-  const bool dev = !be.be && be.ctx && !getenv("SVR_HOST_PYRAMID");
+  const bool dev = !be.external() && be.ctx && !getenv("SVR_HOST_PYRAMID");
   std::map<GridKey, GridGroup> groups;                    // targets of one grid go through the kernels together
   if (dev) {
     if (svr_pyr_upload(be.ctx, 0, source.d.data(), source.n())) { err = std::string("svr_pyr_upload: ") + svr_last_error(be.ctx); return 2; }
@@ -429,10 +499,18 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
     // ---- Initialize(level): every target and the source -------------------------------------------------------------
     Vol<short> src;
     const Schedule ps = guess_parameters(targets[0].full->a, source.a, slice_to_volume);
+    int smn = 0, smx = -1, src_width = 1, src_nbins = 1;
     if (dev) {
       const svr_image_attr *in = &source.a;
-      if (int rc = device_level(be.ctx, 0, 0, 1, &in, &source_padding, ps.s_blur[level], ps.s_res[level], ps.s_res[0], level, 0, &src.a, err)) return rc;
-    } else if (prepare_level(source, ps.s_blur[level], ps.s_res[level], ps.s_res[0], level, source_padding, src, err)) return 1;
+      if (int rc = device_level(be.ctx, 0, 0, 1, &in, &source_padding, ps.s_blur[level], ps.s_res[level], ps.s_res[0], level, 0, &src.a, err, &smn,
+                                &smx))
+        return rc;
+    } else if (prepare_level(source, ps.s_blur[level], ps.s_res[level], ps.s_res[0], level, source_padding, src, err, &smn, &smx)) return 1;
+    if (nmi) {                                                 // the source is binned before it is interpolated (IRWP.cc:243-244)
+      src_nbins = nmi_number_of_bins(smn, smx, src_width);
+      if (!dev) nmi_bin(src.d.data(), src.d.size(), src_width);
+      else if (svr_nmi_bin_source(be.ctx, src_width)) { err = std::string("svr_nmi_bin_source: ") + svr_last_error(be.ctx); return 2; }
+    }
     t_src += now() - t0; t0 = now();
     int tx = 0, ty = 0, planes = 0;
     std::vector<int> bad(targets.size(), 0);
@@ -469,9 +547,14 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
             in[i] = &t.full->a;
             pads[i] = t.own_padding ? t.padding : target_padding;
           }
+          std::vector<int> tmn(n), tmx(n);
           if (int rc = device_level(be.ctx, 1, g.second.offset + c0 * nvox, n, in.data(), pads.data(), p.t_blur[level], p.t_res[level], p.t_res[0], level,
-                                    targets[mem[c0]].first_plane, outa.data(), err))
+                                    targets[mem[c0]].first_plane, outa.data(), err, tmn.data(), tmx.data()))
             return rc;
+          for (int i = 0; i < n; ++i) {                                              // the targets are binned on the fly
+            Target &t = targets[mem[c0 + i]];
+            t.nbins = nmi_number_of_bins(tmn[i], tmx[i], t.bin_width);
+          }
         }
       }
     } else
@@ -479,8 +562,10 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
       for (int r = r0; r < r1; ++r) {
         Target &t = targets[r];
         const Schedule p = guess_parameters(t.full->a, source.a, slice_to_volume);
+        int mn = 0, mx = -1;
         bad[r] = prepare_level(*t.full, p.t_blur[level], p.t_res[level], p.t_res[0], level, t.own_padding ? t.padding : target_padding, t.lvl,
-                               errs[r]);
+                               errs[r], &mn, &mx);
+        t.nbins = nmi_number_of_bins(mn, mx, t.bin_width);
         t.phase = PH_START; t.step_i = 0; t.iter_j = 0; t.done = false;
         t.step = p.length[level]; t.delta = p.delta[level];
       }
@@ -511,9 +596,10 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
     // A round costs the host a few double trigonometric calls per target; with tens of thousands of targets (the patches
     // of the patch-based path) that was 1.6 s of a 2.8 s pass, so the requests are laid out by a prefix sum and written,
     // and the answers consumed, by the host threads -- every target touches only its own state and its own slots.
-    std::vector<int> live, req_off, plane_off, idx;
-    std::vector<double> mats, value;
+    std::vector<int> live, req_off, plane_off, idx, req_planes, req_width, req_nbins;
+    std::vector<double> mats, value, out4;
     std::vector<int64_t> sums;
+    std::vector<uint32_t> hist;
     auto over_live = [&](size_t work, const std::function<void(int, int)> &fn) {
       if (live.size() >= 2048) parallel_rows((int)live.size(), work, fn);
       else fn(0, (int)live.size());
@@ -529,12 +615,16 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
         n_req += nr; n_planes += nr * t.lvl.a.nz;
       }
       if (live.empty()) break;
-      idx.resize(n_planes); mats.resize(16 * (size_t)n_planes); sums.resize(6 * (size_t)n_planes); value.resize(n_req);
+      idx.resize(n_planes); mats.resize(16 * (size_t)n_planes); value.resize(n_req);
+      if (nmi) { req_planes.resize(n_req); req_width.resize(n_req); req_nbins.resize(n_req); out4.resize(4 * (size_t)n_req); }
+      else sums.resize(6 * (size_t)n_planes);
       over_live(3000, [&](int l0, int l1) {
         for (int l = l0; l < l1; ++l) {
           const Target &t = targets[live[l]];
-          int at = plane_off[l];
+          int at = plane_off[l], rq = req_off[l];
           auto request = [&](const M4 &tm) {                 // the per-plane matrices of one evaluation (push_request)
+            if (nmi) { req_planes[rq] = t.lvl.a.nz; req_width[rq] = t.bin_width; req_nbins[rq] = t.nbins; }
+            ++rq;
             const M4 m = mul(mul(s_w2i, tm), image_to_world(t.lvl.a));
             double zx = m.m[3], zy = m.m[7], zz = m.m[11];
             for (int k = 0; k < t.lvl.a.nz; ++k, ++at) {
@@ -558,7 +648,12 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
         }
       });
       const double te = now();
-      if (be.evaluate(n_planes, idx.data(), mats.data(), sums.data())) { err = "svr_ncc_evaluate failed"; return 2; }
+      if (nmi) {
+        if (be.evaluate_nmi(n_req, req_planes.data(), idx.data(), mats.data(), req_width.data(), req_nbins.data(), src_nbins, out4.data(), hist)) {
+          err = be.external() ? "svr_nmi_evaluate failed" : std::string("svr_nmi_evaluate: ") + svr_last_error(be.ctx);
+          return 2;
+        }
+      } else if (be.evaluate(n_planes, idx.data(), mats.data(), sums.data())) { err = "svr_ncc_evaluate failed"; return 2; }
       t_eval += now() - te; ++rounds;
       if (n_eval) *n_eval += (long)n_req;
       over_live(600, [&](int l0, int l1) {
@@ -566,6 +661,7 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
           Target &t = targets[live[l]];
           const int nz = t.lvl.a.nz, nr = t.phase == PH_GRAD ? 12 : 1;
           for (int q = 0; q < nr; ++q) {
+            if (nmi) { value[req_off[l] + q] = nmi_from_sums(&out4[4 * ((size_t)req_off[l] + q)]); continue; }
             int64_t sacc[6] = {0, 0, 0, 0, 0, 0};
             const size_t at = (size_t)plane_off[l] + (size_t)q * nz;
             for (int c = 0; c < nz; ++c) for (int k = 0; k < 6; ++k) sacc[k] += sums[6 * (at + c) + k];
@@ -619,8 +715,8 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
     t_opt += now() - t0;
   }
   if (timing)
-    fprintf(stderr, "[svr reg timing] source pyramid %.1f ms, target pyramids %.1f ms, pack + upload %.1f ms, optimiser %.1f ms (%ld rounds, %.1f ms in the batched evaluations)\n",
-            1e3 * t_src, 1e3 * t_tgt, 1e3 * t_pack, 1e3 * t_opt, rounds, 1e3 * t_eval);
+    fprintf(stderr, "[svr reg timing] %s: source pyramid %.1f ms, target pyramids %.1f ms, pack + upload %.1f ms, optimiser %.1f ms (%ld rounds, %.1f ms in the batched evaluations)\n",
+            nmi ? "NMI" : "CC", 1e3 * t_src, 1e3 * t_tgt, 1e3 * t_pack, 1e3 * t_opt, rounds, 1e3 * t_eval);
   return 0;
 }
 
@@ -694,7 +790,7 @@ int svrh_stack_registrations(svr_ctx *ctx, const svr_ncc_backend *backend, int n
     one[0].matrix = mul(T[s], mo);                                        // include the offset: PutMatrix(m * mo)
     matrix_to_params(one[0].matrix, one[0].p);
     std::string e;
-    const int rc = run_registrations(be, one, source, 0, (short)0, n_evaluations_or_null, e);   // ThickSlices, SetTargetPadding(0)
+    const int rc = run_registrations(be, one, source, 0, (short)0, 0, n_evaluations_or_null, e);   // ThickSlices, SetTargetPadding(0)
     if (rc) { set_err(err, e); return rc; }
     T[s] = mul(params_to_matrix(one[0].p), mo_inv);                       // undo the offset
   }
@@ -708,12 +804,22 @@ int svrh_stack_registrations(svr_ctx *ctx, const svr_ncc_backend *backend, int n
 int svrh_slice_to_volume_registration(svr_ctx *ctx, const svr_ncc_backend *backend, int n_slices, const float *slices, int sx, int sy,
                                       const svr_image_attr *attrs, double *transformations, const svr_image_attr *recon_attr,
                                       const float *reconstructed, int flags, long *n_evaluations_or_null, char err[256]) {
-  if ((!ctx && !backend) || n_slices < 1 || !slices || !attrs || !transformations || !recon_attr || !reconstructed) {
+  return svrh_slice_to_volume_registration_ex(ctx, backend, nullptr, SVRH_SIM_CC, n_slices, slices, sx, sy, attrs, transformations, recon_attr,
+                                              reconstructed, flags, n_evaluations_or_null, err);
+}
+
+int svrh_slice_to_volume_registration_ex(svr_ctx *ctx, const svr_ncc_backend *backend, const svr_nmi_backend *nmi_backend, int similarity,
+                                         int n_slices, const float *slices, int sx, int sy, const svr_image_attr *attrs, double *transformations,
+                                         const svr_image_attr *recon_attr, const float *reconstructed, int flags, long *n_evaluations_or_null,
+                                         char err[256]) {
+  const int nmi = similarity == SVRH_SIM_NMI;
+  if ((similarity != SVRH_SIM_CC && !nmi) || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_slices < 1 || !slices ||
+      !attrs || !transformations || !recon_attr || !reconstructed) {
     set_err(err, "svrh_slice_to_volume_registration: bad arguments");
     return 1;
   }
   if (n_evaluations_or_null) *n_evaluations_or_null = 0;
-  const Backend be{ctx, backend};
+  const Backend be{ctx, nmi ? nullptr : backend, nmi ? nmi_backend : nullptr};
   Vol<short> source;                                                      // irtkGreyImage source = _reconstructed, RG.cc:2031
   source.a = *recon_attr;
   source.d.resize(source.n());
@@ -757,7 +863,7 @@ int svrh_slice_to_volume_registration(svr_ctx *ctx, const svr_ncc_backend *backe
     which.push_back(s);
   }
   std::string e;
-  const int rc = run_registrations(be, targets, source, 1, (short)-1, n_evaluations_or_null, e);   // SliceToVolume, SetTargetPadding(-1)
+  const int rc = run_registrations(be, targets, source, 1, (short)-1, nmi, n_evaluations_or_null, e);   // SliceToVolume, SetTargetPadding(-1)
   if (rc) { set_err(err, e); return rc; }
   for (size_t k = 0; k < targets.size(); ++k) {
     const M4 m = mul(params_to_matrix(targets[k].p), mo_inv[which[k]]);
@@ -817,12 +923,22 @@ static void split_even_odd_half(const Vol<double> &image, int packages, std::vec
 int svrh_package_to_volume(svr_ctx *ctx, const svr_ncc_backend *backend, int n_stacks, const svr_image_attr *attrs, const double *const *stacks,
                            const int *pack_num, int evenodd, int half, int half_iter, double *transformations,
                            const svr_image_attr *recon_attr, const float *reconstructed, long *n_evaluations_or_null, char err[256]) {
-  if ((!ctx && !backend) || n_stacks < 1 || !attrs || !stacks || !pack_num || !transformations || !recon_attr || !reconstructed) {
+  return svrh_package_to_volume_ex(ctx, backend, nullptr, SVRH_SIM_CC, n_stacks, attrs, stacks, pack_num, evenodd, half, half_iter, transformations,
+                                   recon_attr, reconstructed, n_evaluations_or_null, err);
+}
+
+int svrh_package_to_volume_ex(svr_ctx *ctx, const svr_ncc_backend *backend, const svr_nmi_backend *nmi_backend, int similarity, int n_stacks,
+                              const svr_image_attr *attrs, const double *const *stacks, const int *pack_num, int evenodd, int half, int half_iter,
+                              double *transformations, const svr_image_attr *recon_attr, const float *reconstructed, long *n_evaluations_or_null,
+                              char err[256]) {
+  const int nmi = similarity == SVRH_SIM_NMI;
+  if ((similarity != SVRH_SIM_CC && !nmi) || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_stacks < 1 || !attrs ||
+      !stacks || !pack_num || !transformations || !recon_attr || !reconstructed) {
     set_err(err, "svrh_package_to_volume: bad arguments");
     return 1;
   }
   if (n_evaluations_or_null) *n_evaluations_or_null = 0;
-  const Backend be{ctx, backend};
+  const Backend be{ctx, nmi ? nullptr : backend, nmi ? nmi_backend : nullptr};
   Vol<short> source;
   source.a = *recon_attr;
   source.d.resize(source.n());
@@ -871,7 +987,7 @@ int svrh_package_to_volume(svr_ctx *ctx, const svr_ncc_backend *backend, int n_s
     matrix_to_params(tg.matrix, tg.p);
   }
   std::string e;
-  const int rc = run_registrations(be, targets, source, 1, (short)0, n_evaluations_or_null, e);
+  const int rc = run_registrations(be, targets, source, 1, (short)0, nmi, n_evaluations_or_null, e);
   if (rc) { set_err(err, e); return rc; }
   for (size_t k = 0; k < packs.size(); ++k) {
     const M4 m = mul(params_to_matrix(targets[k].p), packs[k].mo_inv);      // PutMatrix: the first slice keeps this matrix
@@ -909,6 +1025,19 @@ int svrh_irtk_blur_with_padding(const svr_image_attr *attr, int16_t *data, doubl
   blur_with_padding(v, sigma, (short)padding);
   memcpy(data, v.d.data(), sizeof(int16_t) * v.d.size());
   return 0;
+}
+
+int svrh_irtk_number_of_bins(int16_t *data_or_null, long n, int min, int max, int *width_or_null) {
+  int width = 1;
+  const int nbins = nmi_number_of_bins(min, max, width);
+  if (data_or_null) nmi_bin(data_or_null, (size_t)n, width);
+  if (width_or_null) *width_or_null = width;
+  return nbins;
+}
+
+double svrh_nmi_sums(const uint32_t *hist64, int target_nbins, int source_nbins, double sums4[4]) {
+  nmi_sums(hist64, target_nbins, source_nbins, sums4);
+  return nmi_from_sums(sums4);
 }
 
 void svrh_irtk_rigid_parameters(const double matrix16[16], double params6[6], double *rebuilt16_or_null) {

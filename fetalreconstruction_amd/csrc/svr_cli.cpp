@@ -16,7 +16,9 @@
 // stack-to-stack registration (StackRegistrations, before and after the other stacks are cropped, main.cc:661,711).
 // Slice-to-volume registration is the reference's default IRTK schedule (csrc/irtk_reg.cpp, every similarity evaluation
 // on the GPU) or, with --useGPUReg, the reference's GPU registration.  --no_registration (not a reference option) skips
-// both.  --enableBiasCorrection (not a reference option either: the reference hard-wires its bias correction off) runs
+// both.  --useNMI makes the IRTK schedule's slice-to-volume and package-to-volume registrations use normalised mutual
+// information (csrc/svr_nmi.inc), as GuessParameterSliceToVolume(true) would; the reference parses it and never passes it
+// on (main.cc:210), so this is a deviation; the GPU registration stays CC-only and refuses it.  --enableBiasCorrection (not a reference option either: the reference hard-wires its bias correction off) runs
 // BiasGPU / NormaliseBiasGPU in every SR iteration with --sigma, --global_bias_correction and --low_intensity_cutoff as the
 // reference's main() would pass them.  --packages runs PackageToVolume with the schedule of main.cc:832-864; --tfolder reads transformation<i>.dof per
 // slice and --debug writes them next to the output.  Not built, refused loudly: patch/superpixel
@@ -39,7 +41,7 @@ int main(int argc, char **argv) {
   std::vector<int> force_excluded, devices, packages;
   int iterations = 4, levels = 3, rec_first = 4, rec_last = 13, num_stacks_tuner = 0;
   double resolution = 0.75, average = 700, delta = 150, lambda = 0.02, last_lambda = 0.01, smooth_mask = 4;
-  bool no_matching = false, use_gpu_reg = false, no_registration = false;
+  bool no_matching = false, use_gpu_reg = false, no_registration = false, use_nmi = false;
   double sigma = 12.0, low_intensity_cutoff = 0.01;                      // main.cc:172, 181
   bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
@@ -83,6 +85,7 @@ int main(int argc, char **argv) {
     else if (o == "--rec_iterations_first") rec_first = atoi(one().c_str());
     else if (o == "--rec_iterations_last") rec_last = atoi(one().c_str());
     else if (o == "--useGPUReg") use_gpu_reg = true;
+    else if (o == "--useNMI") use_nmi = true;                             // main.cc:210 parses it and never calls setUseNMI(): here it takes effect
     else if (o == "-p" || o == "--packages") { std::vector<std::string> v; multi(v); for (auto &x : v) packages.push_back(atoi(x.c_str())); }
     else if (o == "--no_registration") no_registration = true;
     else if (o == "--tfolder") tfolder = one();
@@ -101,7 +104,10 @@ int main(int argc, char **argv) {
              "       [--lastIterLambda 0.01] [--smooth_mask 4] [--no_intensity_matching] [--force_exclude i ..]\n"
              "       [--rec_iterations_first 4] [--rec_iterations_last 13] [--packages p_1 ..] [--useGPUReg] [--no_registration] [--tfolder dir] [--sfolder dir]\n"
              "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n"
-             "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection]\n"
+             "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
+             "  --useNMI                deviation from the reference, whose --useNMI is parsed and never takes effect: slice-to-volume and\n"
+             "                          package-to-volume registration use normalised mutual information (64 bins, IRTK's histogram metric)\n"
+             "                          instead of cross correlation -- for stacks whose contrast differs.  Not with --useGPUReg (CC only).\n"
              "  --enableBiasCorrection  deviation from the reference, whose bias correction cannot be switched on: run BiasGPU and\n"
              "                          NormaliseBiasGPU in every SR iteration (bias field stdev --sigma mm; sigma <= 0: no bias step).\n"
              "                          Without it bias correction is off, as in the reference; --disableBiasCorrection is accepted and changes nothing.\n");
@@ -111,6 +117,9 @@ int main(int argc, char **argv) {
     }
   }
   if (output.empty() || inputs.empty()) die("-o and -i are required (try --help)");
+  if (use_nmi && use_gpu_reg)
+    die("--useNMI selects normalised mutual information for the IRTK registration; the reference's GPU registration (--useGPUReg) is "
+        "cross-correlation only: use one or the other");
   if (num_stacks_tuner > 0 && (size_t)num_stacks_tuner < inputs.size()) {      // main.cc:406-419: only the first stacks are used
     inputs.resize(num_stacks_tuner);
     if (tspecs.size() > (size_t)num_stacks_tuner) tspecs.resize(num_stacks_tuner);
@@ -402,8 +411,8 @@ int main(int argc, char **argv) {
       long evals = 0;
       char e[256] = {0};
       svr::unpermute_rows(T, 16, order);                                   // (packages are sub-stacks: one transformation per slice, stack after stack)
-      if (svrh_package_to_volume(ctx, nullptr, (int)n, at.data(), ptr.data(), packages.data(), it >= 2, it >= 3, it >= 4 ? it - 2 : 1, T.data(),
-                                 &tattr, vol.data(), &evals, e))
+      if (svrh_package_to_volume_ex(ctx, nullptr, nullptr, use_nmi ? SVRH_SIM_NMI : SVRH_SIM_CC, (int)n, at.data(), ptr.data(), packages.data(),
+                                    it >= 2, it >= 3, it >= 4 ? it - 2 : 1, T.data(), &tattr, vol.data(), &evals, e))
         die(std::string("package-to-volume registration: ") + e);
       svr::permute_rows(T, 16, order);
       fprintf(stderr, "package-to-volume registration: %ld similarity evaluations\n", evals);
@@ -418,7 +427,8 @@ int main(int argc, char **argv) {
         ENG(svr_sync_cpu(ctx, vol.data()));                               // _reconstructed after SyncCPU, main.cc:1189
         long evals = 0;
         char e[256] = {0};
-        if (svrh_slice_to_volume_registration(ctx, nullptr, ns, grid.data(), mx, my, sattr.data(), T.data(), &tattr, vol.data(), 0, &evals, e))
+        if (svrh_slice_to_volume_registration_ex(ctx, nullptr, nullptr, use_nmi ? SVRH_SIM_NMI : SVRH_SIM_CC, ns, grid.data(), mx, my, sattr.data(),
+                                                 T.data(), &tattr, vol.data(), 0, &evals, e))
           die(std::string("slice-to-volume registration: ") + e);
         fprintf(stderr, "slice-to-volume registration: %ld similarity evaluations\n", evals);
       }

@@ -1246,6 +1246,13 @@ struct svr_ctx {
   double *d_ncc_m = nullptr;
   long long *d_ncc_s = nullptr;
   size_t ncc_cap = 0;
+  unsigned char *d_nmi_io = nullptr;     // grow-only scratch of svr_nmi_evaluate (svr_nmi.inc): requests in, sums and histograms out
+  size_t nmi_cap = 0;
+  std::vector<unsigned char> nmi_staging;
+  double *d_nmi_terms = nullptr;         // c log c for c = 0 .. nmi_terms_n - 1, from the host's libm
+  size_t nmi_terms_n = 0;
+  unsigned *d_nmi_merge = nullptr;       // merge slots of split evaluations + their counters, all zero between calls
+  size_t nmi_slots = 0;
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
   uint32_t reg_vx = 0, reg_vy = 0, reg_vz = 0;
 
@@ -2210,6 +2217,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_reg_source);
   free_dev(ctx->d_pyr_full[0]); free_dev(ctx->d_pyr_full[1]); free_dev(ctx->d_pyr_a); free_dev(ctx->d_pyr_b); free_dev(ctx->d_pyr_meta);
   free_dev(ctx->d_ncc_idx); free_dev(ctx->d_ncc_m); free_dev(ctx->d_ncc_s);
+  free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
   free_dev(ctx->d_coeff); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff_order);
   reg_free(ctx->reg);
   cell_free(ctx->cell);
@@ -4046,4 +4054,5 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 
 #include "svr_reg.inc"
 #include "svr_pyr.inc"
+#include "svr_nmi.inc"
 #include "svr_em.inc"

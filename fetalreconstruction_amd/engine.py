@@ -40,7 +40,7 @@ EXPORTS = [
     "svr_superresolution_backproject", "svr_superresolution_update", "svr_robust_statistics_sums",
     "svr_mstep_sums", "svr_scale_volume_sums", "svr_scale_volume_apply", "svr_timer_get",
     "svr_unit_counts", "svr_fallbacks", "svr_clock_probe", "svr_slice_em_setup", "svr_slice_em_set_state", "svr_mstep_estep_device", "svr_slice_em_run", "svr_slice_em_apply_weights", "svr_slice_em_fetch", "svr_slice_em_set_patch_form", "svr_cell_stats", "svr_pair_pack", "svr_pair_unpack", "svr_timer_reset", "svr_timer_enable", "svr_timer_begin", "svr_timer_end", "svr_timer_add", "svr_counters", "svr_get_stream", "svr_device", "svr_device_count", "svr_combine_weights", "svr_update_stack_sizes", "svr_ncc_set_targets", "svr_ncc_set_source",
-    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
+    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_pvr_cc_patches", "svr_pvr_register_patches",
@@ -366,6 +366,25 @@ class Reconstruction:
         ncc = np.zeros(len(idx), np.float64)
         self._ck(self._lib.svr_ncc_evaluate(self._h, len(idx), _p(idx), _p(m), _p(sums), _p(ncc)))
         return ncc, sums
+
+    def nmi_bin_source(self, width):
+        """irtkCalculateNumberOfBins' rescaling of the current source, in place (v > 0 -> v // width)"""
+        self._ck(self._lib.svr_nmi_bin_source(self._h, int(width)))
+
+    def nmi_evaluate(self, planes_per_eval, target_index, matrices, target_width, target_nbins, source_nbins, histograms=False):
+        """svr_nmi_evaluate -> ({n, S_xy, S_x, S_y} float64 [n_eval][4], uint32 joint histograms [n_eval][64][64] or None).
+        Evaluation e spans planes_per_eval[e] consecutive entries of target_index / matrices."""
+        ppe = np.ascontiguousarray(planes_per_eval, np.int32)
+        idx = np.ascontiguousarray(target_index, np.int32)
+        m = np.ascontiguousarray(matrices, np.float64).reshape(len(idx), 16)
+        w, nb = np.ascontiguousarray(target_width, np.int32), np.ascontiguousarray(target_nbins, np.int32)
+        if len(idx) != int(ppe.sum()) or len(w) != len(ppe) or len(nb) != len(ppe):
+            raise SvrError("nmi_evaluate: one width and bin count per evaluation, one index and matrix per plane")
+        out = np.zeros((len(ppe), 4), np.float64)
+        h = np.zeros((len(ppe), 64, 64), np.uint32) if histograms else None
+        self._ck(self._lib.svr_nmi_evaluate(self._h, len(ppe), _p(ppe), _p(idx), _p(m), _p(w), _p(nb), int(source_nbins), _p(out),
+                                            _p(h) if h is not None else None))
+        return out, h
 
     # ---- GPU slice-to-volume registration (RC.cuh:326-338) ------------------------------------
     def initRegStorageVolumes(self, W, H, ns, dim=(1.0, 1.0, 1.0)):

@@ -29,7 +29,8 @@ PVR_HOST_EXPORTS = ["pvrh_create", "pvrh_destroy", "pvrh_last_error", "pvrh_init
                     "pvrh_estep", "pvrh_mstep", "pvrh_scale", "pvrh_reconstruct_iteration", "pvrh_register_patches", "pvrh_get_state",
                     "pvrh_create_sharded", "pvrh_force_collectives", "pvrh_set_slab_update", "pvrh_sr_iteration", "pvrh_set_unit_order"]      # csrc/pvr_host.cpp
 IRTK_EXPORTS = ["svrh_stack_registrations", "svrh_slice_to_volume_registration", "svrh_package_to_volume", "svrh_irtk_resample_with_padding",
-                "svrh_irtk_blur_with_padding", "svrh_irtk_rigid_parameters"]                                  # csrc/irtk_reg.cpp
+                "svrh_irtk_blur_with_padding", "svrh_irtk_rigid_parameters", "svrh_slice_to_volume_registration_ex", "svrh_package_to_volume_ex",
+                "svrh_irtk_number_of_bins", "svrh_nmi_sums"]                                                  # csrc/irtk_reg.cpp
 IO_EXPORTS = ["svr_nifti_read", "svr_nifti_write", "svr_free", "svr_dof_read", "svr_dof_write", "svr_host_threads"]      # csrc/svr_io.cpp, declared in svr_host.h
 
 
@@ -494,10 +495,75 @@ class NccBackend:
         self.struct = _NccBackend(None, *self._cbs)
 
 
+_NMI_EVAL = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                        C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint32))
+
+
+class _NmiBackend(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("set_targets", _SET_T), ("set_source", _SET_S), ("evaluate", _NMI_EVAL)]
+
+
+class NmiBackend:
+    """struct svr_nmi_backend over a Python evaluator `fn(planes int16 [nz][ty][tx], M float64 [nz][4][4], source int16 [z][y][x],
+    target_width, target_nbins, source_nbins) -> the joint histogram uint32 [64][64], [source bin][target bin]` (the targets
+    arrive unbinned, the source binned): how the CPU tests put a numpy restatement of the NMI evaluation behind the C++ schedule.
+    keep=True records (histogram, target_nbins, source_nbins) of every evaluation in `log`."""
+
+    def __init__(self, fn, keep=False):
+        self.fn, self.targets, self.source, self.calls, self.log = fn, None, None, 0, ([] if keep else None)
+
+        def set_targets(user, n, tx, ty, t):
+            self.targets = np.ctypeslib.as_array(t, shape=(n, ty, tx)).copy()
+            return 0
+
+        def set_source(user, size, s):
+            self.source = np.ctypeslib.as_array(s, shape=(size[2], size[1], size[0])).copy()
+            return 0
+
+        def evaluate(user, n, ppe, idx, mats, width, nbins, nbs, hist):
+            try:
+                p = np.ctypeslib.as_array(ppe, shape=(n,))
+                total = int(p.sum())
+                i = np.ctypeslib.as_array(idx, shape=(total,))
+                m = np.ctypeslib.as_array(mats, shape=(total, 4, 4))
+                w, nb = np.ctypeslib.as_array(width, shape=(n,)), np.ctypeslib.as_array(nbins, shape=(n,))
+                out = np.ctypeslib.as_array(hist, shape=(n, 64, 64))
+                at = 0
+                for e in range(n):
+                    k = int(p[e])
+                    out[e] = self.fn(self.targets[i[at:at + k]], m[at:at + k], self.source, int(w[e]), int(nb[e]), int(nbs))
+                    if self.log is not None:
+                        self.log.append((out[e].copy(), int(nb[e]), int(nbs)))
+                    at += k
+                self.calls += 1
+                return 0
+            except Exception as ex:      # never let an exception cross the C boundary
+                print("nmi backend failed:", ex)
+                return 1
+
+        self._cbs = (_SET_T(set_targets), _SET_S(set_source), _NMI_EVAL(evaluate))
+        self.struct = _NmiBackend(None, *self._cbs)
+
+
+SIMILARITY = {"cc": 0, "nmi": 1}          # SVRH_SIM_CC, SVRH_SIM_NMI (include/svr_host.h)
+
+
 def _reg_lib():
     lib = _engine.load_library()
     lib.svrh_irtk_rigid_parameters.restype = None
+    lib.svrh_nmi_sums.restype = C.c_double
     return lib
+
+
+def _backends(similarity, backend):
+    """(svr_ncc_backend*, svr_nmi_backend*, SVRH_SIM_*) for the _ex entry points"""
+    sim = SIMILARITY.get(str(similarity).lower())
+    if sim is None:
+        raise ValueError(f"similarity must be one of {sorted(SIMILARITY)}, not {similarity!r}")
+    if backend is not None and isinstance(backend, NmiBackend) != (sim == 1):
+        raise ValueError("similarity='nmi' takes an NmiBackend, 'cc' an NccBackend")
+    ptr = C.byref(backend.struct) if backend is not None else None
+    return (None, ptr, sim) if sim == 1 else (ptr, None, sim)
 
 
 def StackRegistrations(rec, stacks, attrs, transformations, template_number, mask=None, mask_attr=None, backend=None, keep_origin=False):
@@ -521,11 +587,14 @@ def StackRegistrations(rec, stacks, attrs, transformations, template_number, mas
     return t.reshape(n, 4, 4), nev.value
 
 
-def SliceToVolumeRegistration(rec, slices, slice_attrs, transformations, recon_attr, reconstructed, backend=None, no_resample=False):
+def SliceToVolumeRegistration(rec, slices, slice_attrs, transformations, recon_attr, reconstructed, backend=None, no_resample=False,
+                              similarity="cc"):
     """irtkReconstruction::SliceToVolumeRegistration (RG.cc:1991-2059, 2291-2303), the reference's default registration
     -> (new transformations [n][4][4], number of evaluations).  slices: the padded float32 grid [n][sy][sx].
-    no_resample: the patch-to-volume registration of the patch-based command line (patchBased2D3DRegistration.cpp:88-225)."""
+    no_resample: the patch-to-volume registration of the patch-based command line (patchBased2D3DRegistration.cpp:88-225).
+    similarity: "cc" (the reference's) or "nmi" (GuessParameterSliceToVolume(true); `backend` then an NmiBackend)."""
     lib = _reg_lib()
+    ncc_be, nmi_be, sim = _backends(similarity, backend)
     g = np.ascontiguousarray(slices, np.float32)
     n, sy, sx = g.shape
     at = (ImageAttr * n)(*[ImageAttr.of(a) for a in slice_attrs])
@@ -533,18 +602,20 @@ def SliceToVolumeRegistration(rec, slices, slice_attrs, transformations, recon_a
     vol = np.ascontiguousarray(reconstructed, np.float32)
     ra = ImageAttr.of(recon_attr)
     nev, err = C.c_long(0), C.create_string_buffer(256)
-    rc = lib.svrh_slice_to_volume_registration(rec._h if rec is not None else None, C.byref(backend.struct) if backend else None, n,
-                                               g.ctypes.data_as(C.c_void_p), sx, sy, at, t.ctypes.data_as(C.c_void_p), C.byref(ra),
-                                               vol.ctypes.data_as(C.c_void_p), 1 if no_resample else 0, C.byref(nev), err)
+    rc = lib.svrh_slice_to_volume_registration_ex(rec._h if rec is not None else None, ncc_be, nmi_be, sim, n,
+                                                  g.ctypes.data_as(C.c_void_p), sx, sy, at, t.ctypes.data_as(C.c_void_p), C.byref(ra),
+                                                  vol.ctypes.data_as(C.c_void_p), 1 if no_resample else 0, C.byref(nev), err)
     if rc != 0:
         raise _engine.SvrError(f"svrh_slice_to_volume_registration: {err.value.decode()}")
     return t.reshape(n, 4, 4), nev.value
 
 
 def PackageToVolume(rec, stacks, attrs, pack_num, transformations, recon_attr, reconstructed, evenodd=False, half=False, half_iter=1,
-                    backend=None):
-    """irtkReconstruction::PackageToVolume (RG.cc:5096-5192) -> (new per-slice transformations [n][4][4], evaluations)."""
+                    backend=None, similarity="cc"):
+    """irtkReconstruction::PackageToVolume (RG.cc:5096-5192) -> (new per-slice transformations [n][4][4], evaluations).
+    similarity: "cc" or "nmi", as for SliceToVolumeRegistration."""
     lib = _reg_lib()
+    ncc_be, nmi_be, sim = _backends(similarity, backend)
     n = len(stacks)
     data = [np.ascontiguousarray(s, np.float64) for s in stacks]
     ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in data])
@@ -555,9 +626,9 @@ def PackageToVolume(rec, stacks, attrs, pack_num, transformations, recon_attr, r
     vol = np.ascontiguousarray(reconstructed, np.float32)
     ra = ImageAttr.of(recon_attr)
     nev, err = C.c_long(0), C.create_string_buffer(256)
-    rc = lib.svrh_package_to_volume(rec._h if rec is not None else None, C.byref(backend.struct) if backend else None, n, at, ptrs, pk,
-                                    int(bool(evenodd)), int(bool(half)), int(half_iter), t.ctypes.data_as(C.c_void_p), C.byref(ra),
-                                    vol.ctypes.data_as(C.c_void_p), C.byref(nev), err)
+    rc = lib.svrh_package_to_volume_ex(rec._h if rec is not None else None, ncc_be, nmi_be, sim, n, at, ptrs, pk,
+                                       int(bool(evenodd)), int(bool(half)), int(half_iter), t.ctypes.data_as(C.c_void_p), C.byref(ra),
+                                       vol.ctypes.data_as(C.c_void_p), C.byref(nev), err)
     if rc != 0:
         raise _engine.SvrError(f"svrh_package_to_volume: {err.value.decode()}")
     return t.reshape(-1, 4, 4), nev.value
@@ -579,6 +650,24 @@ def irtk_blur_with_padding(data, attr, sigma, padding):
     d = np.ascontiguousarray(data, np.int16).copy()
     _reg_lib().svrh_irtk_blur_with_padding(C.byref(ImageAttr.of(attr)), d.ctypes.data_as(C.c_void_p), C.c_double(sigma), int(padding))
     return d
+
+
+def irtk_number_of_bins(mn, mx, data=None):
+    """irtkCalculateNumberOfBins(image, 64, mn, mx) -> (nbins, width, the binned copy of `data` or None)"""
+    lib = _reg_lib()
+    d = None if data is None else np.ascontiguousarray(data, np.int16).copy()
+    w = C.c_int(0)
+    nb = lib.svrh_irtk_number_of_bins(d.ctypes.data_as(C.c_void_p) if d is not None else None, C.c_long(0 if d is None else d.size),
+                                      int(mn), int(mx), C.byref(w))
+    return nb, w.value, d
+
+
+def nmi_sums(hist, target_nbins, source_nbins):
+    """the schedule's entropy sums of one joint histogram [64][64] -> ({n, S_xy, S_x, S_y}, NMI)"""
+    h = np.ascontiguousarray(hist, np.uint32).reshape(64, 64)
+    s = np.zeros(4)
+    v = _reg_lib().svrh_nmi_sums(h.ctypes.data_as(C.c_void_p), int(target_nbins), int(source_nbins), s.ctypes.data_as(C.c_void_p))
+    return s, v
 
 
 def irtk_rigid_parameters(matrix):

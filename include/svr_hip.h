@@ -289,6 +289,23 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
 int svr_ncc_set_source(svr_ctx *ctx, const uint32_t size[3], const int16_t *source_or_null);
 int svr_ncc_evaluate(svr_ctx *ctx, int n_eval, const int *target_index, const double *matrices,
                      int64_t *sums6_or_null, double *ncc_or_null);
+/* Normalised mutual information of the same registration (csrc/svr_nmi.inc; the reference's --useNMI, which IRTK evaluates with
+ * irtkNormalisedMutualInformationSimilarityMetric over irtkHistogram_2D: IRRWP.cc:534-610, H2D.cc:443-623).  The targets and
+ * the source are the ones svr_ncc_evaluate reads (svr_ncc_set_targets / svr_ncc_alloc_targets + svr_pyr_level, svr_ncc_set_source
+ * or svr_pyr_level slot 0).
+ * svr_nmi_bin_source: irtkCalculateNumberOfBins on the source (irtkUtil.cc:438-474), in place: every value v > 0 becomes
+ *   int(v / width).  The source is binned before it is interpolated; the targets are binned on the fly.
+ * svr_nmi_evaluate: n_eval evaluations; evaluation e is one candidate matrix on planes_per_eval[e] target planes (1 for a slice,
+ *   nz for a package), whose per-plane target index and row-major 4x4 (as for svr_ncc_evaluate) follow one another in
+ *   target_index / matrices.  The joint histogram of an evaluation spans all of its planes: bin (target v / target_width[e],
+ *   source round(value)) of target_nbins[e] x source_nbins, both at most 64.  out4[e] = {n, S_xy, S_x, S_y}: the number of samples
+ *   and the sums of c log c over the nonzero joint bins in irtkHistogram_2D's visit order (source-major), over the target marginal
+ *   and over the source marginal, each added serially in that order; the entropies are -S/n + log n, the NMI (E_x + E_y) / E_xy
+ *   (0 when n = 0).  hist_or_null: uint32 [n_eval][64][64], [source bin][target bin], zero outside the bins.  A sample outside
+ *   the bins (widths or bin counts that do not fit the images) fails the call. */
+int svr_nmi_bin_source(svr_ctx *ctx, int width);
+int svr_nmi_evaluate(svr_ctx *ctx, int n_eval, const int *planes_per_eval, const int *target_index, const double *matrices,
+                     const int *target_width, const int *target_nbins, int source_nbins, double *out4, uint32_t *hist_or_null);
 
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::

@@ -224,6 +224,36 @@ int svrh_slice_to_volume_registration(svr_ctx *ctx, const svr_ncc_backend *backe
 int svrh_package_to_volume(svr_ctx *ctx, const svr_ncc_backend *backend, int n_stacks, const svr_image_attr *attrs, const double *const *stacks,
                            const int *pack_num, int evenodd, int half, int half_iter, double *transformations,
                            const svr_image_attr *recon_attr, const float *reconstructed, long *n_evaluations_or_null, char err[256]);
+/* ---- normalised mutual information (the reference's --useNMI: GuessParameterSliceToVolume(true), IRRWP.cc:304-321) ----------
+ * The same schedules with irtkNormalisedMutualInformationSimilarityMetric (64 bins, irtkCalculateNumberOfBins per image and
+ * level) instead of cross correlation; similarity SVRH_SIM_CC = the entry points above.  `nmi_backend` NULL = the engine
+ * (svr_nmi_evaluate); tests pass a CPU evaluator that returns one joint histogram per evaluation: hist[n_eval][64][64],
+ * [source bin][target bin], zero outside target_nbins[e] x source_nbins.  Evaluation e spans planes_per_eval[e] consecutive
+ * entries of target_index / matrices (as for svr_nmi_evaluate); the targets are handed over unbinned (the evaluator takes
+ * v / target_width[e]), the source binned.  The schedule turns every histogram into {n, S_xy, S_x, S_y} with the serial loops
+ * of irtkHistogram_2D (svrh_nmi_sums) -- the engine's sums equal them bit for bit. */
+#define SVRH_SIM_CC 0
+#define SVRH_SIM_NMI 1
+typedef struct svr_nmi_backend {
+  void *user;
+  int (*set_targets)(void *user, int n, int tx, int ty, const int16_t *targets);
+  int (*set_source)(void *user, const uint32_t size[3], const int16_t *source);
+  int (*evaluate)(void *user, int n_eval, const int *planes_per_eval, const int *target_index, const double *matrices,
+                  const int *target_width, const int *target_nbins, int source_nbins, uint32_t *hist);
+} svr_nmi_backend;
+int svrh_slice_to_volume_registration_ex(svr_ctx *ctx, const svr_ncc_backend *backend, const svr_nmi_backend *nmi_backend, int similarity,
+                                         int n_slices, const float *slices, int sx, int sy, const svr_image_attr *attrs, double *transformations,
+                                         const svr_image_attr *recon_attr, const float *reconstructed, int flags, long *n_evaluations_or_null,
+                                         char err[256]);
+int svrh_package_to_volume_ex(svr_ctx *ctx, const svr_ncc_backend *backend, const svr_nmi_backend *nmi_backend, int similarity, int n_stacks,
+                              const svr_image_attr *attrs, const double *const *stacks, const int *pack_num, int evenodd, int half, int half_iter,
+                              double *transformations, const svr_image_attr *recon_attr, const float *reconstructed, long *n_evaluations_or_null,
+                              char err[256]);
+/* irtkCalculateNumberOfBins(image, 64, min, max) (irtkUtil.cc:438-474): returns the number of bins, the width through
+ * width_or_null, and bins data_or_null[n] in place (v > 0 -> int(v / width)); max < min gives 1 bin of width 1 */
+int svrh_irtk_number_of_bins(int16_t *data_or_null, long n, int min, int max, int *width_or_null);
+/* {n, S_xy, S_x, S_y} of one histogram [64][64] as above; returns NormalizedMutualInformation (0 when n = 0) */
+double svrh_nmi_sums(const uint32_t *hist64, int target_nbins, int source_nbins, double sums4[4]);
 /* building blocks (irtkResamplingWithPadding<short>, irtkGaussianBlurringWithPadding<short>, irtkRigidTransformation::
  * Matrix2Parameters / UpdateMatrix), exported for the tests */
 int svrh_irtk_resample_with_padding(const svr_image_attr *attr, const int16_t *data, double rx, double ry, double rz, int padding,
