@@ -583,7 +583,6 @@ int main(int argc, char **argv) {
     const size_t o = (size_t)rlo[r];
     ENGR(r, svr_set_option(ctxs[r], "pvr", 1));
     if (coeff_table) ENGR(r, svr_set_option(ctxs[r], "coeff_table", 1));
-    ENGR(r, svr_set_option(ctxs[r], "tune_tiles", 32768));                 // a run is a few dozen PSF launches: cheap tuning trials
     ENGR(r, svr_init_reconstruction_volume(ctxs[r], vsize, vdim, existing.empty() ? nullptr : existing.data(), 12.0f));   // copyFromHost :310-314
     ENGR(r, svr_set_mask(ctxs[r], vsize, vdim, maskf.data(), 12.0f));
     const uint32_t ssize[3] = {(uint32_t)px, (uint32_t)py, (uint32_t)nl};

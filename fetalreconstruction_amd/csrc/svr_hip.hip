@@ -654,7 +654,6 @@ struct TileArgs {
   uint32_t ntiles;
   int tiles_x, tiles_y;
   int cap;                 // voxels of LDS accumulator available
-  int dbg;                 // dev experiments only (0 = production)
   int tw, th;              // tile size in pixels, tw * th <= 64
   int gauss;               // scatter kernels: 1 = Gaussian-reconstruction pass 2 (recon|volw instead of addon|cmap)
 };
@@ -1137,15 +1136,12 @@ struct svr_ctx {
   uint32_t n_active = 0, n_psf = 0, n_tiles = 0;
   int tiles_x = 0, tiles_y = 0, tile_w = 4, tile_h = 4;
   int reg_blind = 4;        // GPU slice-to-volume registration: line-search steps per host round trip, the active count on the device (0: a round trip per step)
-  int tune_tiles = 0;       // tiles a tuner's trial launch runs on (0: TUNE_TILES); a short job -- the command lines -- asks for fewer
   int reg_red_threads = 0;  // workgroup size of the registration's per-image reductions: 0 = by image size, 256, 1024
   int reg_batch = 1;        // GPU slice-to-volume registration: the twelve evaluations of a gradient as one launch sequence (0: one by one)
   int pvr_reg_levels = 3, pvr_reg_steps = 4, pvr_reg_iterations = 20;   // PatchBased2D3DRegistration_gpu2 schedule (tests shorten it)
   bool psf_list_valid = false;
   unsigned char *d_gauss_flag = nullptr;   // pixels whose sume passed in the current Gaussian pass
   uint32_t *d_tiles_tmp = nullptr;         // tile list of the Gaussian passes
-  uint32_t *d_tiles_sample = nullptr;      // every stride-th tile, for the trial launches of the tuners
-  size_t tiles_sample_cap = 0;
   size_t tiles_tmp_cap = 0;                // its capacity in tiles (the tile shapes can change between calls)
   int gauss_mode = 1;                      // 1 = unit-based pass 1 (fwd_unit_kernel<GAUSS1>) + the LDS scatter, 0 = psf_kernel<MODE_GAUSS>
   uint32_t *d_tiles_fwd = nullptr;   // tiles of fwd_tw x fwd_th pixels for fwd_unit_kernel
@@ -1155,14 +1151,10 @@ struct svr_ctx {
   int fwd_unit_cap = 9300;  // box voxels (float2) of fwd_unit_kernel: 72.7 KiB + up to 6.6 KiB static = 64 LDS granules of 1280 B -> 2 workgroups of 8 waves per CU (9400 would push the GAUSS1 table instantiation to 65)
   int fwd_mode = 2;         // 2 = the gather over (cell, plane) items (fwd_cell_kernel, svr_cell.inc; SVR on the fly -- patch-based runs and the
                             // coefficient table take 1), >= 1 = unit-based gather per slice tile (fwd_unit_kernel), 0 = wave-per-pixel kernel (psf_kernel<MODE_FWD>)
-  // The forward tile shape that suits a problem depends on how many voxels a pixel spans: at 2 voxels per pixel (0.5 mm
-  // reconstructions of 1 mm pixels) the box of a 4x4 tile no longer fits the LDS and every tap falls back to global loads.  The first forward pass of a problem times the candidate shapes on the real data
-  // and keeps the fastest; the results do not depend on the shape (per-pixel sums in a fixed order).
-  bool fwd_tune_pending = false, fwd_tile_user = false;
-  int fwd_autotune = 0;     // 1: tile shapes by timed trial launches (rounds 1-3); 0: from the geometry (tile_shape_rule): every run, every rank the same
-  // the same for the scatter's tile (4x4 pixels; 4x2 and 2x2 once a pixel spans more than ~2.4 voxels), timed on the first
-  // back-projection after new slice geometry.  The scatter's sums are float atomics in run-dependent order with any shape.
-  bool back_tune_pending = false, tile_user = false, in_tune = false;
+  // The tile shapes follow from the geometry (tile_shape_rule for the unit gather, 6 x 4 for the tiled scatters: every run, every rank the
+  // same) unless the caller named one: fwd_tile_w / fwd_tile_h, tile_w / tile_h, SVR_TILE_PIN.  The results do not depend on the gather's
+  // shape (per-pixel sums in a fixed order); the tiled scatters' sums are float atomics in run-dependent order with any shape.
+  bool fwd_tile_user = false, tile_user = false;
   int pvr = 0;              // 1: patch-to-volume constants and kernels (svr_set_option "pvr")
   int pvr_mode = 1;         // PVR kernels: 1 = the unit-based gather / wave-owned scatter with support 12, 0 = wave-per-pixel (pvr_kernel)
   unsigned char *d_spx = nullptr;
@@ -1172,8 +1164,6 @@ struct svr_ctx {
                             // 1 = LDS tiles with ds_add_f32 (back_tiled_kernel), 0 = direct device-scope atomics per tap (psf_kernel<MODE_BACK>)
   int tile_cap = 0;         // voxels of LDS accumulator per workgroup
   int n_cu = 0;             // compute units of the device (the grids of the persistent cell kernels)
-  int dbg_back = 0;
-  int dbg_fwd_lds = 0;      // dev experiment: extra dynamic LDS on the forward launch (limits occupancy)
   uint32_t n_tiles_fb = 0;
   uint32_t n_tiles_fb8 = 0;   // tiles of the last scatter that the wave-owned kernel handed to the workgroup kernel (box larger than wave_cap)
   // PSF launches that were asked for on the cell path (back_mode 5 / fwd_mode 2: no atomics, bit-identical from run to run) and left it
@@ -1278,7 +1268,6 @@ struct svr_ctx {
 
   // timers
   bool timers = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;        // tile tuning
   // kernel timers: event pairs are recorded on the stream and read back later (svr_timer_get / reset / every TIMER_BATCH
   // pairs) -- timing a pass does not synchronise the stream
   struct TimedSpan { int which; hipEvent_t a, b; };
@@ -1324,10 +1313,6 @@ int fail(svr_ctx *c, int code, const std::string &msg) {
     if (!(cond)) return fail(ctx, SVR_E_STATE, std::string(__func__) + ": " + what);      \
   } while (0)
 
-// The scatter variant in effect: the cell-owned scatter (5) unless the caller named another (4 = wave-owned planes per
-// slice tile with the atomic flush, the default until round 3; patch-based runs took it until the cell kernels got five
-// slots of 12 lanes for support 12 and cell sizes that follow the pixel density: PVR4 11.3 -> 9.4 ms, PVR8spx 36.6 -> 27.3 ms).
-inline int back_mode_eff(const svr_ctx *ctx) { return ctx->back_mode; }
 void reg_free(RegState *r);
 void cell_free(CellState *c);
 
@@ -1348,7 +1333,6 @@ enum Change : unsigned {
   CH_TABLE = 1u << 11,            // the table thrown away (option coeff_invalidate: what a new slice geometry does to it)
   CH_TABLE_OFF = 1u << 12,        // the table's memory freed: the table and the cell lists
   CH_TABLE_IDS = 1u << 13,        // the pixels got new places in the table: the records' table ids
-  CH_TILE_TIMING = 1u << 14,      // time the tile shapes again (with fwd_autotune)
 };
 void invalidate(svr_ctx *ctx, unsigned changes);
 
@@ -1436,7 +1420,6 @@ void free_slices(svr_ctx *c) {
   free_dev(c->d_tiles_fwd);
   free_dev(c->d_gauss_flag);
   free_dev(c->d_tiles_tmp);
-  free_dev(c->d_tiles_sample); c->tiles_sample_cap = 0;
   free_dev(c->d_tiles_fb);
   free_dev(c->d_tiles_fb2);
   free_dev(c->d_partial); free_dev(c->d_per_slice);
@@ -1680,45 +1663,6 @@ int ensure_psf_list(svr_ctx *ctx) {
   return SVR_OK;
 }
 
-// The tuners time their candidates on real launches whose results are thrown away.  On a long tile list (S8, the
-// patch-based cases: millions of tiles, 0.05-0.2 s per launch, two dozen trials) a trial runs on one run of 4096 consecutive tiles out of every `stride` runs
-// instead, so that tuning costs what it costs on P4 (a list of up to 2 x TUNE_TILES tiles is timed whole).
-constexpr uint32_t TUNE_TILES = 131072;
-__global__ void k_sample_list(const uint32_t *src, uint32_t n_out, uint32_t stride, uint32_t run, uint32_t *dst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_out) dst[i] = src[(size_t)(i / run) * run * stride + i % run];
-}
-struct TileSample {
-  uint32_t **list = nullptr, *saved = nullptr;
-  uint32_t *n = nullptr, saved_n = 0;
-  float scale = 1.0f;                    // full list / timed part: the candidates are compared on the time of a whole launch
-  int begin(svr_ctx *ctx, uint32_t *&l, uint32_t &count) {
-    static const long env_tiles = getenv("SVR_TUNE_TILES") ? atol(getenv("SVR_TUNE_TILES")) : -1;   // 0: always the whole list
-    if (env_tiles == 0) return SVR_OK;
-    static const long env_run = getenv("SVR_TUNE_RUN") ? atol(getenv("SVR_TUNE_RUN")) : -1;
-    const uint32_t target = env_tiles > 0 ? (uint32_t)env_tiles : ctx->tune_tiles > 0 ? (uint32_t)ctx->tune_tiles : TUNE_TILES;
-    const uint32_t TUNE_RUN = env_run > 0 ? (uint32_t)env_run : std::min(65536u, std::max(4096u, target / 2));
-    const uint32_t stride = count / target;
-    if (stride < 2 || (uint64_t)TUNE_RUN * stride > count) return SVR_OK;
-    const uint32_t n_out = count / (TUNE_RUN * stride) * TUNE_RUN;     // whole runs only: the last index stays inside the list
-    if (ctx->tiles_sample_cap < n_out) {
-      free_dev(ctx->d_tiles_sample);
-      ctx->tiles_sample_cap = 0;
-      HIPCHK(hipMalloc(&ctx->d_tiles_sample, (size_t)n_out * sizeof(uint32_t)));
-      ctx->tiles_sample_cap = n_out;
-    }
-    hipLaunchKernelGGL(k_sample_list, dim3(nblk(n_out)), dim3(256), 0, ctx->stream, l, n_out, stride, TUNE_RUN, ctx->d_tiles_sample);
-    KCHK("k_sample_list");
-    list = &l; n = &count; saved = l; saved_n = count;
-    scale = (float)count / (float)n_out;
-    l = ctx->d_tiles_sample; count = n_out;
-    return SVR_OK;
-  }
-  void end() {
-    if (list) { *list = saved; *n = saved_n; list = nullptr; }
-  }
-};
-
 // The scatter over a tile list (back-projection into addon|cmap, or pass 2 of the Gaussian reconstruction into
 // recon|volw): the wave-owned kernel with a box of `wave_cap` voxels; tiles whose planes do not fit it are re-run by the
 // workgroup kernel (8 wavefronts, the largest box the CU can hold); what fits neither -- strongly oblique tiles of very fine
@@ -1827,8 +1771,10 @@ int launch_slot(svr_ctx *ctx, bool pvr, const PsfArgs &a, const TileArgs &ta_, u
     return (int)SVR_OK;
   });
 }
-int launch_scatter(svr_ctx *ctx, int level, const PsfArgs &a_, TileArgs ta, const uint32_t *tiles, uint32_t n, int mode_last) {
+int launch_scatter(svr_ctx *ctx, int level, const PsfArgs &a_, const uint32_t *tiles, uint32_t n, int mode_last) {
   PsfArgs a = a_;
+  TileArgs ta;
+  ta.tiles_x = ctx->tiles_x; ta.tiles_y = ctx->tiles_y; ta.tw = ctx->tile_w; ta.th = ctx->tile_h; ta.gauss = mode_last == MODE_GAUSS2;
   const bool pvr = ctx->pvr != 0;
   uint32_t *cnt = ctx->d_counter;                         // [0]: did not fit the wavefront's box, [1]: did not fit the workgroup's
   HIPCHK(hipMemsetAsync(cnt, 0, 2 * sizeof(uint32_t), ctx->stream));
@@ -1932,7 +1878,144 @@ void invalidate(svr_ctx *ctx, unsigned ch) {
   if (ch & (CH_VOLUME_GRID | CH_MASK_BLUR)) ctx->maskC_valid = false;
   if (ch & CH_VOLUME_VALUES) ctx->vol_clean[ctx->recon_cur == ctx->d_recon_new ? 1 : 0] = false;
   if (ch & (CH_VOLUME_GRID | CH_SCATTER_TARGETS)) ctx->cmap_from_scatter = false;
-  if (ch & CH_TILE_TIMING) ctx->fwd_tune_pending = ctx->back_tune_pending = ctx->fwd_autotune != 0;
+}
+
+// The tile shape of the unit gather (fwd_unit_kernel: fwd_mode 1, and the coefficient table's gather) from the geometry, not from a
+// timed trial: what the trials of rounds 1-3 picked, as a rule of the pixel density d = voxel area / pixel area in the slice plane.
+// With the table (the pass waits for HBM; 24-32 pixels per tile keep two workgroups per CU): P4 (d 0.72) 6 x 4 2.79 ms against 2.85 for
+// 6 x 5 and 3.07 for 4 x 4; S8 (d 0.56) 6 x 5 26.8 against 28.6 / 28.4 for 6 x 4 / 8 x 4; patches (support 12: smaller boxes) 8 x 4
+// 8.1 against 9.0-9.5 ms.  On the fly: 6 x 4 (round 2: 4.21 against 4.60 ms for 4 x 4 on P4).  Near-ties all (2-6 %): a rule that
+// repeats is worth more than the last per cent -- the table line of round 3 moved by 4 % from run to run with the trials' picks.
+double pixel_density(const svr_ctx *ctx) {              // voxel area / pixel area in the slice plane
+  double d = 1.0;
+  if (ctx->slice_dims.size() >= 3 && ctx->slice_dims[0] > 0 && ctx->slice_dims[1] > 0)
+    d = (double)ctx->vdim[0] * ctx->vdim[1] / ((double)ctx->slice_dims[0] * ctx->slice_dims[1]);
+  return d;
+}
+void tile_shape_rule(const svr_ctx *ctx, bool table, int &w, int &h) {
+  const double d = pixel_density(ctx);
+  if (ctx->pvr) { w = 8; h = 4; }
+  else if (table && d < 0.65) { w = 6; h = 5; }
+  else { w = 6; h = 4; }
+}
+// The tiled scatters' tile of w x h pixels (option tile_w / tile_h, and the 6 x 4 rule of svr_superresolution_backproject): the tile
+// lists are sized for it and built again.
+int set_scatter_tile(svr_ctx *ctx, int w, int h) {
+  ctx->tile_w = w; ctx->tile_h = h;
+  if (!ctx->np) return SVR_OK;
+  free_dev(ctx->d_tiles); free_dev(ctx->d_tiles_fb); free_dev(ctx->d_tiles_fb2);
+  ctx->tiles_x = (int)((ctx->sx + w - 1) / w);
+  ctx->tiles_y = (int)((ctx->sy + h - 1) / h);
+  const size_t nb = (size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns * sizeof(uint32_t);
+  HIPCHK(hipMalloc(&ctx->d_tiles, nb));
+  HIPCHK(hipMalloc(&ctx->d_tiles_fb, nb));
+  HIPCHK(hipMalloc(&ctx->d_tiles_fb2, nb));
+  invalidate(ctx, CH_TILE_SHAPE);
+  return SVR_OK;
+}
+
+// Which kernel family runs a PSF pass: the one place that reads pvr, pvr_mode, back_mode, fwd_mode, gauss_mode and bias_mode for it.  Device-free:
+// the options and the geometry in, a plain value out.  What only the built cell lists can tell (CellState::usable) is cells_or_fallback's.
+enum Family {
+  FAM_CELLS,    // svr_cell.inc: (cell, plane) items, no atomics -- the default
+  FAM_TILES,    // svr_tile.inc: slice tiles -- the audible fallback, and the table's gather on coarse slices
+  FAM_PIXELS,   // psf_kernel / pvr_kernel: a wavefront per pixel, kept for the parity tests
+};
+enum Pass { PASS_GAUSS1, PASS_GAUSS2, PASS_FORWARD, PASS_BACK, PASS_BIAS };   // (the Gaussian reconstruction: pass 1 gathers, pass 2 scatters)
+struct PassPath {
+  Family family;           // what the options ask for
+  int scatter_level;       // launch_scatter's level for a scatter on FAM_TILES: 4 = wave-owned planes first, 3 = the workgroup kernel, 1 = LDS atomics
+  bool may_stream_table;   // the family's kernels have a COEFF instantiation: the pass streams the table when it holds the pass's pixels
+  bool table_on_cells;     // a gather on FAM_CELLS stays there when it streams the table (else it takes FAM_TILES, silently; a pass that writes
+                           // the table is the cell gather)
+};
+PassPath pass_path(const svr_ctx *ctx, Pass pass) {
+  const bool pvr = ctx->pvr != 0;
+  const bool pvr_units = ctx->pvr_mode == 1;             // patch-based runs: the unit-based kernels of either family, else pvr_kernel
+  PassPath p = {FAM_PIXELS, 0, false, false};
+  switch (pass) {
+    case PASS_GAUSS1:      // pass 1 follows the gather: over the (cell, plane) items when that is the gather's mode (fwd_mode 2; round 4), per slice
+    case PASS_GAUSS2:      // tile otherwise; pass 2 follows the scatter.  The same bits
+      if (ctx->gauss_mode != 1 || (pvr && !pvr_units)) break;
+      p.may_stream_table = true;
+      if (pass == PASS_GAUSS1) p.family = ctx->fwd_mode == 2 ? FAM_CELLS : FAM_TILES;
+      else p.family = ctx->back_mode == 5 ? FAM_CELLS : FAM_TILES;
+      p.scatter_level = pvr ? 4 : std::min(4, std::max(1, ctx->back_mode));
+      break;
+    case PASS_FORWARD:
+      if (pvr ? !pvr_units : ctx->fwd_mode < 1) break;
+      p.may_stream_table = true;
+      p.family = ctx->fwd_mode == 2 ? FAM_CELLS : FAM_TILES;
+      // fwd_mode 2 (the default for SVR on the fly): the gather over the (cell, plane) items of the scatter without atomics
+      // (with the coefficient table: the cell gather for support 12 only -- PVR8spx 24.5 -> 20.7 ms; for support 16 its ring and its 16
+      // box values do not fit the registers and the unit gather streams the table faster: P4 2.76 against 3.04 ms)
+      // ... and there only on large cells, i.e. fine volumes: PVR4 (9 x 6) 8.1 ms on tiles against 8.5 ms on cells)
+      // Round 6: support 16 takes the cell gather too -- the table's rows land in the LDS by LDS-DMA instead of in a ring of registers (fwd_cell_kernel,
+      // COEFF == 2): P4 2.39 against 2.84 ms; option fwd_mode 1 keeps the tile kernel reachable
+      // ... where the slices' pixels are not much coarser than the voxels (the density of tile_shape_rule): S8 (d 0.56, a 174 GB table) 28.1 ms on the
+      // cells whatever their size (6 x 4 .. 12 x 6) against 26.9 ms on 6 x 5 slice tiles
+      if (pvr) {
+        int sw, sh, gw, gh;
+        cell_sizes(ctx, sw, sh, gw, gh);
+        p.table_on_cells = gw * gh >= 96 || ctx->fwd_mode_user;
+      } else {
+        p.table_on_cells = ctx->fwd_mode_user || pixel_density(ctx) >= 0.65;
+      }
+      break;
+    case PASS_BACK:
+      if (pvr ? !pvr_units : ctx->back_mode < 1) break;
+      p.family = ctx->back_mode == 5 ? FAM_CELLS : FAM_TILES;
+      p.scatter_level = pvr ? 4 : std::min(4, ctx->back_mode);
+      p.may_stream_table = pvr || ctx->back_mode >= 4;     // (back_tiled_kernel and back_slot_kernel evaluate)
+      break;
+    case PASS_BIAS:        // the NormaliseBias scatter: the SR scatter's cell kernels, or round 1's psf_kernel<MODE_BIAS>
+      if (ctx->bias_mode >= 1 && !pvr && ctx->back_mode == 5) { p.family = FAM_CELLS; p.may_stream_table = true; }
+      break;
+  }
+  return p;
+}
+// The cell lists for a pass on FAM_CELLS (gather: the gather's own when it works on another cell size) -> cs; nullptr where they cannot
+// hold the geometry (CellState::usable), with the fallback counted and, the first time, said.
+int cells_or_fallback(svr_ctx *ctx, bool gather, int kind, const char *what, CellState *&cs) {
+  cs = nullptr;
+  int r;
+  if (gather) r = cell_prepare_gather(ctx, cs);
+  else if (!(r = cell_prepare(ctx))) cs = ctx->cell;
+  if (r) return r;
+  if (cs && cs->usable) return SVR_OK;
+  cs = nullptr;
+  ctx->note_fallback(kind, what);
+  return SVR_OK;
+}
+const char *const SCATTER_LEFT_CELLS = "the scatter left the cell path (the cell lists cannot hold this geometry): back_mode 4, float atomics, last bits depend on the run";
+
+// FAM_PIXELS: a wavefront per entry of the pixel list (psf_kernel<MODE> / pvr_kernel<MODE>)
+int launch_pixels(svr_ctx *ctx, const PsfArgs &a, void (*kernel)(PsfArgs), const char *name) {
+  return pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
+    hipLaunchKernelGGL(kernel, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), 0, ctx->stream, ap);
+    KCHK(name);
+    return (int)SVR_OK;
+  });
+}
+// {V m, m} per voxel for the gathers' boxes (patch-based: V through the 8-voxel average) -> a.volm
+int pack_volm(svr_ctx *ctx, PsfArgs &a) {
+  if (!ctx->d_volm) HIPCHK(hipMalloc(&ctx->d_volm, ctx->nv * sizeof(float2)));
+  if (ctx->pvr) hipLaunchKernelGGL(k_pack_volm_pvr, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, a.vg);
+  else hipLaunchKernelGGL(k_pack_volm, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, ctx->nv);
+  KCHK(ctx->pvr ? "k_pack_volm_pvr" : "k_pack_volm");
+  a.volm = ctx->d_volm;
+  return SVR_OK;
+}
+// FAM_TILES, the gathers: fwd_unit_kernel over a list of tw x th-pixel tiles (GAUSS1: pass 1 of the Gaussian reconstruction)
+template <bool GAUSS1>
+int launch_unit_gather(svr_ctx *ctx, const PsfArgs &a, const uint32_t *tiles, uint32_t ntiles, int tiles_x, int tiles_y, int tw, int th) {
+  if (!ntiles) return SVR_OK;
+  TileArgs ta;
+  ta.tiles = tiles; ta.ntiles = ntiles; ta.tiles_x = tiles_x; ta.tiles_y = tiles_y; ta.tw = tw; ta.th = th; ta.gauss = GAUSS1 ? 1 : 0;
+  ta.cap = std::min(ctx->fwd_unit_cap, ctx->tile_cap);
+  launch_fwd_unit<GAUSS1>(ctx, a, ta, (size_t)ta.cap * 2 * sizeof(float));
+  KCHK(GAUSS1 ? "fwd_unit_kernel<GAUSS1>" : "fwd_unit_kernel");
+  return SVR_OK;
 }
 
 // reduce partial[ns*chunks][K] -> per_slice[ns][K] (+ optionally -> d_out[K])
@@ -2035,8 +2118,6 @@ int svr_create(int device, svr_ctx **out) {
   e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete ctx; return (int)e; }
   ctx->own_stream = true;
-  (void)hipEventCreate(&ctx->ev0);
-  (void)hipEventCreate(&ctx->ev1);
   if (hipMalloc(&ctx->d_counter, 64) != hipSuccess || hipMalloc(&ctx->d_out, 16 * sizeof(double)) != hipSuccess) {
     svr_destroy(ctx);
     return (int)hipErrorOutOfMemory;
@@ -2067,7 +2148,7 @@ int svr_create(int device, svr_ctx **out) {
     }
     ctx->tile_cap = dyn / (2 * (int)sizeof(float));
   }
-  // SVR_TILE_PIN="GWxGH,SWxSH,BOX": the gather's tile, the tiled scatter's tile and its LDS box fixed instead of timed, so that a
+  // SVR_TILE_PIN="GWxGH,SWxSH,BOX": the gather's tile, the tiled scatter's tile and its LDS box fixed instead of following the geometry, so that a
   // run can be repeated with the same shapes (on every rank, in every process); bench.py prints the shapes in config.tuned
   if (const char *v = getenv("SVR_CELL_ORDER")) ctx->cell_order = std::min(20, std::max(0, atoi(v)));   // (experiments: the options' defaults)
   if (const char *v = getenv("SVR_CELL_BALANCE")) ctx->cell_balance = std::min(1024, std::max(0, atoi(v)));
@@ -2112,19 +2193,17 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
     int w = !strcmp(name, "fwd_tile_w") ? value : ctx->fwd_tw, h = !strcmp(name, "fwd_tile_h") ? value : ctx->fwd_th;
     if (w < 1 || h < 1 || w * h > 32) return fail(ctx, SVR_E_ARG, "fwd tile must hold 1..32 pixels");   // FWDU_MAXPIX: the gather's pixel tables
     ctx->fwd_tw = w; ctx->fwd_th = h; invalidate(ctx, CH_TILE_SHAPE);
-    ctx->fwd_tile_user = true;                           // an explicit shape switches the tuning off
+    ctx->fwd_tile_user = true;                           // an explicit shape is left alone
     return SVR_OK;
   }
-  if (!strcmp(name, "fwd_autotune")) {
-    ctx->fwd_autotune = value ? 1 : 0;
-    invalidate(ctx, CH_TILE_TIMING);
+  if (!strcmp(name, "fwd_autotune")) {                     // (the name stays readable; 0 is all it can be)
+    if (value) return fail(ctx, SVR_E_ARG, "fwd_autotune: the timed trial launches were removed; the tile shapes follow from the geometry (0 is accepted and changes nothing)");
     return SVR_OK;
   }
   if (!strcmp(name, "pvr")) { ctx->pvr = value ? 1 : 0; if (!ctx->coeff_user) ctx->coeff_mode = value ? 0 : 1; invalidate(ctx, CH_SLICE_GEOMETRY | CH_TILE_SHAPE | CH_TABLE_OFF); return SVR_OK; }
   if (!strcmp(name, "coeff_lazy")) { ctx->coeff_lazy = value ? 1 : 0; return SVR_OK; }
   if (!strcmp(name, "coeff_invalidate")) { invalidate(ctx, CH_TABLE); return SVR_OK; }   // (what a new slice geometry does to the table: bench.py's outer iterations)
   if (!strcmp(name, "coeff_table")) {
-    if ((value ? 1 : 0) != ctx->coeff_mode) invalidate(ctx, CH_TILE_TIMING);   // other shapes win
     ctx->coeff_mode = value ? 1 : 0;
     ctx->coeff_user = true;
     if (!value) invalidate(ctx, CH_TABLE_OFF);
@@ -2148,12 +2227,9 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
     invalidate(ctx, CH_CELL_SHAPE);
     return SVR_OK;
   }
-  if (!strcmp(name, "dbg_back")) { ctx->dbg_back = value; return SVR_OK; }
-  if (!strcmp(name, "dbg_fwd_lds")) { ctx->dbg_fwd_lds = value; return SVR_OK; }
   if (!strcmp(name, "wave_groups")) { ctx->wave_groups = std::max(1, value); return SVR_OK; }
   if (!strcmp(name, "wave_cap")) { ctx->wave_cap = std::max(1024, value); ctx->wave_cap_user = true; return SVR_OK; }
   if (!strcmp(name, "reg_blind")) { ctx->reg_blind = std::max(0, value); return SVR_OK; }
-  if (!strcmp(name, "tune_tiles")) { ctx->tune_tiles = std::max(0, value); return SVR_OK; }
   if (!strcmp(name, "reg_red_threads")) {
     if (value != 0 && value != 256 && value != 1024) return fail(ctx, SVR_E_ARG, "reg_red_threads: 0, 256 or 1024");
     ctx->reg_red_threads = value;
@@ -2167,19 +2243,8 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
   if (!strcmp(name, "tile_w") || !strcmp(name, "tile_h")) {
     int w = !strcmp(name, "tile_w") ? value : ctx->tile_w, h = !strcmp(name, "tile_h") ? value : ctx->tile_h;
     if (w < 1 || h < 1 || w * h > 64) return fail(ctx, SVR_E_ARG, "tile_w * tile_h must be in 1..64");
-    ctx->tile_w = w; ctx->tile_h = h;
-    if (!ctx->in_tune) ctx->tile_user = true;            // an explicit shape switches the tuning off
-    if (ctx->np) {
-      free_dev(ctx->d_tiles); free_dev(ctx->d_tiles_fb); free_dev(ctx->d_tiles_fb2);
-      ctx->tiles_x = (int)((ctx->sx + w - 1) / w);
-      ctx->tiles_y = (int)((ctx->sy + h - 1) / h);
-      const size_t nb = (size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns * sizeof(uint32_t);
-      HIPCHK(hipMalloc(&ctx->d_tiles, nb));
-      HIPCHK(hipMalloc(&ctx->d_tiles_fb, nb));
-      HIPCHK(hipMalloc(&ctx->d_tiles_fb2, nb));
-      invalidate(ctx, CH_TILE_SHAPE);
-    }
-    return SVR_OK;
+    ctx->tile_user = true;                               // an explicit shape is left alone
+    return set_scatter_tile(ctx, w, h);
   }
   return fail(ctx, SVR_E_ARG, std::string("unknown option ") + name);
 }
@@ -2191,9 +2256,9 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value) {
   cell_sizes(ctx, csw, csh, cgw, cgh);                   // the cell sizes in effect (0 = automatic resolved)
   const bool cells_valid = ctx->cell && ctx->cell->valid && ((cgw == csw && cgh == csh) || !ctx->cell_g || ctx->cell_g->valid);   // (+ the gather's own)
   const struct { const char *n; int v; } tab[] = {
-      {"back_mode", back_mode_eff(ctx)}, {"reg_mode", ctx->reg_mode}, {"fwd_mode", ctx->fwd_mode}, {"gauss_mode", ctx->gauss_mode}, {"pvr_mode", ctx->pvr_mode},
+      {"back_mode", ctx->back_mode}, {"reg_mode", ctx->reg_mode}, {"fwd_mode", ctx->fwd_mode}, {"gauss_mode", ctx->gauss_mode}, {"pvr_mode", ctx->pvr_mode},
       {"pvr", ctx->pvr}, {"coeff_table", ctx->coeff_mode}, {"coeff_lazy", ctx->coeff_lazy}, {"coeff_valid", ctx->coeff_state != COEFF_NONE}, {"coeff_state", ctx->coeff_state}, {"tile_w", ctx->tile_w}, {"tile_h", ctx->tile_h},
-      {"fwd_tile_w", ctx->fwd_tw}, {"fwd_tile_h", ctx->fwd_th}, {"wave_cap", ctx->wave_cap}, {"cell_w", csw}, {"cell_h", csh}, {"cell_gw", cgw}, {"cell_gh", cgh}, {"cell_split", ctx->cell_split}, {"cell_order", ctx->cell_order}, {"cell_balance", ctx->cell_balance}, {"cell_combine", ctx->cell_combine}, {"fwd_autotune", ctx->fwd_autotune}, {"cell_qx", ctx->cell_qx}, {"fwd_unit_cap", ctx->fwd_unit_cap}, {"reg_batch", ctx->reg_batch}, {"reg_blind", ctx->reg_blind},
+      {"fwd_tile_w", ctx->fwd_tw}, {"fwd_tile_h", ctx->fwd_th}, {"wave_cap", ctx->wave_cap}, {"cell_w", csw}, {"cell_h", csh}, {"cell_gw", cgw}, {"cell_gh", cgh}, {"cell_split", ctx->cell_split}, {"cell_order", ctx->cell_order}, {"cell_balance", ctx->cell_balance}, {"cell_combine", ctx->cell_combine}, {"fwd_autotune", 0}, {"cell_qx", ctx->cell_qx}, {"fwd_unit_cap", ctx->fwd_unit_cap}, {"reg_batch", ctx->reg_batch}, {"reg_blind", ctx->reg_blind},
       {"bias_mode", ctx->bias_mode}, {"bias_corrections", ctx->bias_corrections}, {"bias_normalisations", ctx->bias_normalisations},
       {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells},
       {"bias_field_bx", ctx->last_bias_bx}, {"bias_tail_lds", ctx->last_tail_lds}, {"bias_tail_rows", ctx->last_tail_rows},
@@ -2233,8 +2298,6 @@ void svr_destroy(svr_ctx *ctx) {
   if (ctx->ev_open) (void)hipEventDestroy(ctx->ev_open);
   for (hipEvent_t e : ctx->ev_free) (void)hipEventDestroy(e);
   ctx->ev_free.clear();
-  if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -2460,7 +2523,7 @@ int svr_set_slice_dims(svr_ctx *ctx, const float *slice_dims, float quality_fact
   ctx->slice_dims.assign(slice_dims, slice_dims + 3 * (size_t)ctx->ns);
   ctx->quality_factor = quality_factor;   // only sizes the (unused) finite-support dim, RC.cu:772-784
   ctx->have_dims = true;
-  invalidate(ctx, CH_SLICE_GEOMETRY | CH_TILE_TIMING);   // (the pixel density: time the tile shapes again)
+  invalidate(ctx, CH_SLICE_GEOMETRY);
   return SVR_OK;
 }
 
@@ -2588,18 +2651,18 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
   HIPCHK(hipMemsetAsync(ctx->d_voxcount, 0, ctx->np * sizeof(int), ctx->stream));
   ctx->recon_cur = ctx->d_recon_volw;      // recon | volw as one allocation again (the pair a sharded run all-reduces); the old volume is not read
   HIPCHK(hipMemsetAsync(ctx->d_recon_volw, 0, 2 * ctx->nv * sizeof(float), ctx->stream));
-  const bool tiled = ctx->gauss_mode == 1 && (!ctx->pvr || ctx->pvr_mode == 1);
-  if (tiled) {
+  const PassPath p1 = pass_path(ctx, PASS_GAUSS1), p2 = pass_path(ctx, PASS_GAUSS2);
+  if (p1.may_stream_table) {
     r = coeff_lazy_pending(ctx) ? SVR_OK : ensure_coeff(ctx);   // (coeff_lazy: pass 2 writes the table below)
     if (r) return r;
   }
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_active;
   a.n = ctx->n_active;
-  if (tiled && table_holds(ctx, COEFF_FULL)) give_coeff(ctx, a);
+  if (p1.may_stream_table && table_holds(ctx, COEFF_FULL)) give_coeff(ctx, a);
   bool stored = false;
   ScopedTimer t(ctx, SVR_T_GAUSS);
-  if (a.n && tiled) {
+  if (a.n && p1.family != FAM_PIXELS) {
     // pass 1 = the unit-based walk of the gather (sume, gate, v_PSF_sums, voxel-count flag), pass 2 = the scatter of the
     // back-projection with {recon|volw} as targets and unit voxel / slice weights
     if (!ctx->d_gauss_flag) HIPCHK(hipMalloc(&ctx->d_gauss_flag, ctx->np));
@@ -2614,71 +2677,39 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
       ctx->tiles_tmp_cap = max_tiles;
     }
     uint32_t n1 = 0, n2 = 0;
-    TileArgs ta;
-    ta.tiles_x = ftx; ta.tiles_y = fty; ta.tw = gtw; ta.th = gth; ta.gauss = 1;
-    ta.cap = std::min(ctx->fwd_unit_cap, ctx->tile_cap); ta.dbg = ctx->dbg_back;
     a.flag = nullptr; a.flag_out = ctx->d_gauss_flag;
-    // pass 1 follows the gather: over the (cell, plane) items when that is the gather's mode (fwd_mode 2; round 4), per slice tile
-    // otherwise (fwd_mode 1, the coefficient table, geometries the cell lists cannot hold).  The same bits.
-    bool pass1_cells = false;
-    if (ctx->fwd_mode == 2 && !a.coeff) {
-      CellState *gcs = nullptr;
-      if ((r = cell_prepare_gather(ctx, gcs))) return r;
-      if (gcs && gcs->usable) {
-        if ((r = launch_cell_gauss1(ctx, *gcs, a))) return r;
-        pass1_cells = true;
-      } else {
-        ctx->note_fallback(2, "pass 1 of the Gaussian reconstruction left the cell path (the cell lists cannot hold this geometry): tile kernel, same bits");
-      }
-    }
-    if (!pass1_cells) {
-    HIPCHK(hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
-    if ((r = build_tile_list(ctx, nullptr, nullptr, ftx, fty, gtw, gth, ctx->d_tiles_tmp, ctx->d_counter))) return r;
-    HIPCHK(hipMemcpyAsync(&n1, ctx->d_counter, sizeof(n1), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ta.tiles = ctx->d_tiles_tmp; ta.ntiles = n1;
-    if (n1) {
-      const size_t lds = (size_t)ta.cap * 2 * sizeof(float);
-      launch_fwd_unit<true>(ctx, a, ta, lds);
-      KCHK("fwd_unit_kernel<GAUSS1>");
-    }
+    CellState *gcs = nullptr;
+    if (p1.family == FAM_CELLS && (!a.coeff || p1.table_on_cells) &&
+        (r = cells_or_fallback(ctx, true, 2, "pass 1 of the Gaussian reconstruction left the cell path (the cell lists cannot hold this geometry): tile kernel, same bits", gcs))) return r;
+    if (gcs) {
+      if ((r = launch_cell_gauss1(ctx, *gcs, a))) return r;
+    } else {
+      HIPCHK(hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
+      if ((r = build_tile_list(ctx, nullptr, nullptr, ftx, fty, gtw, gth, ctx->d_tiles_tmp, ctx->d_counter))) return r;
+      HIPCHK(hipMemcpyAsync(&n1, ctx->d_counter, sizeof(n1), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      if ((r = launch_unit_gather<true>(ctx, a, ctx->d_tiles_tmp, n1, ftx, fty, gtw, gth))) return r;
     }
     a.flag = ctx->d_gauss_flag;
     a.addon = ctx->recon(); a.cmap = ctx->volw();       // scatter targets of pass 2 (RC.cu:279-282)
-    ta.tiles_x = ctx->tiles_x; ta.tiles_y = ctx->tiles_y; ta.tw = ctx->tile_w; ta.th = ctx->tile_h; ta.dbg = 0;
-    bool cells = false;
-    if (back_mode_eff(ctx) == 5) {
-      if ((r = cell_prepare(ctx))) return r;
-      cells = ctx->cell->usable;
-      if (!cells) ctx->note_fallback(0, "the scatter left the cell path (the cell lists cannot hold this geometry): back_mode 4, float atomics, last bits depend on the run");
-    }
-    if (cells) {
+    CellState *scs = nullptr;
+    if (p2.family == FAM_CELLS && (r = cells_or_fallback(ctx, false, 0, SCATTER_LEFT_CELLS, scs))) return r;
+    if (scs) {
       // (coeff_lazy: pass 2 evaluates every unit the SR iterations will read -- it writes the table, and the SimulateSlices that follows streams it)
-      if (!a.coeff && !ctx->pvr && (r = coeff_begin_store(ctx, &stored))) return r;
+      if (!a.coeff && (r = coeff_begin_store(ctx, &stored))) return r;
       if (stored) give_coeff(ctx, a);
       r = launch_cell_scatter(ctx, a, 1, ctx->recon(), ctx->volw(), stored);
-    }
-    else {
+    } else {
       // the tiles of the pixels that passed the gate (the tiled scatters only)
       HIPCHK(hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
       if ((r = build_tile_list(ctx, nullptr, ctx->d_gauss_flag, ctx->tiles_x, ctx->tiles_y, ctx->tile_w, ctx->tile_h, ctx->d_tiles_tmp, ctx->d_counter))) return r;
       HIPCHK(hipMemcpyAsync(&n2, ctx->d_counter, sizeof(n2), hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(hipStreamSynchronize(ctx->stream));
-      r = launch_scatter(ctx, ctx->pvr ? 4 : std::min(4, std::max(1, back_mode_eff(ctx))), a, ta, ctx->d_tiles_tmp, n2, MODE_GAUSS2);
+      r = launch_scatter(ctx, p2.scatter_level, a, ctx->d_tiles_tmp, n2, MODE_GAUSS2);
     }
     if (r) return r;
-  } else if (a.n && ctx->pvr) {
-    { const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
-        hipLaunchKernelGGL(pvr_kernel<MODE_GAUSS>, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), 0, ctx->stream, ap);
-        KCHK("pvr_kernel<GAUSS>");
-        return (int)SVR_OK; });
-      if (rr) return rr; }
   } else if (a.n) {
-    { const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
-        hipLaunchKernelGGL(psf_kernel<MODE_GAUSS>, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), 0, ctx->stream, ap);
-        KCHK("psf_kernel<GAUSS>");
-        return (int)SVR_OK; });
-      if (rr) return rr; }
+    if ((r = launch_pixels(ctx, a, ctx->pvr ? pvr_kernel<MODE_GAUSS> : psf_kernel<MODE_GAUSS>, "psf_kernel / pvr_kernel<GAUSS>"))) return r;
   }
   t.stop();
   invalidate(ctx, CH_PSF_SUMS);
@@ -2711,25 +2742,6 @@ int svr_gaussian_reconstruction(svr_ctx *ctx, int *voxel_num) {
   return svr_gaussian_reconstruction_finish(ctx, voxel_num);
 }
 
-// The tile shape of the unit gather (fwd_unit_kernel: fwd_mode 1, and the coefficient table's gather) from the geometry, not from a
-// timed trial: what the trials of rounds 1-3 picked, as a rule of the pixel density d = voxel area / pixel area in the slice plane.
-// With the table (the pass waits for HBM; 24-32 pixels per tile keep two workgroups per CU): P4 (d 0.72) 6 x 4 2.79 ms against 2.85 for
-// 6 x 5 and 3.07 for 4 x 4; S8 (d 0.56) 6 x 5 26.8 against 28.6 / 28.4 for 6 x 4 / 8 x 4; patches (support 12: smaller boxes) 8 x 4
-// 8.1 against 9.0-9.5 ms.  On the fly: 6 x 4 (round 2: 4.21 against 4.60 ms for 4 x 4 on P4).  Near-ties all (2-6 %): a rule that
-// repeats is worth more than the last per cent -- the table line of round 3 moved by 4 % from run to run with the trials' picks.
-double pixel_density(const svr_ctx *ctx) {              // voxel area / pixel area in the slice plane
-  double d = 1.0;
-  if (ctx->slice_dims.size() >= 3 && ctx->slice_dims[0] > 0 && ctx->slice_dims[1] > 0)
-    d = (double)ctx->vdim[0] * ctx->vdim[1] / ((double)ctx->slice_dims[0] * ctx->slice_dims[1]);
-  return d;
-}
-void tile_shape_rule(const svr_ctx *ctx, bool table, int &w, int &h) {
-  const double d = pixel_density(ctx);
-  if (ctx->pvr) { w = 8; h = 4; }
-  else if (table && d < 0.65) { w = 6; h = 5; }
-  else { w = 6; h = 4; }
-}
-
 // ---- forward projection ----------------------------------------------------------------
 int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   SVR_ENTER(ctx);
@@ -2738,6 +2750,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   if (r) return r;
   r = ensure_psf_list(ctx);
   if (r) return r;
+  const PassPath p = pass_path(ctx, PASS_FORWARD);
   // Round 6 (coeff_lazy): with the table wanted and not there, THIS pass writes it -- it evaluates every tap of every PSF pixel anyway
   // (fwd_cell_kernel<.., 3>); needs the cell gather.  Otherwise k_coeff_build, as before.
   bool store = false;
@@ -2753,70 +2766,12 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
-  if (store || ((ctx->pvr ? ctx->pvr_mode == 1 : ctx->fwd_mode >= 1) && table_holds(ctx, COEFF_PSF))) give_coeff(ctx, a);
-  if (!ctx->pvr && ctx->fwd_mode >= 1 && a.n) {
-    if (!ctx->d_volm) HIPCHK(hipMalloc(&ctx->d_volm, ctx->nv * sizeof(float2)));
-    hipLaunchKernelGGL(k_pack_volm, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, ctx->nv);
-    KCHK("k_pack_volm");
-    a.volm = ctx->d_volm;
-  } else if (ctx->pvr && ctx->pvr_mode == 1 && a.n) {
-    if (!ctx->d_volm) HIPCHK(hipMalloc(&ctx->d_volm, ctx->nv * sizeof(float2)));
-    hipLaunchKernelGGL(k_pack_volm_pvr, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, a.vg);
-    KCHK("k_pack_volm_pvr");
-    a.volm = ctx->d_volm;
-  }
-  // fwd_mode 2 (the default for SVR on the fly): the gather over the (cell, plane) items of the scatter without atomics
-  bool cells = false;
-  // (with the coefficient table: the cell gather for support 12 only -- PVR8spx 24.5 -> 20.7 ms; for support 16 its ring and its 16
-  // box values do not fit the registers and the unit gather streams the table faster: P4 2.76 against 3.04 ms)
-  // ... and there only on large cells, i.e. fine volumes: PVR4 (9 x 6) 8.1 ms on tiles against 8.5 ms on cells)
-  // Round 6: support 16 takes the cell gather too -- the table's rows land in the LDS by LDS-DMA instead of in a ring of registers (fwd_cell_kernel,
-  // COEFF == 2): P4 2.39 against 2.84 ms; option fwd_mode 1 keeps the tile kernel reachable
-  // ... where the slices' pixels are not much coarser than the voxels (the density of tile_shape_rule): S8 (d 0.56, a 174 GB table) 28.1 ms on the
-  // cells whatever their size (6 x 4 .. 12 x 6) against 26.9 ms on 6 x 5 slice tiles
-  bool table_on_cells = a.coeff && !ctx->pvr && (store || ctx->fwd_mode_user || pixel_density(ctx) >= 0.65);
-  if (a.coeff && ctx->pvr) {
-    int sw, sh, gw, gh;
-    cell_sizes(ctx, sw, sh, gw, gh);
-    table_on_cells = gw * gh >= 96 || ctx->fwd_mode_user;
-  }
-  if (ctx->fwd_mode == 2 && (!ctx->pvr || ctx->pvr_mode == 1) && (!a.coeff || table_on_cells) && a.n) {
-    if ((r = cell_prepare_gather(ctx, gcs))) return r;
-    cells = gcs->usable;
-    if (!cells) ctx->note_fallback(1, "the gather left the cell path (the cell lists cannot hold this geometry): tile kernel, same bits");
-  }
-  auto launch_forward = [&]() -> int {
-    const bool tiled_ = ctx->pvr ? ctx->pvr_mode == 1 : ctx->fwd_mode >= 1;
-    if (cells) {
-      const int rr = launch_cell_gather(ctx, *gcs, a, store);
-      if (rr) return rr;
-      if (store) ctx->coeff_state = COEFF_PSF;             // (the PSF pixels' live units: what the SR iterations' passes read)
-    } else if (a.n && tiled_) {
-      { const int rr = ensure_tiles_fwd(ctx); if (rr) return rr; }
-      TileArgs ta;
-      ta.tiles = ctx->d_tiles_fwd; ta.ntiles = ctx->n_tiles_fwd; ta.tiles_x = ctx->fwd_tiles_x; ta.tiles_y = ctx->fwd_tiles_y;
-      ta.cap = std::min(ctx->fwd_unit_cap, ctx->tile_cap); ta.dbg = ctx->dbg_back; ta.tw = ctx->fwd_tw; ta.th = ctx->fwd_th;
-      ta.gauss = 0;
-      const size_t lds = (size_t)ta.cap * 2 * sizeof(float);
-      launch_fwd_unit<false>(ctx, a, ta, lds);
-      KCHK("fwd_unit_kernel");
-    } else if (a.n && ctx->pvr) {
-      { const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
-          hipLaunchKernelGGL(pvr_kernel<MODE_FWD>, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), 0, ctx->stream, ap);
-          KCHK("pvr_kernel<FWD>");
-          return (int)SVR_OK; });
-        if (rr) return rr; }
-    } else if (a.n) {
-      { const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
-          hipLaunchKernelGGL(psf_kernel<MODE_FWD>, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), (size_t)ctx->dbg_fwd_lds, ctx->stream, ap);
-          KCHK("psf_kernel<FWD>");
-          return (int)SVR_OK; });
-        if (rr) return rr; }
-    }
-    return SVR_OK;
-  };
-  const bool tiled = a.n && (ctx->pvr ? ctx->pvr_mode == 1 : ctx->fwd_mode >= 1);
-  if (tiled && !cells && !ctx->fwd_autotune && !ctx->fwd_tile_user) {
+  if (store || (p.may_stream_table && table_holds(ctx, COEFF_PSF))) give_coeff(ctx, a);
+  if (a.n && p.family != FAM_PIXELS && (r = pack_volm(ctx, a))) return r;
+  gcs = nullptr;
+  if (a.n && p.family == FAM_CELLS && (!a.coeff || store || p.table_on_cells) &&
+      (r = cells_or_fallback(ctx, true, 1, "the gather left the cell path (the cell lists cannot hold this geometry): tile kernel, same bits", gcs))) return r;
+  if (a.n && p.family != FAM_PIXELS && !gcs && !ctx->fwd_tile_user) {
     int w, h;
     tile_shape_rule(ctx, a.coeff != nullptr, w, h);
     if (w != ctx->fwd_tw || h != ctx->fwd_th) {
@@ -2826,51 +2781,19 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
       a.list = ctx->d_psf_list; a.n = ctx->n_psf;
     }
   }
-  if (tiled && !cells && ctx->fwd_tune_pending && !ctx->fwd_tile_user) {
-    ctx->fwd_tune_pending = false;
-    static const int cand[6][2] = {{4, 4}, {6, 4}, {6, 5}, {8, 4}, {4, 2}, {2, 2}};   // the first is the default; smaller boxes for finer volumes (at most FWDU_MAXPIX = 32 pixels)
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    float best = 3.0e38f;
-    int pick = 0;
-    for (int c = 0; c < 6; ++c) {
-      ctx->fwd_tw = cand[c][0]; ctx->fwd_th = cand[c][1]; invalidate(ctx, CH_TILE_SHAPE);
-      r = ensure_psf_list(ctx);
-      if (r) return r;
-      a.list = ctx->d_psf_list; a.n = ctx->n_psf;
-      TileSample sample;
-      if (!r) r = ensure_tiles_fwd(ctx);
-      if (r) return r;
-      r = sample.begin(ctx, ctx->d_tiles_fwd, ctx->n_tiles_fwd);
-      float ms = 0.0f;
-      for (int rep = 0; rep < 2 && !r; ++rep) {          // the second run is the one that counts (a new tile list costs its first launch)
-        hipError_t he = hipEventRecord(e0, ctx->stream);
-        r = launch_forward();
-        if (he == hipSuccess) he = hipEventRecord(e1, ctx->stream);
-        if (he == hipSuccess) he = hipEventSynchronize(e1);
-        if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-        if (!r && he != hipSuccess) r = fail(ctx, (int)he, std::string("tile tuning: ") + hipGetErrorString(he));
-      }
-      sample.end();                                      // before anything can rebuild or free the list
-      if (r) return r;
-      ms *= sample.scale;
-      if (getenv("SVR_TUNE_DEBUG")) fprintf(stderr, "[tune] gather %dx%d: %.3f ms (whole launch; timed 1/%.1f of the tiles)\n", cand[c][0], cand[c][1], ms, sample.scale);
-      if (ms < best) { best = ms; pick = c; }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    ctx->fwd_tw = cand[pick][0]; ctx->fwd_th = cand[pick][1]; invalidate(ctx, CH_TILE_SHAPE);
-    r = ensure_psf_list(ctx);
-    if (r) return r;
-    a.list = ctx->d_psf_list; a.n = ctx->n_psf;
-  }
   ScopedTimer t(ctx, SVR_T_FORWARD);
   if (store) t.also(SVR_T_FORWARD_STORE); else if (a.coeff) t.also(SVR_T_FORWARD_TABLE);
-  r = launch_forward();
-  if (r) return r;
+  if (gcs) {
+    if ((r = launch_cell_gather(ctx, *gcs, a, store))) return r;
+    if (store) ctx->coeff_state = COEFF_PSF;               // (the PSF pixels' live units: what the SR iterations' passes read)
+  } else if (a.n && p.family != FAM_PIXELS) {
+    if ((r = ensure_tiles_fwd(ctx))) return r;
+    if ((r = launch_unit_gather<false>(ctx, a, ctx->d_tiles_fwd, ctx->n_tiles_fwd, ctx->fwd_tiles_x, ctx->fwd_tiles_y, ctx->fwd_tw, ctx->fwd_th))) return r;
+  } else if (a.n) {
+    if ((r = launch_pixels(ctx, a, ctx->pvr ? pvr_kernel<MODE_FWD> : psf_kernel<MODE_FWD>, "psf_kernel / pvr_kernel<FWD>"))) return r;
+  }
   t.stop();
-  if (!cells) {                                            // (the cell gather's finish raises the slices' flags itself)
+  if (!gcs) {                                              // (the cell gather's finish raises the slices' flags itself)
     hipLaunchKernelGGL(k_slice_inside, dim3(ctx->ns), dim3(256), 0, ctx->stream, ctx->d_siminside,
                        (int)(ctx->sx * ctx->sy), ctx->d_slice_inside);
     KCHK("k_slice_inside");
@@ -3163,150 +3086,42 @@ int svr_superresolution_backproject(svr_ctx *ctx, const float *slice_weight) {
     r = svr_update_slice_weights(ctx, slice_weight);   // RC.cu:2123
     if (r) return r;
   }
-  if (!ctx->fwd_autotune && !ctx->tile_user && !ctx->in_tune && back_mode_eff(ctx) != 5 && (ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) >= 3) &&
-      (ctx->tile_w != 6 || ctx->tile_h != 4)) {
+  const PassPath p = pass_path(ctx, PASS_BACK);
+  if (p.family == FAM_TILES && p.scatter_level >= 3 && !ctx->tile_user && (ctx->tile_w != 6 || ctx->tile_h != 4)) {
     // the tiled scatters (back_mode 3 / 4: fallbacks of the cell scatter, and what a caller names) without trials: 6 x 4 pixels with
     // the 2096-voxel box -- the trials' pick or within 2 % of it on P4 (4.97 ms against 4.96-5.08) and S8 (6 x 5 / 2096: 50.5 against 52.2)
-    ctx->in_tune = true;
-    r = svr_set_option(ctx, "tile_w", 6);
-    if (!r) r = svr_set_option(ctx, "tile_h", 4);
-    ctx->tile_user = false;
-    ctx->in_tune = false;
-    if (r) return r;
-  }
-  if (ctx->back_tune_pending && !ctx->tile_user && !ctx->in_tune && back_mode_eff(ctx) != 5 && (ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) >= 3)) {   // (mode 5: cells, no tile shape to time)
-    ctx->back_tune_pending = false;
-    ctx->in_tune = true;
-    // with the coefficient table the pass waits for memory, not for the ALUs: larger tiles (fewer flushed voxels per
-    // pixel) are tried first, with the largest box, before the box sizes are timed for the shape that won
-    static const int cand_eval[6][2] = {{6, 5}, {6, 4}, {5, 4}, {4, 4}, {4, 2}, {2, 2}};   // the first four always, then smaller ones while they win
-    static const int cand_tab[5][2] = {{8, 4}, {6, 4}, {4, 4}, {4, 2}, {2, 2}};
-    const bool tab = ctx->coeff_mode && (ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) == 4);
-    const int (*cand)[2] = tab ? cand_tab : cand_eval;
-    const int ncand = tab ? 5 : 6;
-    const int cap0 = ctx->wave_cap;
-    const auto timing = ctx->timers;
-    ctx->timers = false;                                 // the trial runs stay out of the kernel timers
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    // one trial: the whole-launch time of the current shape with box `cap`
-    bool warm = false;
-    auto trial = [&](int cap, TileSample &sample, float &ms) -> int {
-      ctx->wave_cap = cap;
-      int rr = SVR_OK;
-      ms = 0.0f;
-      for (int rep = warm ? 1 : 0; rep < 2 && !rr; ++rep) {   // one timed run per box, after one warm-up run per shape (a new tile list
-        warm = true;                                          // costs its first launch 0.1 ms on P4, enough to turn a near-tie)
-        hipError_t he = hipEventRecord(e0, ctx->stream);
-        rr = svr_superresolution_backproject(ctx, nullptr);
-        if (he == hipSuccess) he = hipEventRecord(e1, ctx->stream);
-        if (he == hipSuccess) he = hipEventSynchronize(e1);
-        if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-        if (!rr && he != hipSuccess) rr = fail(ctx, (int)he, std::string("tile tuning: ") + hipGetErrorString(he));
-      }
-      ms *= sample.scale;
-      return rr;
-    };
-    // the wave-owned scatter's LDS request decides how many wavefronts a CU holds; the smallest box that still takes
-    // (nearly) every tile wins -- tiles that do not fit are re-run by the workgroup kernel, so any value is correct.
-    // LDS is handed out in 1280-byte granules (measured: the time steps between 1764 and 1850 box voxels, not where
-    // 160 KiB / request changes), so a CU holds floor(128 / granules) wavefronts: the candidates are the largest boxes
-    // (with the kernel's 1152 static bytes) that still give 8, 9, 10, 11 and 12 of them.  A larger tile flushes fewer
-    // voxels per pixel but needs the larger box, so shape and box are timed together: per shape the boxes from the
-    // largest down while they get faster (6x4 with 2096 beats 6x5, which wins at 2416 and then cannot shrink).
-    static const int caps[5] = {2416, 2096, 1776, 1616, 1456};
-    const bool wave = (ctx->pvr || back_mode_eff(ctx) == 4) && !ctx->wave_cap_user;
-    float best = 3.0e38f;
-    int pick = 0, pick_cap = wave ? caps[0] : cap0;
-    for (int c = 0; c < ncand && !r; ++c) {
-      r = svr_set_option(ctx, "tile_w", cand[c][0]);
-      if (!r) r = svr_set_option(ctx, "tile_h", cand[c][1]);
-      if (!r) r = ensure_psf_list(ctx);                  // the list of this shape, so that the trials below find it valid
-      TileSample sample;
-      if (!r) r = ensure_tiles_back(ctx);
-      if (!r) r = sample.begin(ctx, ctx->d_tiles, ctx->n_tiles);
-      float shape_best = 3.0e38f;
-      warm = false;
-      for (int k = 0; k < (wave ? 5 : 1) && !r; ++k) {
-        float ms;
-        r = trial(wave ? caps[k] : cap0, sample, ms);
-        if (r) break;
-        if (getenv("SVR_TUNE_DEBUG"))
-          fprintf(stderr, "[tune] scatter %dx%d box %d: %.3f ms (whole launch; timed 1/%.1f of the tiles)\n", cand[c][0], cand[c][1], ctx->wave_cap, ms, sample.scale);
-        if (ms < best) { best = ms; pick = c; pick_cap = ctx->wave_cap; }
-        if (ms < shape_best) shape_best = ms;
-        else break;                                      // a smaller box stopped paying for this shape
-        if (ms > 1.3f * best) break;                     // ... or the shape is out of reach
-      }
-      sample.end();
-      if (r) break;
-      if (pick != c && c >= (tab ? 2 : 3)) break;        // the small shapes only while they win
-    }
-    ctx->wave_cap = pick_cap;
-    if (!r) r = svr_set_option(ctx, "tile_w", cand[pick][0]);
-    if (!r) r = svr_set_option(ctx, "tile_h", cand[pick][1]);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    ctx->timers = timing;
-    ctx->in_tune = false;
-    if (r) return r;
+    if ((r = set_scatter_tile(ctx, 6, 4))) return r;
   }
   r = ensure_psf_list(ctx);
   if (r) return r;
   // (coeff_lazy: a scatter that finds no table evaluates -- and, on the cell path, writes it: whichever PSF pass comes first after a new geometry does)
   r = coeff_lazy_pending(ctx) ? SVR_OK : ensure_coeff(ctx);
   if (r) return r;
-  bool store = false;
-  // RC.cu:2202-2203 -- not needed where the cell scatter runs: its combine writes EVERY voxel of addon | cmap (0 outside the mask); decided below
-  bool need_clear = true;
   ctx->prep_pending = false;
   ctx->cmap_from_scatter = true;
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
-  if ((ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) >= 4) && table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
-  const bool tiled = ctx->pvr ? ctx->pvr_mode == 1 : back_mode_eff(ctx) >= 1;
-  if (!a.coeff && a.n && tiled && back_mode_eff(ctx) == 5 && !ctx->pvr) {
-    if ((r = cell_prepare(ctx))) return r;
-    if (ctx->cell->usable) {
-      if ((r = coeff_begin_store(ctx, &store))) return r;
-      if (store) give_coeff(ctx, a);
-    }
+  if (p.may_stream_table && table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
+  CellState *cs = nullptr;
+  if (a.n && p.family == FAM_CELLS && (r = cells_or_fallback(ctx, false, 0, SCATTER_LEFT_CELLS, cs))) return r;
+  bool store = false;
+  if (cs && !a.coeff) {
+    if ((r = coeff_begin_store(ctx, &store))) return r;
+    if (store) give_coeff(ctx, a);
   }
   ScopedTimer t(ctx, SVR_T_BACKPROJECT);
   if (store) t.also(SVR_T_BACKPROJECT_STORE); else if (a.coeff) t.also(SVR_T_BACKPROJECT_TABLE);
-  if (!(a.n && tiled)) { need_clear = false; HIPCHK(hipMemsetAsync(ctx->d_addon_cmap, 0, 2 * ctx->nv * sizeof(float), ctx->stream)); }
-  if (a.n && tiled) {
-    TileArgs ta;
-    ta.tiles_x = ctx->tiles_x; ta.tiles_y = ctx->tiles_y; ta.dbg = ctx->dbg_back;
-    ta.tw = ctx->tile_w; ta.th = ctx->tile_h; ta.gauss = 0;
-    bool cells = false;
-    if (back_mode_eff(ctx) == 5) {
-      if ((r = cell_prepare(ctx))) return r;
-      cells = ctx->cell->usable;
-      if (!cells) ctx->note_fallback(0, "the scatter left the cell path (the cell lists cannot hold this geometry): back_mode 4, float atomics, last bits depend on the run");
-    }
-    need_clear = !cells;
-    if (need_clear) { need_clear = false; HIPCHK(hipMemsetAsync(ctx->d_addon_cmap, 0, 2 * ctx->nv * sizeof(float), ctx->stream)); }
-    if (cells) {
-      r = launch_cell_scatter(ctx, a, 0, ctx->addon(), ctx->cmap(), store);
-      if (!r && store) ctx->coeff_state = COEFF_PSF;       // (the PSF pixels' live units: what the SR iterations' passes read)
-    }
-    else if (!(r = ensure_tiles_back(ctx))) r = launch_scatter(ctx, ctx->pvr ? 4 : std::min(4, back_mode_eff(ctx)), a, ta, ctx->d_tiles, ctx->n_tiles, MODE_BACK);
-    if (r) return r;
-  } else if (a.n && ctx->pvr) {
-    { const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
-        hipLaunchKernelGGL(pvr_kernel<MODE_BACK>, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), 0, ctx->stream, ap);
-        KCHK("pvr_kernel<BACK>");
-        return (int)SVR_OK; });
-      if (rr) return rr; }
+  // RC.cu:2202-2203 -- not needed where the cell scatter runs: its combine writes EVERY voxel of addon | cmap (0 outside the mask)
+  if (!cs) HIPCHK(hipMemsetAsync(ctx->d_addon_cmap, 0, 2 * ctx->nv * sizeof(float), ctx->stream));
+  if (cs) {
+    if ((r = launch_cell_scatter(ctx, a, 0, ctx->addon(), ctx->cmap(), store))) return r;
+    if (store) ctx->coeff_state = COEFF_PSF;               // (the PSF pixels' live units: what the SR iterations' passes read)
+  } else if (a.n && p.family != FAM_PIXELS) {
+    if ((r = ensure_tiles_back(ctx))) return r;
+    if ((r = launch_scatter(ctx, p.scatter_level, a, ctx->d_tiles, ctx->n_tiles, MODE_BACK))) return r;
   } else if (a.n) {
-    { const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
-        hipLaunchKernelGGL(psf_kernel<MODE_BACK>, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), 0, ctx->stream, ap);
-        KCHK("psf_kernel<BACK>");
-        return (int)SVR_OK; });
-      if (rr) return rr; }
+    if ((r = launch_pixels(ctx, a, ctx->pvr ? pvr_kernel<MODE_BACK> : psf_kernel<MODE_BACK>, "psf_kernel / pvr_kernel<BACK>"))) return r;
   }
   t.stop();
   if (!ctx->sr_no_wait) HIPCHK(hipStreamSynchronize(ctx->stream));   // (svr_superresolution: the update follows on the same stream)
@@ -3744,29 +3559,22 @@ int svr_normalise_bias_local(svr_ctx *ctx) {
   // factors f1 = 1 / sume, f0 = f1 (bias - log scale) over the PSF pixels, back_cell_kernel (streaming the table when it is valid:
   // NormaliseBias follows SuperresolutionGPU on the same geometry), the combine writes bias_vol and this call's weights, which are
   // then added to the never-cleared dev_volume_weights_.  A sharded rank scatters its own slices through its own cell lists.
-  if (ctx->bias_mode >= 1 && a.n && !ctx->pvr && back_mode_eff(ctx) == 5) {
-    if ((r = cell_prepare(ctx))) return r;
-    if (ctx->cell->usable) {
-      if (table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
-      if ((r = launch_cell_scatter(ctx, a, 2, ctx->d_bias_vol, ctx->d_mbuf))) return r;
-      hipLaunchKernelGGL(k_add_to, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->d_volume_weights, ctx->d_mbuf, ctx->nv);
-      KCHK("k_add_to");
-      ++ctx->bias_scatters_on_cells;
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      return SVR_OK;
-    }
-    ctx->note_fallback(0, "the NormaliseBias scatter left the cell path (the cell lists cannot hold this geometry): float atomics, last bits depend on the run");
+  CellState *cs = nullptr;
+  if (a.n && pass_path(ctx, PASS_BIAS).family == FAM_CELLS &&
+      (r = cells_or_fallback(ctx, false, 0, "the NormaliseBias scatter left the cell path (the cell lists cannot hold this geometry): float atomics, last bits depend on the run", cs))) return r;
+  if (cs) {
+    if (table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
+    if ((r = launch_cell_scatter(ctx, a, 2, ctx->d_bias_vol, ctx->d_mbuf))) return r;
+    hipLaunchKernelGGL(k_add_to, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->d_volume_weights, ctx->d_mbuf, ctx->nv);
+    KCHK("k_add_to");
+    ++ctx->bias_scatters_on_cells;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SVR_OK;
   }
   HIPCHK(hipMemsetAsync(ctx->d_bias_vol, 0, ctx->nv * sizeof(float), ctx->stream));   // RC.cu:2621
   a.recon = ctx->d_bias_vol;            // scattered value: psf/sume * (bias - log scale)
   a.volw = ctx->d_volume_weights;       // dev_volume_weights_: accumulates, never cleared (RC.cu:2633)
-  if (a.n) {
-    { const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t) {
-        hipLaunchKernelGGL(psf_kernel<MODE_BIAS>, dim3(nblk(ap.n, WAVES_PER_BLOCK)), dim3(WAVES_PER_BLOCK * 64), 0, ctx->stream, ap);
-        KCHK("psf_kernel<BIAS>");
-        return (int)SVR_OK; });
-      if (rr) return rr; }
-  }
+  if (a.n && (r = launch_pixels(ctx, a, psf_kernel<MODE_BIAS>, "psf_kernel<BIAS>"))) return r;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }

@@ -120,15 +120,8 @@ __global__ __launch_bounds__(TILE_WAVES * 64) void back_tiled_kernel(PsfArgs a, 
         for (int x = 0; x < 16; ++x) {
           const uint32_t ax = sat0(P.cxi + x - PSF_CENTRE);
           if (rowin && ax < (uint32_t)vg.vx && !(out[x] < 0.0f)) {
-            if (ta.dbg == 1) {
-              t_addon[rbase + (int)ax] += out[x] * f0;
-              t_cmap[rbase + (int)ax] += out[x] * f1;
-            } else if (ta.dbg == 2) {
-              if (out[x] * f0 == 123.456f) t_addon[0] = 1.0f;
-            } else {
-              atomicAdd(t_addon + rbase + (int)ax, out[x] * f0);
-              atomicAdd(t_cmap + rbase + (int)ax, out[x] * f1);
-            }
+            atomicAdd(t_addon + rbase + (int)ax, out[x] * f0);
+            atomicAdd(t_cmap + rbase + (int)ax, out[x] * f1);
           }
         }
       } else {
@@ -147,7 +140,7 @@ __global__ __launch_bounds__(TILE_WAVES * 64) void back_tiled_kernel(PsfArgs a, 
       }
     }
   }
-  if (!in_lds || ta.dbg == 3) return;
+  if (!in_lds) return;
   __syncthreads();
   // flush: one pair of device-scope atomics per touched, in-mask voxel of the box
   BoxWalk bw;
@@ -270,7 +263,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(SVR_
   const int PL = (hix - lox + 1) | 1;                   // pitch of a plane that takes whole rows (odd: 16 y rows -> distinct banks)
   const int PD = (sh_hi[0] - sh_lo[0] + 1) | 1;         // pitch of a plane that only takes first taps
   const RowConst RC = load_row_const(S);
-  if (!PVR && ta.dbg != 4) {
+  if (!PVR) {
     for (int i = threadIdx.x; i < npix * NS; i += T) {  // which (pixel, z) units are dead
       const int k = i / NS, z = i % NS;
       const PixelRec R = sh_px[k];
@@ -417,7 +410,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(SVR_
     }
   }
   __syncthreads();
-  if (ta.dbg == 3) return;                              // timing experiments: no flush
   // flush: one pair of device-scope atomics per touched, in-mask voxel of the box; the float->uint saturation of the
   // reference (negative -> 0, RC.cu:508) is applied here, which sums exactly the taps that alias
   RowWalk wl, wd;
@@ -557,7 +549,7 @@ void back_wave_kernel(PsfArgs a, TileArgs ta, int groups, uint32_t *fallback_til
   const RowConst RC = load_row_const(S);
   // dead (pixel, z) units: lane k < npix ends up with the NS bits of its pixel
   uint32_t deadbits = 0u;
-  if (!PVR && ta.dbg != 4) {
+  if (!PVR) {
     static_assert(PVR || NS == 16, "four pixels of 16 units per pass of the dead-unit test");
     for (int m = 0; m * 4 < npix; ++m) {
       const int k = m * 4 + (lane >> 4), z = lane & 15;
@@ -611,10 +603,10 @@ void back_wave_kernel(PsfArgs a, TileArgs ta, int groups, uint32_t *fallback_til
       if (isl) sh_list[q][__popcll(bl & below)] = (unsigned char)lane;
       if (isd) sh_list[q][WAVE_MAXPIX - 1 - __popcll(bdd & below)] = (unsigned char)lane;
     }
-    for (int i = lane; i < 4 * PP; i += 64) box[i] = ta.dbg == 5 ? (f2){1.0f, 1.0f} : (f2){0.0f, 0.0f};
+    for (int i = lane; i < 4 * PP; i += 64) box[i] = (f2){0.0f, 0.0f};
     __syncthreads();
 
-    if (p >= 0 && ta.dbg < 5) {                         // (timing experiments 5 / 6: flush of a full / an empty box only)
+    if (p >= 0) {
       const int P = loz + p;                            // <= hiz: plane in bounds
       f2 *pb = box + slot * PP - lox;
       // One live unit: the row's accumulators are fetched before its taps are there (their LDS latency hides behind the
@@ -707,7 +699,7 @@ void back_wave_kernel(PsfArgs a, TileArgs ta, int groups, uint32_t *fallback_til
       }
     }
     __syncthreads();
-    if (ta.dbg != 3 && ta.dbg != 7) {
+    {
       // flush: one pair of device-scope atomics per touched, in-mask voxel; the float->uint saturation of the reference
       // (negative -> 0, RC.cu:508) is applied here, which sums exactly the taps that alias
       // the lane's elements i = lane + 64 u of a plane sit at the same in-plane voxel offset on all four planes: work
@@ -715,6 +707,7 @@ void back_wave_kernel(PsfArgs a, TileArgs ta, int groups, uint32_t *fallback_til
       constexpr int FLUSH_U = COEFF ? 10 : 8;           // plane voxels per lane of the unrolled flush (table mode: 8 x 4 / 8 x 8 tiles, planes of up to 640)
       RowWalk w0;
       w0.init(lane, 64, PL);
+      asm volatile("" : "+v"(w0.x));                      // the offsets are worked out per pass: hoisted out of the j0 loop they stay live through the evaluation (up to 23 VGPRs more, spills in the patch-based table instantiation)
       if (PP <= 64 * FLUSH_U) {
         int eoff[FLUSH_U];
         {
@@ -937,7 +930,7 @@ __global__ __launch_bounds__(FWDU_WAVES * 64) void fwd_unit_kernel(PsfArgs a, Ti
       const int cu = swap ? R.cy : R.cz;
       const bool inb = cu + u - NC < (swap ? vg.vy : vg.vz);      // negatives alias to 0: "in bounds"
       if (inb) {
-        const bool dead = !PVR && ta.dbg != 4 && unit_is_dead(RC, R.bx, R.by, R.bz, F, (float)(u - NC));
+        const bool dead = !PVR && unit_is_dead(RC, R.bx, R.by, R.bz, F, (float)(u - NC));
         if (dead) {
           atomicOr(&sh_dead[k], 1u << u);
           sh_units[FWDU_MAXPIX * US - 1 - atomicAdd(&sh_ndead, 1)] = (unsigned short)(k << 4 | u);

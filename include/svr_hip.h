@@ -61,17 +61,16 @@ int svr_set_flags(svr_ctx *ctx, int disable_bias_correction, int debug_gpu);
  *   pixels; 0 = (cell, plane) order.  "cell_balance" (default 0 = never): an item heavier than the launch's work /
  *   (1024 x value) is cut into parts, each a workgroup of its own; "cell_split": at least that many parts per item.
  * "tile_w"/"tile_h", "wave_cap", "fwd_tile_w"/"fwd_tile_h", "fwd_unit_cap": tile shapes and LDS box sizes of the tile kernels.
- * "fwd_autotune" (default 0 since round 4: the shapes follow from the geometry, every run and every rank picks the same):
- *   1 = the first forward projection / back-projection after new slice geometry times the
- *   candidate shapes and box sizes on the data and keeps the fastest; an explicit shape switches that off.
- *   Long tile lists are timed on runs of consecutive tiles (one run out of every stride, about 131072 tiles per trial;
- *   "tune_tiles" sets another number); environment: SVR_TUNE_TILES (tiles per trial, 0 = always the whole list), SVR_TUNE_RUN,
- *   SVR_TUNE_DEBUG=1 (the candidates' times on stderr).
+ *   The shapes follow from the geometry (the unit gather's from the pixel density, 6 x 4 pixels with a 2096-voxel box for the
+ *   tiled scatters): every run and every rank picks the same.  A shape or box named here, or by SVR_TILE_PIN, is left alone.
+ * "fwd_autotune": reads 0.  The timed trial launches it switched on in rounds 1-3 were removed; setting 0 is accepted and
+ *   changes nothing, any other value is SVR_E_ARG.
+ * environment: SVR_TUNE_DEBUG=1 prints the stages of the cell lists' construction on stderr.
  * "pvr": 1 selects the patch-to-volume constants and kernels.
  * Other environment variables: SVR_COEFF_MAX_GB (ceiling of the coefficient table), SVR_FWD_PIECE (test hook: tiles per
  *   dispatch of the gather, at most 2^22). */
 int svr_set_option(svr_ctx *ctx, const char *name, int value);
-/* the current value of an option: what the tile-shape / box-size timing chose, or whether "coeff_table" stayed on (it
+/* the current value of an option: the tile shapes / box size in effect, or whether "coeff_table" stayed on (it
  * switches itself off when the table -- 16 KiB per PSF pixel -- does not fit the free device memory) */
 int svr_get_option(svr_ctx *ctx, const char *name, int *value);
 /* "pvr" = 1 switches the PSF kernels to the patch-to-volume constants of
