@@ -21,8 +21,11 @@
 // on (main.cc:210), so this is a deviation; the GPU registration stays CC-only and refuses it.  --enableBiasCorrection (not a reference option either: the reference hard-wires its bias correction off) runs
 // BiasGPU / NormaliseBiasGPU in every SR iteration with --sigma, --global_bias_correction and --low_intensity_cutoff as the
 // reference's main() would pass them.  --packages runs PackageToVolume with the schedule of main.cc:832-864; --tfolder reads transformation<i>.dof per
-// slice and --debug writes them next to the output.  Not built, refused loudly: patch/superpixel
-// modes, the CPU reconstruction path.
+// slice and --debug writes them next to the output.  --useAutoTemplate picks the template stack by the reference's matrix rank
+// method (main.cc:565-591, stackMotionEstimator.cpp:67-164; there only in builds with CULA): every stack, cropped to the
+// mask, gets the motion score of its first nz / 3 slices (svr_stack_motion, csrc/svr_motion.inc) and the smallest score replaces
+// the stack found from `-t id`; --autoTemplateCentral (a deviation) scores the middle third instead, which is what the
+// reference's comment describes.  Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
 #include <functional>
 #include <thread>
 
@@ -42,6 +45,7 @@ int main(int argc, char **argv) {
   int iterations = 4, levels = 3, rec_first = 4, rec_last = 13, num_stacks_tuner = 0;
   double resolution = 0.75, average = 700, delta = 150, lambda = 0.02, last_lambda = 0.01, smooth_mask = 4;
   bool no_matching = false, use_gpu_reg = false, no_registration = false, use_nmi = false;
+  bool auto_template = false, auto_central = false;                      // --useAutoTemplate (main.cc:199), --autoTemplateCentral (not a reference option)
   double sigma = 12.0, low_intensity_cutoff = 0.01;                      // main.cc:172, 181
   bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
@@ -86,6 +90,8 @@ int main(int argc, char **argv) {
     else if (o == "--rec_iterations_last") rec_last = atoi(one().c_str());
     else if (o == "--useGPUReg") use_gpu_reg = true;
     else if (o == "--useNMI") use_nmi = true;                             // main.cc:210 parses it and never calls setUseNMI(): here it takes effect
+    else if (o == "--useAutoTemplate") auto_template = true;              // main.cc:199, 565-591 (there: HAVE_CULA builds only)
+    else if (o == "--autoTemplateCentral") auto_template = auto_central = true;   // the middle third of the slices instead of the first
     else if (o == "-p" || o == "--packages") { std::vector<std::string> v; multi(v); for (auto &x : v) packages.push_back(atoi(x.c_str())); }
     else if (o == "--no_registration") no_registration = true;
     else if (o == "--tfolder") tfolder = one();
@@ -105,6 +111,14 @@ int main(int argc, char **argv) {
              "       [--rec_iterations_first 4] [--rec_iterations_last 13] [--packages p_1 ..] [--useGPUReg] [--no_registration] [--tfolder dir] [--sfolder dir]\n"
              "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n"
              "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
+             "       [--useAutoTemplate] [--autoTemplateCentral]\n"
+             "  --useAutoTemplate       select the 3D registration template stack automatically with the reference's matrix rank method:\n"
+             "                          every stack is cropped to the mask and the first third of its slices is scored by the rank its\n"
+             "                          singular values need for 99 %% of their norm; the smallest score becomes the template instead of the\n"
+             "                          first stack whose -t is id.  All transformations stay as given, only the template's number changes\n"
+             "                          (the chosen stack's -t need not be id; like the reference this build does not look at it).\n"
+             "  --autoTemplateCentral   deviation from the reference, whose code scores the FIRST third of the slices although its comment\n"
+             "                          says the central ones: score the middle third.  Implies --useAutoTemplate.\n"
              "  --useNMI                deviation from the reference, whose --useNMI is parsed and never takes effect: slice-to-volume and\n"
              "                          package-to-volume registration use normalised mutual information (64 bins, IRTK's histogram metric)\n"
              "                          instead of cross correlation -- for stacks whose contrast differs.  Not with --useGPUReg (CC only).\n"
@@ -162,6 +176,33 @@ int main(int argc, char **argv) {
     // normal mask path follows (main.cc:458-480, RG.cc:736-748)
     mask_img = stacks[tmpl];
     for (auto &v : mask_img.d) v = v > 0.0 ? 1.0 : 0.0;
+  }
+  if (auto_template) {                                                                           // main.cc:565-591
+    if (!have_mask) die("--useAutoTemplate crops every stack to the mask before it scores it: give -m (the reference skips the selection without a mask)");
+    if (dry_run) die("--dryRun makes no engine context and cannot score the stacks' motion: drop --useAutoTemplate / --autoTemplateCentral");
+    need_ctx();
+    double best = 1e300;                                                                         // tmp_motionestimate, main.cc:271
+    size_t best_k = tmpl;
+    for (size_t k = 0; k < n; ++k) {
+      // on a copy: TransformMask + CropImage with the -t transformations as given (the stack registrations come later)
+      const Image c = crop_image(stacks[k], transform_nn(mask_img, stacks[k].a, ts[k], 0.0));
+      const int m = c.a.nx * c.a.ny, nw = (int)(c.a.nz / 3.0), first = auto_central ? (c.a.nz - nw) / 2 : 0;
+      if (nw < 1) die("--useAutoTemplate: stack " + std::to_string(k) + " has " + std::to_string(c.a.nz) + " slices inside the mask; a third of them is none");
+      const auto mm = std::minmax_element(c.d.begin(), c.d.end());                               // the whole cropped stack's, not the window's
+      const double lo = *mm.first, hi = *mm.second;
+      if (!(hi > lo)) die("--useAutoTemplate: stack " + std::to_string(k) + " is constant inside the mask");
+      std::vector<float> win((size_t)m * nw);
+      for (size_t i = 0; i < win.size(); ++i) win[i] = (float)((c.d[(size_t)first * m + i] - lo) / (hi - lo));
+      double et = 0, score = 0;
+      int r_min = 0;
+      if (svr_stack_motion(ctx, win.data(), m, nw, nullptr, &et, &r_min, &score))
+        die("--useAutoTemplate: stack " + std::to_string(k) + ": " + svr_last_error(ctx));
+      fprintf(stderr, "stack %zu: motion score %.9g (r_min %d, et %.9g)\n", k, score, r_min, et);
+      if (score < best) { best = score; best_k = k; }                                            // strictly smaller: the first one on ties
+    }
+    tmpl = best_k;
+    fprintf(stderr, "Determined stack %zu as template.\n", tmpl);
+    clk.mark("motion measurement");
   }
   if (have_mask) {
     const Image m = transform_nn(mask_img, stacks[tmpl].a, ts[tmpl], 0.0);                     // TransformMask RG.cc:805-821

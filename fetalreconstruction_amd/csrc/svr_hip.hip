@@ -1243,6 +1243,8 @@ struct svr_ctx {
   size_t nmi_terms_n = 0;
   unsigned *d_nmi_merge = nullptr;       // merge slots of split evaluations + their counters, all zero between calls
   size_t nmi_slots = 0;
+  float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
+  double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
   uint32_t reg_vx = 0, reg_vy = 0, reg_vz = 0;
 
@@ -1317,7 +1319,8 @@ void reg_free(RegState *r);
 void cell_free(CellState *c);
 
 // The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
-// of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.
+// of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  The buffers of
+// svr_stack_motion (svr_motion.inc) cache nothing between calls -- they are freed before the call returns -- and have no line there.
 enum Change : unsigned {
   CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
   CH_TAPS = 1u << 1,              // new slice constants, generatePSFVolume: the table and the cell lists
@@ -2283,6 +2286,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_pyr_full[0]); free_dev(ctx->d_pyr_full[1]); free_dev(ctx->d_pyr_a); free_dev(ctx->d_pyr_b); free_dev(ctx->d_pyr_meta);
   free_dev(ctx->d_ncc_idx); free_dev(ctx->d_ncc_m); free_dev(ctx->d_ncc_s);
   free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
+  free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
   free_dev(ctx->d_coeff); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff_order);
   reg_free(ctx->reg);
   cell_free(ctx->cell);
@@ -3863,4 +3867,5 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 #include "svr_reg.inc"
 #include "svr_pyr.inc"
 #include "svr_nmi.inc"
+#include "svr_motion.inc"
 #include "svr_em.inc"

@@ -40,7 +40,7 @@ EXPORTS = [
     "svr_superresolution_backproject", "svr_superresolution_update", "svr_robust_statistics_sums",
     "svr_mstep_sums", "svr_scale_volume_sums", "svr_scale_volume_apply", "svr_timer_get",
     "svr_unit_counts", "svr_fallbacks", "svr_clock_probe", "svr_slice_em_setup", "svr_slice_em_set_state", "svr_mstep_estep_device", "svr_slice_em_run", "svr_slice_em_apply_weights", "svr_slice_em_fetch", "svr_slice_em_set_patch_form", "svr_cell_stats", "svr_pair_pack", "svr_pair_unpack", "svr_timer_reset", "svr_timer_enable", "svr_timer_begin", "svr_timer_end", "svr_timer_add", "svr_counters", "svr_get_stream", "svr_device", "svr_device_count", "svr_combine_weights", "svr_update_stack_sizes", "svr_ncc_set_targets", "svr_ncc_set_source",
-    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
+    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_pvr_cc_patches", "svr_pvr_register_patches",
@@ -385,6 +385,17 @@ class Reconstruction:
         self._ck(self._lib.svr_nmi_evaluate(self._h, len(ppe), _p(ppe), _p(idx), _p(m), _p(w), _p(nb), int(source_nbins), _p(out),
                                             _p(h) if h is not None else None))
         return out, h
+
+    def stack_motion(self, slices):
+        """svr_stack_motion on float32 slices [n][...] (already normalised; a slice is flattened to its pixels) ->
+        (singular values float64 [n] descending, et, r_min, score): the reference's --useAutoTemplate score of a stack window."""
+        a = _f32(slices)
+        n = int(a.shape[0]) if a.ndim else 0
+        a = a.reshape(n, int(np.prod(a.shape[1:])) if a.ndim > 1 else 1)
+        s = np.zeros(max(n, 1), np.float64)
+        et, r_min, score = C.c_double(0.0), C.c_int(0), C.c_double(0.0)
+        self._ck(self._lib.svr_stack_motion(self._h, _p(a), int(a.shape[1]), n, _p(s), C.byref(et), C.byref(r_min), C.byref(score)))
+        return s[:n], et.value, r_min.value, score.value
 
     # ---- GPU slice-to-volume registration (RC.cuh:326-338) ------------------------------------
     def initRegStorageVolumes(self, W, H, ns, dim=(1.0, 1.0, 1.0)):

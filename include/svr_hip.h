@@ -305,6 +305,16 @@ int svr_ncc_evaluate(svr_ctx *ctx, int n_eval, const int *target_index, const do
 int svr_nmi_bin_source(svr_ctx *ctx, int width);
 int svr_nmi_evaluate(svr_ctx *ctx, int n_eval, const int *planes_per_eval, const int *target_index, const double *matrices,
                      const int *target_width, const int *target_nbins, int source_nbins, double *out4, uint32_t *hist_or_null);
+/* The motion score of a stack (csrc/svr_motion.inc; the reference's --useAutoTemplate, stackMotionEstimator.cpp:67-164, there on
+ * CULA's SVD).  slices: host memory, [n][m] -- n slices of m pixels, already normalised to [0, 1] with the stack's min / max.  The
+ * singular values of the m x n matrix whose columns are the slices come from its n x n Gram matrix (accumulated in double on the
+ * device, in a fixed order) and cyclic Jacobi in double: descending, [n], when asked for.  Then, as the reference has it:
+ * error(r) = sqrt(sum_{i<r} S_i^2) / sqrt(sum_i S_i^2) for r = 0 .. n - 1, the last r with error(r) < 0.99 is *r_min, its error
+ * *et (start values -1 and 0), and *score = et * r_min; the smallest score is the stack that moved least.  Refused with a message:
+ * n < 1 (a stack of fewer than 3 slices has no third), n > m, a window that is zero everywhere.  Nothing of the call stays on the
+ * device. */
+int svr_stack_motion(svr_ctx *ctx, const float *slices, int m, int n, double *singular_values_or_null, double *et, int *r_min,
+                     double *score);
 
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::
