@@ -25,7 +25,10 @@
 // method (main.cc:565-591, stackMotionEstimator.cpp:67-164; there only in builds with CULA): every stack, cropped to the
 // mask, gets the motion score of its first nz / 3 slices (svr_stack_motion, csrc/svr_motion.inc) and the smallest score replaces
 // the stack found from `-t id`; --autoTemplateCentral (a deviation) scores the middle third instead, which is what the
-// reference's comment describes.  Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
+// reference's comment describes.  --sliceReport <file> and --simulatedStacks <prefix> (deviations: the reference keeps SlicesInfo and
+// SimulateStacks, RG.cc:4937-4975, 1205-1262, and its main() calls neither) say how the run went, after the volume has been written:
+// one forward projection of the final volume, per slice the reference's twelve columns plus n_px, n, ncc, rmse, mae and mean_weight
+// (svr_slice_quality, csrc/svr_quality.inc), and the simulated slices put back into the cropped stacks.  Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
 #include <functional>
 #include <thread>
 
@@ -48,6 +51,7 @@ int main(int argc, char **argv) {
   bool auto_template = false, auto_central = false;                      // --useAutoTemplate (main.cc:199), --autoTemplateCentral (not a reference option)
   double sigma = 12.0, low_intensity_cutoff = 0.01;                      // main.cc:172, 181
   bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
+  std::string report_name, sim_prefix;                                   // --sliceReport, --simulatedStacks (not reference options)
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
   // ---- options (main.cc:164-211) ---------------------------------------------------------------------
   auto is_opt = [](const char *s) { return s[0] == '-' && !(s[1] >= '0' && s[1] <= '9') && s[1] != '.'; };
@@ -102,6 +106,8 @@ int main(int argc, char **argv) {
     else if (o == "--saveSliceTransformations") save_slice_transformations = true;   // main.cc:211, 1213-1217
     else if (o == "--dumpProblem") dump_name = one();                     // test hooks: what the engine is about to receive [--dryRun: stop there]
     else if (o == "--dryRun") dry_run = true;
+    else if (o == "--sliceReport") report_name = one();                   // not reference options: the reference's main() never calls SlicesInfo / SimulateStacks
+    else if (o == "--simulatedStacks") sim_prefix = one();
     else if (o == "--useCPUReg" || o == "--disableBiasCorrection" || o == "--debug_gpu") {}
     else if (o == "-d" || o == "--devices") { std::vector<std::string> v; multi(v); for (auto &s : v) devices.push_back(atoi(s.c_str())); }
     else if (o == "-h" || o == "--help") {
@@ -111,7 +117,16 @@ int main(int argc, char **argv) {
              "       [--rec_iterations_first 4] [--rec_iterations_last 13] [--packages p_1 ..] [--useGPUReg] [--no_registration] [--tfolder dir] [--sfolder dir]\n"
              "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n"
              "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
-             "       [--useAutoTemplate] [--autoTemplateCentral]\n"
+             "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix]\n"
+             "  --sliceReport <file>    deviation from the reference, which has SlicesInfo and never calls it: after the volume is written,\n"
+             "                          project it into the slices once more and write one tab-separated row per slice, in slice order:\n"
+             "                          SlicesInfo's stack_index included excluded outside weight scale Translation{X,Y,Z} Rotation{X,Y,Z},\n"
+             "                          then n_px (pixels in the mask), n (pixels the M-step counts) and over those the correlation ncc, rmse,\n"
+             "                          mae of the scaled slice against its simulation and the mean posterior weight (nan: too few pixels).\n"
+             "                          Totals and the median ncc per stack go to stderr.  The volume is the same with and without it.\n"
+             "  --simulatedStacks <pfx> deviation from the reference, which has SimulateStacks and never calls it: write <pfx><k>.nii.gz for\n"
+             "                          every stack k in the geometry of the cropped stack: the simulated slice where the slice has a pixel\n"
+             "                          and is included, 0 elsewhere.  Not with --sfolder.  Neither option with --dryRun.\n"
              "  --useAutoTemplate       select the 3D registration template stack automatically with the reference's matrix rank method:\n"
              "                          every stack is cropped to the mask and the first third of its slices is scored by the rank its\n"
              "                          singular values need for 99 %% of their norm; the smallest score becomes the template instead of the\n"
@@ -131,6 +146,11 @@ int main(int argc, char **argv) {
     }
   }
   if (output.empty() || inputs.empty()) die("-o and -i are required (try --help)");
+  if (dry_run && (!report_name.empty() || !sim_prefix.empty()))
+    die("--dryRun stops before the reconstruction; --sliceReport / --simulatedStacks describe a finished one: drop one or the other");
+  if (!sim_prefix.empty() && !sfolder.empty())
+    die("--simulatedStacks puts every simulated slice back into the stack it was cut from; with --sfolder the slices come from files of "
+        "their own and belong to no stack: use --sliceReport, or drop --sfolder");
   if (use_nmi && use_gpu_reg)
     die("--useNMI selects normalised mutual information for the IRTK registration; the reference's GPU registration (--useGPUReg) is "
         "cross-correlation only: use one or the other");
@@ -531,6 +551,93 @@ int main(int argc, char **argv) {
   clk.mark("restore, scale, download");
   if (svr_nifti_write(output.c_str(), &tattr, vol.data(), err)) die(output + ": " + err);
   clk.mark("write the volume");
+  if (!report_name.empty() || !sim_prefix.empty()) {
+    // How the run went (not in the reference's main(); SlicesInfo RG.cc:4937-4975, SimulateStacks :1205-1262, EvaluateGPU :4503-4538).
+    // The volume is on disk: nothing from here on can reach it.  Every rank projects the final volume into its slices once and
+    // reduces them (svr_slice_quality); rows and stacks are written in the reference's slice order, through order[].
+    std::vector<float> scale_g(ns), weight_g(ns), sim;
+    std::vector<unsigned char> inside(ns);
+    std::vector<double> sums((size_t)ns * SVR_SLICE_QUALITY_SUMS, 0.0);
+    if (!sim_prefix.empty()) sim.resize((size_t)ns * mx * my);
+    par([&](int r) {                                                     // (collective: the other ranks' vectors may still be on their way)
+      HOSTR(r, svrh_get_state(hosts[r], r ? nullptr : scale_g.data(), r ? nullptr : weight_g.data(), nullptr, nullptr, nullptr));
+    });
+    std::vector<double> t_sim(nr, 0.0), t_qual(nr, 0.0);
+    par([&](int r) {
+      const size_t o = (size_t)rlo[r], nl = (size_t)(rhi[r] - rlo[r]);
+      const auto t0 = std::chrono::steady_clock::now();
+      ENGR(r, svr_simulate_slices(ctxs[r], inside.data() + o));
+      const auto t1 = std::chrono::steady_clock::now();
+      if (!report_name.empty()) ENGR(r, svr_slice_quality(ctxs[r], sums.data() + o * SVR_SLICE_QUALITY_SUMS));
+      const auto t2 = std::chrono::steady_clock::now();
+      if (!sim_prefix.empty()) ENGR(r, svr_debug_get(ctxs[r], SVR_BUF_SIMSLICES, sim.data() + o * mx * my, nl * mx * my * sizeof(float)));
+      t_sim[r] = std::chrono::duration<double>(t1 - t0).count(); t_qual[r] = std::chrono::duration<double>(t2 - t1).count();
+    });
+    if (clk.on)
+      fprintf(stderr, "[timing] forward projection of the final volume %.3f ms, svr_slice_quality %.3f ms (slowest rank, host clock)\n",
+              1e3 * *std::max_element(t_sim.begin(), t_sim.end()), 1e3 * *std::max_element(t_qual.begin(), t_qual.end()));
+    auto included = [&](int s) { return weight_g[s] >= 0.5f && inside[s]; };
+    if (!report_name.empty()) {
+      std::vector<int> r_stack(ns);
+      std::vector<float> r_weight(ns), r_scale(ns);
+      std::vector<unsigned char> r_inside(ns);
+      std::vector<double> r_p6(6 * (size_t)ns), r_sums(sums.size());
+      for (int i = 0; i < ns; ++i) {                                     // row i = slice i of the reference's order
+        const int s = inv_order[i];
+        r_stack[i] = stack_index[s]; r_weight[i] = weight_g[s]; r_scale[i] = scale_g[s]; r_inside[i] = inside[s];
+        svrh_irtk_rigid_parameters(&T[16 * (size_t)s], &r_p6[6 * (size_t)i], nullptr);
+        std::copy(sums.begin() + (size_t)s * SVR_SLICE_QUALITY_SUMS, sums.begin() + (size_t)(s + 1) * SVR_SLICE_QUALITY_SUMS,
+                  r_sums.begin() + (size_t)i * SVR_SLICE_QUALITY_SUMS);
+      }
+      if (svr_slice_report_write(report_name.c_str(), ns, r_stack.data(), r_weight.data(), r_inside.data(), r_scale.data(), r_p6.data(),
+                                 r_sums.data(), err))
+        die(report_name + ": " + err);
+      // the three lists of EvaluateGPU, then what the weights alone do not say: how well each stack's kept slices match the volume
+      const char *names[3] = {"Included", "Excluded", "Outside"};
+      for (int kind = 0; kind < 3; ++kind) {
+        int total = 0;
+        fprintf(stderr, "%s slices:", names[kind]);
+        for (int i = 0; i < ns; ++i) {
+          const bool in = r_inside[i] != 0, kept = r_weight[i] >= 0.5f;
+          if (kind == 0 ? (kept && in) : kind == 1 ? (!kept && in) : !in) { fprintf(stderr, " %d", i); ++total; }
+        }
+        fprintf(stderr, "\nTotal: %d\n", total);
+      }
+      for (size_t k = 0; k < n; ++k) {
+        std::vector<double> v;
+        for (int i = 0; i < ns; ++i) {
+          if (r_stack[i] != (int)k || !(r_weight[i] >= 0.5f && r_inside[i])) continue;
+          double d4[4];
+          svr_slice_quality_derive(&r_sums[(size_t)i * SVR_SLICE_QUALITY_SUMS], d4);
+          if (d4[0] == d4[0]) v.push_back(d4[0]);
+        }
+        std::sort(v.begin(), v.end());
+        const double med = v.empty() ? NAN : (v.size() % 2 ? v[v.size() / 2] : 0.5 * (v[v.size() / 2 - 1] + v[v.size() / 2]));
+        if (v.empty()) fprintf(stderr, "stack %zu: no included slice with a defined ncc\n", k);
+        else fprintf(stderr, "stack %zu: median ncc %.6f over %zu included slices\n", k, med, v.size());
+      }
+    }
+    if (!sim_prefix.empty()) {
+      int base = 0;                                                      // the stack's first slice in the reference's order
+      for (size_t k = 0; k < n; ++k) {
+        const svr_image_attr &a = stacks[k].a;
+        std::vector<float> out((size_t)a.nx * a.ny * a.nz, 0.0f);       // excluded and outside slices stay zero, as SimulateStacks leaves them
+        for (int j = 0; j < a.nz; ++j) {
+          const int s = inv_order[base + j];
+          if (!included(s)) continue;
+          for (int y = 0; y < a.ny; ++y)
+            for (int x = 0; x < a.nx; ++x) {
+              const size_t g = ((size_t)s * my + y) * mx + x;
+              if (grid[g] != -1.0f) out[((size_t)j * a.ny + y) * a.nx + x] = sim[g];
+            }
+        }
+        base += a.nz;
+        const std::string path = sim_prefix + std::to_string(k) + ".nii.gz";
+        if (svr_nifti_write(path.c_str(), &a, out.data(), err)) die(path + ": " + err);
+      }
+    }
+    clk.mark("slice report, simulated stacks");
+  }
   if (debug) {                                                           // SaveTransformations, RG.cc:4903-4915
     const size_t cut = output.find_last_of('/');
     const std::string folder = cut == std::string::npos ? "." : output.substr(0, cut);

@@ -1097,6 +1097,7 @@ struct svr_ctx {
   unsigned char *d_siminside = nullptr;
   int *d_voxcount = nullptr;
   bool have_slices = false;
+  bool have_sim = false;                // d_simslices / d_simweights hold a forward projection (svr_simulate_slices, or a test's svr_debug_set)
   bool sem_weights_current = false;     // d_slice_weights holds the device-side EM's weights (svr_slice_em_run) and nobody has written it since
   float *d_scales = nullptr, *d_slice_weights = nullptr, *d_scales_host_copy = nullptr,
         *d_tmp_ns = nullptr;
@@ -1245,6 +1246,8 @@ struct svr_ctx {
   size_t nmi_slots = 0;
   float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
   double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
+  double *d_qual_partial = nullptr, *d_qual_sums = nullptr;   // svr_slice_quality (svr_quality.inc): likewise
+  int last_quality_chunks = -1;          // chunks per slice of the last svr_slice_quality (read-only option "quality_chunks"; -1 = not launched yet)
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
   uint32_t reg_vx = 0, reg_vy = 0, reg_vz = 0;
 
@@ -1320,7 +1323,8 @@ void cell_free(CellState *c);
 
 // The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
 // of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  The buffers of
-// svr_stack_motion (svr_motion.inc) cache nothing between calls -- they are freed before the call returns -- and have no line there.
+// svr_stack_motion (svr_motion.inc) cache nothing between calls -- they are freed before the call returns -- and have no line there;
+// nor have those of svr_slice_quality (svr_quality.inc).
 enum Change : unsigned {
   CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
   CH_TAPS = 1u << 1,              // new slice constants, generatePSFVolume: the table and the cell lists
@@ -2266,7 +2270,7 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value) {
       {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells},
       {"bias_field_bx", ctx->last_bias_bx}, {"bias_tail_lds", ctx->last_tail_lds}, {"bias_tail_rows", ctx->last_tail_rows},
       {"bias_tail_bxy", ctx->last_tail_bxy}, {"bias_tail_bxz", ctx->last_tail_bxz}, {"reg_zc", ctx->last_reg_zc}, {"reg_chunks", ctx->last_reg_chunks},
-      {"psf_list_valid", ctx->psf_list_valid}, {"cells_valid", cells_valid}};
+      {"psf_list_valid", ctx->psf_list_valid}, {"cells_valid", cells_valid}, {"quality_chunks", ctx->last_quality_chunks}};
   for (const auto &e : tab)
     if (!strcmp(name, e.n)) { *value = e.v; return SVR_OK; }
   return fail(ctx, SVR_E_ARG, std::string("unknown option ") + name);
@@ -2287,6 +2291,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_ncc_idx); free_dev(ctx->d_ncc_m); free_dev(ctx->d_ncc_s);
   free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
   free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
+  free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums);
   free_dev(ctx->d_coeff); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff_order);
   reg_free(ctx->reg);
   cell_free(ctx->cell);
@@ -2466,7 +2471,7 @@ int svr_init_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const float d
   free_dev(ctx->d_bias); free_dev(ctx->d_wb); free_dev(ctx->d_wr); free_dev(ctx->d_buffer);
   ctx->sx = size[0]; ctx->sy = size[1]; ctx->ns = size[2];
   ctx->np = np;
-  ctx->have_slices = false; ctx->have_scales = false; ctx->have_dims = false; ctx->have_mats = false;
+  ctx->have_slices = false; ctx->have_sim = false; ctx->have_scales = false; ctx->have_dims = false; ctx->have_mats = false;
   ctx->n_active = ctx->n_psf = 0;
   invalidate(ctx, CH_SLICE_GEOMETRY | CH_SLICE_PIXELS | CH_TABLE_OFF);
   free_dev(ctx->d_coeff_id);
@@ -2797,6 +2802,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
     if ((r = launch_pixels(ctx, a, ctx->pvr ? pvr_kernel<MODE_FWD> : psf_kernel<MODE_FWD>, "psf_kernel / pvr_kernel<FWD>"))) return r;
   }
   t.stop();
+  ctx->have_sim = true;
   if (!gcs) {                                              // (the cell gather's finish raises the slices' flags itself)
     hipLaunchKernelGGL(k_slice_inside, dim3(ctx->ns), dim3(256), 0, ctx->stream, ctx->d_siminside,
                        (int)(ctx->sx * ctx->sy), ctx->d_slice_inside);
@@ -3429,6 +3435,7 @@ int svr_debug_set(svr_ctx *ctx, int which, const void *host_in, size_t bytes) {
   // (a mask set behind svr_set_mask's back: no mask box, the whole pair is exchanged; maskC stays as it was)
   invalidate(ctx, which == SVR_BUF_SLICES ? CH_SLICE_PIXELS : which == SVR_BUF_PSF_SUMS ? CH_PSF_SUMS : which == SVR_BUF_MASK ? CH_MASK
                   : which == SVR_BUF_RECONSTRUCTED ? CH_VOLUME_VALUES : which == SVR_BUF_ADDON || which == SVR_BUF_CONFIDENCE_MAP ? CH_SCATTER_TARGETS : 0u);
+  if (which == SVR_BUF_SIMSLICES) ctx->have_sim = true;   // (a test's own forward projection: svr_slice_quality takes it)
   if (which == SVR_BUF_SLICES) return build_list(ctx, false);
   return SVR_OK;
 }
@@ -3868,4 +3875,5 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 #include "svr_pyr.inc"
 #include "svr_nmi.inc"
 #include "svr_motion.inc"
+#include "svr_quality.inc"
 #include "svr_em.inc"

@@ -405,4 +405,50 @@ int svr_dof_write(const char *path, const double params6[6], char err[256]) {
 
 void svr_free(void *p) { free(p); }
 
+// One row of svr_slice_quality -> {ncc, rmse, mae, mean_weight}, in double.  ncc is Pearson's coefficient of the scaled slice
+// against the simulated one over the M-step's pixels; undefined (nan) for fewer than two pixels or when either variance
+// (their product under the root) is not positive.  The other three are nan for a slice without such pixels.
+void svr_slice_quality_derive(const double s[SVR_SLICE_QUALITY_SUMS], double derived4[4]) {
+  if (!s || !derived4) return;
+  const double n = s[1], sx = s[2], sy = s[3], sxx = s[4], syy = s[5], sxy = s[6];
+  derived4[0] = derived4[1] = derived4[2] = derived4[3] = NAN;
+  if (n >= 2) {
+    const double under = (sxx - sx * sx / n) * (syy - sy * sy / n);
+    if (under > 0) derived4[0] = (sxy - sx * sy / n) / sqrt(under);
+  }
+  if (n > 0) {
+    derived4[1] = sqrt(s[7] / n);
+    derived4[2] = s[8] / n;
+    derived4[3] = s[9] / n;
+  }
+}
+
+// The per-slice report of --sliceReport: the twelve columns of irtkReconstruction::SlicesInfo (irtkReconstructionGPU.cc:4937-4975)
+// under its names and in its order, then n_px, n and the derived values of the slice's sums.  Tab-separated, one row per slice
+// in the order of the arrays; nan is written as `nan` whatever its sign bit.
+int svr_slice_report_write(const char *path, int n_slices, const int *stack_index, const float *slice_weight, const unsigned char *slice_inside,
+                           const float *scale, const double *params6, const double *sums, char err[256]) {
+  if (!path || n_slices < 0 || (n_slices > 0 && (!stack_index || !slice_weight || !slice_inside || !scale || !params6 || !sums)))
+    return set_err(err, "svr_slice_report_write: missing argument");
+  FILE *f = fopen(path, "w");
+  if (!f) return set_err(err, std::string("cannot create ") + path);
+  auto num = [&](double v) { if (v != v) fputs("\tnan", f); else fprintf(f, "\t%.9g", v); };
+  fputs("stack_index\tincluded\texcluded\toutside\tweight\tscale\tTranslationX\tTranslationY\tTranslationZ\tRotationX\tRotationY\tRotationZ"
+        "\tn_px\tn\tncc\trmse\tmae\tmean_weight\n", f);
+  for (int i = 0; i < n_slices; ++i) {
+    const bool inside = slice_inside[i] != 0, kept = slice_weight[i] >= 0.5f;
+    fprintf(f, "%d\t%d\t%d\t%d", stack_index[i], (kept && inside) ? 1 : 0, (!kept && inside) ? 1 : 0, inside ? 0 : 1);
+    num(slice_weight[i]); num(scale[i]);
+    for (int k = 0; k < 6; ++k) num(params6[6 * (size_t)i + k]);
+    const double *s = sums + (size_t)SVR_SLICE_QUALITY_SUMS * i;
+    double d[4];
+    svr_slice_quality_derive(s, d);
+    fprintf(f, "\t%.0f\t%.0f", s[0], s[1]);
+    for (int k = 0; k < 4; ++k) num(d[k]);
+    fputc('\n', f);
+  }
+  const bool ok = !ferror(f);
+  return (fclose(f) == 0 && ok) ? SVR_OK : set_err(err, "write failed");
+}
+
 }  // extern "C"

@@ -40,7 +40,7 @@ EXPORTS = [
     "svr_superresolution_backproject", "svr_superresolution_update", "svr_robust_statistics_sums",
     "svr_mstep_sums", "svr_scale_volume_sums", "svr_scale_volume_apply", "svr_timer_get",
     "svr_unit_counts", "svr_fallbacks", "svr_clock_probe", "svr_slice_em_setup", "svr_slice_em_set_state", "svr_mstep_estep_device", "svr_slice_em_run", "svr_slice_em_apply_weights", "svr_slice_em_fetch", "svr_slice_em_set_patch_form", "svr_cell_stats", "svr_pair_pack", "svr_pair_unpack", "svr_timer_reset", "svr_timer_enable", "svr_timer_begin", "svr_timer_end", "svr_timer_add", "svr_counters", "svr_get_stream", "svr_device", "svr_device_count", "svr_combine_weights", "svr_update_stack_sizes", "svr_ncc_set_targets", "svr_ncc_set_source",
-    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
+    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_pvr_cc_patches", "svr_pvr_register_patches",
@@ -396,6 +396,16 @@ class Reconstruction:
         et, r_min, score = C.c_double(0.0), C.c_int(0), C.c_double(0.0)
         self._ck(self._lib.svr_stack_motion(self._h, _p(a), int(a.shape[1]), n, _p(s), C.byref(et), C.byref(r_min), C.byref(score)))
         return s[:n], et.value, r_min.value, score.value
+
+    def slice_quality(self):
+        """svr_slice_quality -> float64 [ns][10]: per slice {n_px, n, sum x, sum y, sum x^2, sum y^2, sum xy, sum e^2, sum |e|, sum w}
+        of x = the scaled (bias-corrected) slice against y = the simulated slice, over the M-step's pixels (include/svr_hip.h).
+        SimulateSlices first; host.slice_quality_derive turns a row into ncc / rmse / mae / mean weight."""
+        if not self.sgrid:
+            raise SvrError("slice_quality: initStorageVolumes first")
+        out = np.zeros((self.sgrid[0], 10), np.float64)
+        self._ck(self._lib.svr_slice_quality(self._h, _p(out)))
+        return out
 
     # ---- GPU slice-to-volume registration (RC.cuh:326-338) ------------------------------------
     def initRegStorageVolumes(self, W, H, ns, dim=(1.0, 1.0, 1.0)):

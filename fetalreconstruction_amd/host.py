@@ -31,7 +31,8 @@ PVR_HOST_EXPORTS = ["pvrh_create", "pvrh_destroy", "pvrh_last_error", "pvrh_init
 IRTK_EXPORTS = ["svrh_stack_registrations", "svrh_slice_to_volume_registration", "svrh_package_to_volume", "svrh_irtk_resample_with_padding",
                 "svrh_irtk_blur_with_padding", "svrh_irtk_rigid_parameters", "svrh_slice_to_volume_registration_ex", "svrh_package_to_volume_ex",
                 "svrh_irtk_number_of_bins", "svrh_nmi_sums"]                                                  # csrc/irtk_reg.cpp
-IO_EXPORTS = ["svr_nifti_read", "svr_nifti_write", "svr_free", "svr_dof_read", "svr_dof_write", "svr_host_threads"]      # csrc/svr_io.cpp, declared in svr_host.h
+IO_EXPORTS = ["svr_nifti_read", "svr_nifti_write", "svr_free", "svr_dof_read", "svr_dof_write", "svr_host_threads",
+              "svr_slice_quality_derive", "svr_slice_report_write"]      # csrc/svr_io.cpp, declared in svr_host.h
 
 
 class ImageAttr(C.Structure):
@@ -675,3 +676,34 @@ def irtk_rigid_parameters(matrix):
     p, r = np.zeros(6), np.zeros(16)
     _reg_lib().svrh_irtk_rigid_parameters(m.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p))
     return p, r.reshape(4, 4)
+
+
+def slice_quality_derive(sums):
+    """svr_slice_quality_derive on rows of engine.Reconstruction.slice_quality() -> float64 [..., 4] = {ncc, rmse, mae, mean_weight}
+    (nan where a slice has too few pixels, include/svr_host.h)"""
+    lib = _engine.load_library()
+    lib.svr_slice_quality_derive.restype = None
+    s = np.ascontiguousarray(sums, np.float64)
+    if s.shape[-1] != 10:
+        raise ValueError("slice_quality_derive: rows of ten sums expected")
+    rows = s.reshape(-1, 10)
+    out = np.zeros((len(rows), 4), np.float64)
+    for i in range(len(rows)):
+        lib.svr_slice_quality_derive(rows[i].ctypes.data_as(C.c_void_p), out[i].ctypes.data_as(C.c_void_p))
+    return out.reshape(s.shape[:-1] + (4,))
+
+
+def write_slice_report(path, stack_index, slice_weight, slice_inside, scale, params6, sums):
+    """svr_slice_report_write: the tab-separated per-slice report of --sliceReport, one row per slice in the order of the arrays"""
+    lib = _engine.load_library()
+    si = np.ascontiguousarray(stack_index, np.int32)
+    n = len(si)
+    w, sc = np.ascontiguousarray(slice_weight, np.float32), np.ascontiguousarray(scale, np.float32)
+    ins = np.ascontiguousarray(np.asarray(slice_inside) != 0, np.uint8)
+    p6, s = np.ascontiguousarray(params6, np.float64).reshape(n, 6), np.ascontiguousarray(sums, np.float64).reshape(n, 10)
+    if not (len(w) == len(sc) == len(ins) == n):
+        raise ValueError("write_slice_report: one entry per slice expected")
+    err = C.create_string_buffer(256)
+    rc = lib.svr_slice_report_write(str(path).encode(), n, *[a.ctypes.data_as(C.c_void_p) for a in (si, w, ins, sc, p6, s)], err)
+    if rc != 0:
+        raise _engine.SvrError(f"svr_slice_report_write: {err.value.decode()}")

@@ -315,6 +315,17 @@ int svr_nmi_evaluate(svr_ctx *ctx, int n_eval, const int *planes_per_eval, const
  * device. */
 int svr_stack_motion(svr_ctx *ctx, const float *slices, int m, int n, double *singular_values_or_null, double *et, int *r_min,
                      double *score);
+/* How well every slice (or patch) of the context agrees with the volume it helped build (csrc/svr_quality.inc; no reference
+ * equivalent on the device -- irtkReconstruction::SlicesInfo / EvaluateGPU, irtkReconstructionGPU.cc:4937-4975, 4503-4538, list
+ * weights and flags only).  Reads the buffers as they stand, so svr_simulate_slices comes first; refused with a message while
+ * the slices, the scale vector or a forward projection are missing.  With the M-step's float expressions (RC.cu:2940-3000)
+ *   x = bias ? s * expf(-bias) * scale : s * scale,   y = simulated slice,   e = x - y
+ * sums[slice][10] = {n_px: pixels with s != -1;  n: the M-step's pixels, s != -1 and simweight > 0.99;  then over those:
+ * sum x, sum y, sum x^2, sum y^2, sum x y, sum e^2, sum |e|, sum of the posterior weights (SVR_BUF_WEIGHTS)}, every product and
+ * sum in double.  No atomics, a fixed order: the same bits on every call.  The number of workgroups per slice follows from the
+ * slice grid alone and is readable afterwards as the option "quality_chunks".  Nothing of the call stays on the device. */
+#define SVR_SLICE_QUALITY_SUMS 10
+int svr_slice_quality(svr_ctx *ctx, double *sums /* [ns][SVR_SLICE_QUALITY_SUMS] */);
 
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::

@@ -163,6 +163,19 @@ int svr_dof_write(const char *path, const double params6[6], char err[256]);
  * periods to throttling when a pool starts 128 threads.  SVR_HOST_THREADS overrides.  Used by the registration's work
  * pool, the pre-processing of the command lines and the NIfTI writer. */
 int svr_host_threads(void);
+/* The quality report of a finished run (the command line's --sliceReport; a deviation from the reference, whose
+ * irtkReconstruction::SlicesInfo, irtkReconstructionGPU.cc:4937-4975, is never called by its main()).
+ * svr_slice_quality_derive: one row of svr_slice_quality's sums -> derived4 = {ncc, rmse, mae, mean_weight}, in double:
+ *   ncc = (Sxy - Sx Sy / n) / sqrt((Sxx - Sx^2 / n)(Syy - Sy^2 / n)), nan when n < 2 or the product under the root is <= 0;
+ *   rmse = sqrt(See / n), mae = S|e| / n, mean_weight = Sw / n, all nan when n = 0.
+ * svr_slice_report_write: a tab-separated file, a header and one row per slice in the order of the arrays: SlicesInfo's
+ *   stack_index included excluded outside weight scale TranslationX TranslationY TranslationZ RotationX RotationY RotationZ
+ * (included = weight >= 0.5 and inside, excluded = weight < 0.5 and inside, outside = not inside; params6 [n][6] as
+ * svrh_irtk_rigid_parameters gives them), then n_px n ncc rmse mae mean_weight from sums [n][SVR_SLICE_QUALITY_SUMS].  nan is
+ * written as `nan`. */
+void svr_slice_quality_derive(const double sums[SVR_SLICE_QUALITY_SUMS], double derived4[4]);
+int svr_slice_report_write(const char *path, int n_slices, const int *stack_index, const float *slice_weight, const unsigned char *slice_inside,
+                           const float *scale, const double *params6, const double *sums, char err[256]);
 
 /* The numbering of a sharded run (round 5).  A launcher may deal the units to the ranks in any order -- e.g. the r-th part of EVERY stack
  * to rank r, so that a rank's slices are neighbours in space and it stages 1/N of the volume's work items instead of those of whole
