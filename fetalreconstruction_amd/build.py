@@ -16,6 +16,7 @@ SRC_PYR = os.path.join(HERE, "csrc", "svr_pyr.inc")       # device pyramid of th
 SRC_NMI = os.path.join(HERE, "csrc", "svr_nmi.inc")       # NMI joint histograms of the IRTK registration, #included by svr_hip.hip
 SRC_MOTION = os.path.join(HERE, "csrc", "svr_motion.inc")  # the stack motion score of --useAutoTemplate (Gram matrix by f64 MFMA), #included by svr_hip.hip
 SRC_QUALITY = os.path.join(HERE, "csrc", "svr_quality.inc")  # the per-slice quality sums of --sliceReport, #included by svr_hip.hip
+SRC_SEED = os.path.join(HERE, "csrc", "svr_seed.inc")        # a volume on any grid resampled onto the reconstruction grid (--referenceVolume), #included by svr_hip.hip
 SRC_HOST = os.path.join(HERE, "csrc", "svr_host.cpp")     # plain host C++ (the irtkReconstruction mirror)
 SRC_IO = os.path.join(HERE, "csrc", "svr_io.cpp")         # NIfTI-1 reader / writer (zlib)
 SRC_PVR_HOST = os.path.join(HERE, "csrc", "pvr_host.cpp")  # the irtkPatchBasedReconstruction loop (host C++)
@@ -63,7 +64,7 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(f) > t for f in (SRC, SRC_REG, SRC_PYR, SRC_NMI, SRC_MOTION, SRC_QUALITY, SRC_HOST, SRC_IO, SRC_PVR_HOST, SRC_IRTK, SRC_RCCL, SRC_PREP, SRC_SLIC, SRC_SHARD, SRC_UNIT_EM, SRC_REGUL, SRC_EM, SRC_CELL, SRC_TILE, SRC_SMALL, SRC_BIAS, SRC_RCCL_ABI, SRC_SORT, SRC_CLI, SRC_PVR_CLI, INC, INC_HOST,
+    return any(os.path.getmtime(f) > t for f in (SRC, SRC_REG, SRC_PYR, SRC_NMI, SRC_MOTION, SRC_QUALITY, SRC_SEED, SRC_HOST, SRC_IO, SRC_PVR_HOST, SRC_IRTK, SRC_RCCL, SRC_PREP, SRC_SLIC, SRC_SHARD, SRC_UNIT_EM, SRC_REGUL, SRC_EM, SRC_CELL, SRC_TILE, SRC_SMALL, SRC_BIAS, SRC_RCCL_ABI, SRC_SORT, SRC_CLI, SRC_PVR_CLI, INC, INC_HOST,
                                                __file__)) or not (os.path.exists(CLI) and os.path.exists(PVR_CLI))
 
 

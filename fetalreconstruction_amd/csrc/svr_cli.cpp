@@ -28,7 +28,11 @@
 // reference's comment describes.  --sliceReport <file> and --simulatedStacks <prefix> (deviations: the reference keeps SlicesInfo and
 // SimulateStacks, RG.cc:4937-4975, 1205-1262, and its main() calls neither) say how the run went, after the volume has been written:
 // one forward projection of the final volume, per slice the reference's twelve columns plus n_px, n, ncc, rmse, mae and mean_weight
-// (svr_slice_quality, csrc/svr_quality.inc), and the simulated slices put back into the cropped stacks.  Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
+// (svr_slice_quality, csrc/svr_quality.inc), and the simulated slices put back into the cropped stacks.  --referenceVolume <file> (a
+// deviation: the reference reads the file, main.cc:253-258, lets iteration 0 register, :826, and outside its T1 experiment never hands
+// the voxels to the registration) seeds the run with a volume in the template's world space on any grid: resampled onto the
+// reconstruction grid on the device (svr_resample_to_reconstruction, csrc/svr_seed.inc), brought to the stacks' intensity scale, it is
+// every rank's reconstructed volume when the loop starts, and iteration 0 registers against it like any later one.  Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
 #include <functional>
 #include <thread>
 
@@ -51,6 +55,7 @@ int main(int argc, char **argv) {
   bool auto_template = false, auto_central = false;                      // --useAutoTemplate (main.cc:199), --autoTemplateCentral (not a reference option)
   double sigma = 12.0, low_intensity_cutoff = 0.01;                      // main.cc:172, 181
   bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
+  std::string reference_name;                                             // --referenceVolume (main.cc:207; takes effect here)
   std::string report_name, sim_prefix;                                   // --sliceReport, --simulatedStacks (not reference options)
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
   // ---- options (main.cc:164-211) ---------------------------------------------------------------------
@@ -108,6 +113,7 @@ int main(int argc, char **argv) {
     else if (o == "--dryRun") dry_run = true;
     else if (o == "--sliceReport") report_name = one();                   // not reference options: the reference's main() never calls SlicesInfo / SimulateStacks
     else if (o == "--simulatedStacks") sim_prefix = one();
+    else if (o == "--referenceVolume") reference_name = one();            // main.cc:207, 253-258: read there and (outside the T1 experiment) never used
     else if (o == "--useCPUReg" || o == "--disableBiasCorrection" || o == "--debug_gpu") {}
     else if (o == "-d" || o == "--devices") { std::vector<std::string> v; multi(v); for (auto &s : v) devices.push_back(atoi(s.c_str())); }
     else if (o == "-h" || o == "--help") {
@@ -117,7 +123,14 @@ int main(int argc, char **argv) {
              "       [--rec_iterations_first 4] [--rec_iterations_last 13] [--packages p_1 ..] [--useGPUReg] [--no_registration] [--tfolder dir] [--sfolder dir]\n"
              "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n"
              "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
-             "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix]\n"
+             "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix] [--referenceVolume file]\n"
+             "  --referenceVolume <file> deviation from the reference (the reference reads the file and, outside its T1 experiment, never uses\n"
+             "                          its voxels): use the volume as the initial reconstruction.  It must be in the template stack's world\n"
+             "                          space, roughly aligned, like every stack given with -t; its grid (voxel size, field of view, axis\n"
+             "                          order, oblique axes) is free: it is resampled onto the reconstruction grid (values <= -1 are background),\n"
+             "                          masked, and scaled to --average unless --no_intensity_matching 0.  The first iteration then registers\n"
+             "                          the slices (and packages) against it instead of reconstructing from unregistered slices; the volume\n"
+             "                          itself is overwritten by the first reconstruction.  Only the first volume of a 4D file is used.\n"
              "  --sliceReport <file>    deviation from the reference, which has SlicesInfo and never calls it: after the volume is written,\n"
              "                          project it into the slices once more and write one tab-separated row per slice, in slice order:\n"
              "                          SlicesInfo's stack_index included excluded outside weight scale Translation{X,Y,Z} Rotation{X,Y,Z},\n"
@@ -151,6 +164,7 @@ int main(int argc, char **argv) {
   if (!sim_prefix.empty() && !sfolder.empty())
     die("--simulatedStacks puts every simulated slice back into the stack it was cut from; with --sfolder the slices come from files of "
         "their own and belong to no stack: use --sliceReport, or drop --sfolder");
+  if (dry_run && !reference_name.empty()) die("--dryRun makes no engine context and cannot resample a volume: drop --referenceVolume");
   if (use_nmi && use_gpu_reg)
     die("--useNMI selects normalised mutual information for the IRTK registration; the reference's GPU registration (--useGPUReg) is "
         "cross-correlation only: use one or the other");
@@ -458,9 +472,38 @@ int main(int argc, char **argv) {
   }
 
   clk.mark("slices, engine set-up, upload");
+  const bool have_reference = !reference_name.empty();
+  if (have_reference) {
+    // The seed on its own grid -> the reconstruction grid, on rank 0's device: once to learn its mean inside the mask, once more to
+    // scale and install it; the other ranks get the result.  -1 is this program's own background (MaskVolume) and must not bleed in.
+    svr_image_attr ra;
+    float *rdata = nullptr;
+    int rnt = 1;
+    char e[256] = {0};
+    if (svr_nifti_read(reference_name.c_str(), &ra, &rnt, &rdata, e)) die(reference_name + ": " + e);   // (4D: the first volume comes first)
+    const M4 m = mul(world_to_image(ra), image_to_world(tattr));
+    const uint32_t rsize[3] = {(uint32_t)ra.nx, (uint32_t)ra.ny, (uint32_t)ra.nz};
+    double rs[5];
+    ENGR(0, svr_resample_to_reconstruction(ctx, rsize, rdata, m.m, -1.0f, 0, 1.0f, nullptr, rs));
+    if (rs[0] == 0) die("--referenceVolume does not overlap the mask");
+    const double rmean = rs[1] / rs[0];
+    // the stacks were matched to --average, and the default registration casts the volume to short: a seed in [0, 1] would have two levels
+    double rscale = 1.0;
+    if (!no_matching) {
+      if (!(rmean > 0)) die("--referenceVolume: the mean inside the mask is " + std::to_string(rmean) + ", it cannot be scaled to --average");
+      rscale = average / rmean;
+    }
+    std::vector<float> seed(nr > 1 ? (size_t)tattr.nx * tattr.ny * tattr.nz : 0);
+    ENGR(0, svr_resample_to_reconstruction(ctx, rsize, rdata, m.m, -1.0f, SVR_RESAMPLE_INSTALL | (no_matching ? 0 : SVR_RESAMPLE_SCALE), (float)rscale,
+                                           nr > 1 ? seed.data() : nullptr, rs));
+    svr_free(rdata);
+    for (int r = 1; r < nr; ++r) ENGR(r, svr_update_reconstructed(ctxs[r], vsize, seed.data()));
+    fprintf(stderr, "reference volume: n=%.0f mean=%.9g min=%.9g max=%.9g scale=%.9g\n", rs[0], rmean, rs[3], rs[4], rscale);
+    clk.mark("reference volume");
+  }
   // ---- registration-reconstruction loop (main.cc:816-1237) ---------------------------------------------
   for (int it = 0; it < iterations; ++it) {
-    bool slice_reg = it > 0 && !no_registration;
+    bool slice_reg = (it > 0 || have_reference) && !no_registration;      // main.cc:826
     if (slice_reg && !packages.empty() && it <= iterations * (levels - 1) / levels && it < iterations - 1) {
       // packages first (main.cc:832-864): plain, even/odd, even/odd halves; from iteration 4 on also the slices
       std::vector<svr_image_attr> at(n);

@@ -1247,6 +1247,8 @@ struct svr_ctx {
   float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
   double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
   double *d_qual_partial = nullptr, *d_qual_sums = nullptr;   // svr_slice_quality (svr_quality.inc): likewise
+  float *d_seed_src = nullptr, *d_seed_out = nullptr;          // svr_resample_to_reconstruction (svr_seed.inc): likewise
+  double *d_seed_partial = nullptr;
   int last_quality_chunks = -1;          // chunks per slice of the last svr_slice_quality (read-only option "quality_chunks"; -1 = not launched yet)
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
   uint32_t reg_vx = 0, reg_vy = 0, reg_vz = 0;
@@ -1324,7 +1326,7 @@ void cell_free(CellState *c);
 // The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
 // of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  The buffers of
 // svr_stack_motion (svr_motion.inc) cache nothing between calls -- they are freed before the call returns -- and have no line there;
-// nor have those of svr_slice_quality (svr_quality.inc).
+// nor have those of svr_slice_quality (svr_quality.inc) and svr_resample_to_reconstruction (svr_seed.inc).
 enum Change : unsigned {
   CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
   CH_TAPS = 1u << 1,              // new slice constants, generatePSFVolume: the table and the cell lists
@@ -2292,6 +2294,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
   free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
   free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums);
+  free_dev(ctx->d_seed_src); free_dev(ctx->d_seed_out); free_dev(ctx->d_seed_partial);
   free_dev(ctx->d_coeff); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff_order);
   reg_free(ctx->reg);
   cell_free(ctx->cell);
@@ -2600,6 +2603,7 @@ int svr_update_reconstructed(svr_ctx *ctx, const uint32_t size[3], const float *
   if ((size_t)size[0] * size[1] * size[2] != ctx->nv) return fail(ctx, SVR_E_ARG, "size mismatch");
   HIPCHK(hipMemcpyAsync(ctx->recon(), data, ctx->nv * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  invalidate(ctx, CH_VOLUME_VALUES);                       // (as svr_debug_set(SVR_BUF_RECONSTRUCTED): the caller's volume need not be zero outside the mask)
   return SVR_OK;
 }
 
@@ -3876,4 +3880,5 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 #include "svr_nmi.inc"
 #include "svr_motion.inc"
 #include "svr_quality.inc"
+#include "svr_seed.inc"
 #include "svr_em.inc"

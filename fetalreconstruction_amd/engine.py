@@ -24,6 +24,7 @@ BUF_BIAS_VOLUME, BUF_SMOOTH_MASK = 5, 6
 BUF_SLICES, BUF_WEIGHTS, BUF_SIMSLICES, BUF_SIMWEIGHTS, BUF_PSF_SUMS, BUF_BIAS = 10, 11, 12, 13, 14, 15
 BUF_SIMINSIDE, BUF_VOXEL_COUNT = 20, 21
 T_BACKPROJECT, T_FORWARD, T_GAUSS, T_REGULARIZE, T_ESTEP, T_MSTEP, T_SCALE, T_REGISTER = range(8)
+RESAMPLE_INSTALL, RESAMPLE_SCALE = 1, 2                # SVR_RESAMPLE_* (include/svr_hip.h)
 TIMER_NAMES = ("backproject", "forward", "gauss", "regularize", "estep", "mstep", "scale", "register", "allreduce", "exchange_host", "coeff_build", "reduce_scatter", "allgather",
                "backproject_table", "forward_table", "forward_store", "backproject_store")
 
@@ -40,7 +41,7 @@ EXPORTS = [
     "svr_superresolution_backproject", "svr_superresolution_update", "svr_robust_statistics_sums",
     "svr_mstep_sums", "svr_scale_volume_sums", "svr_scale_volume_apply", "svr_timer_get",
     "svr_unit_counts", "svr_fallbacks", "svr_clock_probe", "svr_slice_em_setup", "svr_slice_em_set_state", "svr_mstep_estep_device", "svr_slice_em_run", "svr_slice_em_apply_weights", "svr_slice_em_fetch", "svr_slice_em_set_patch_form", "svr_cell_stats", "svr_pair_pack", "svr_pair_unpack", "svr_timer_reset", "svr_timer_enable", "svr_timer_begin", "svr_timer_end", "svr_timer_add", "svr_counters", "svr_get_stream", "svr_device", "svr_device_count", "svr_combine_weights", "svr_update_stack_sizes", "svr_ncc_set_targets", "svr_ncc_set_source",
-    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
+    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_pvr_cc_patches", "svr_pvr_register_patches",
@@ -406,6 +407,24 @@ class Reconstruction:
         out = np.zeros((self.sgrid[0], 10), np.float64)
         self._ck(self._lib.svr_slice_quality(self._h, _p(out)))
         return out
+
+    def resample_to_reconstruction(self, src, src_from_recon, padding=-1.0, install=False, scale=None, want_volume=True):
+        """svr_resample_to_reconstruction: src float32 [nz][ny][nx] on any grid, src_from_recon = source world-to-image x reconstruction
+        image-to-world (float64, 3x4 or 4x4) -> (the volume on the reconstruction grid [vz][vy][vx] or None, stats float64 [5] =
+        {n, sum v, sum v^2, min, max} of the valid voxels before scaling).  scale: multiply the valid voxels; install: the result becomes
+        the reconstructed volume (include/svr_hip.h)."""
+        if not self.vsize:
+            raise SvrError("resample_to_reconstruction: InitReconstructionVolume first")
+        a = _f32(src)
+        if a.ndim != 3:
+            raise SvrError("resample_to_reconstruction: a [nz][ny][nx] array expected")
+        m = np.ascontiguousarray(np.asarray(src_from_recon, np.float64).reshape(-1, 4)[:3])
+        out = np.empty(self.vsize[::-1], np.float32) if want_volume else None
+        stats = np.zeros(5, np.float64)
+        flags = (RESAMPLE_INSTALL if install else 0) | (RESAMPLE_SCALE if scale is not None else 0)
+        self._ck(self._lib.svr_resample_to_reconstruction(self._h, _u3(a.shape[::-1]), _p(a), _p(m), C.c_float(padding), int(flags),
+                                                          C.c_float(1.0 if scale is None else scale), None if out is None else _p(out), _p(stats)))
+        return out, stats
 
     # ---- GPU slice-to-volume registration (RC.cuh:326-338) ------------------------------------
     def initRegStorageVolumes(self, W, H, ns, dim=(1.0, 1.0, 1.0)):

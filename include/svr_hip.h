@@ -326,6 +326,24 @@ int svr_stack_motion(svr_ctx *ctx, const float *slices, int m, int n, double *si
  * slice grid alone and is readable afterwards as the option "quality_chunks".  Nothing of the call stays on the device. */
 #define SVR_SLICE_QUALITY_SUMS 10
 int svr_slice_quality(svr_ctx *ctx, double *sums /* [ns][SVR_SLICE_QUALITY_SUMS] */);
+/* A volume on ANY grid brought onto the context's reconstruction grid (csrc/svr_seed.inc; the command line's --referenceVolume, which
+ * the reference reads -- reconstruction.cc:253-258 -- and, outside its T1 experiment, never uses).  src: host memory, src_size = {nx, ny,
+ * nz}, x fastest.  src_from_recon: rows 0..2 of  source world-to-image x reconstruction image-to-world,  composed by the caller in double;
+ * target voxel (i, j, k) reads the source at p = M (i, j, k, 1), evaluated in double.  Trilinear with padding: base = floor(p), a
+ * neighbour takes part if it lies inside the source grid and its value is > padding; with W the sum of the weights that take part the
+ * result is sum(w v) / W if W >= 0.5 and `padding` otherwise, accumulated in double and rounded to float once.  Where the context's mask
+ * is 0 the result is -1 (what svr_mask_volume leaves); without a mask every voxel counts as inside.
+ * stats = {n, sum v, sum v^2, min v, max v} over the valid voxels (inside the mask, W >= 0.5), v = the float result BEFORE any
+ *   scaling, in double; n = 0: sums 0, min = +infinity, max = -infinity.  No atomics, a fixed order: the same bits on every call.
+ * flags: SVR_RESAMPLE_SCALE multiplies the valid voxels by `scale` (float) in a second pass, padding and masked voxels stay;
+ *   SVR_RESAMPLE_INSTALL makes the result the context's reconstructed volume (as svr_update_reconstructed would).
+ * out_or_null: the result on the reconstruction grid (scaled, when asked for).  Refused with a message: a null src / matrix / stats, a
+ * size of zero, a source of more than 2^31 - 1 voxels, a matrix, padding or scale that is not finite, an unknown flag, no
+ * reconstruction volume.  Nothing of the call stays on the device. */
+#define SVR_RESAMPLE_INSTALL 1
+#define SVR_RESAMPLE_SCALE 2
+int svr_resample_to_reconstruction(svr_ctx *ctx, const uint32_t src_size[3], const float *src, const double src_from_recon[12], float padding,
+                                   int flags, float scale, float *out_or_null, double stats[5]);
 
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::
