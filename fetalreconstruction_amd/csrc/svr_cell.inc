@@ -602,11 +602,7 @@ void back_cell_kernel(PsfArgs a, CellArgs ca, uint32_t b0) {
               const int j = valid ? __builtin_ctz(ml) : 0;
               ml &= ml - 1u;
               u = fetch(j);
-              if (valid) {
-                const float4 *src = a.coeff + ((size_t)(uint32_t)u.pid * NS + (size_t)(P - u.cz + NC)) * (NS / 4 * 16) + (y < NS ? y : 0);
-#pragma unroll
-                for (int q = 0; q < NS / 4; ++q) dst[q] = load_stream(src + q * 16);
-              }
+              if (valid) coeff_load_row<NS>(coeff_row<NS>(a.coeff, (uint32_t)u.pid, P - u.cz + NC, y < NS ? y : 0), dst);
             };
 #pragma unroll
             for (int r3 = 0; r3 < RING; ++r3) request(ru[r3], rv[r3], ring[r3]);
@@ -666,11 +662,7 @@ void back_cell_kernel(PsfArgs a, CellArgs ca, uint32_t b0) {
               if (COEFF == 3) {
                 // the pass that evaluates writes the coefficient table (fwd_cell_kernel<.., 3> does the same; whichever PSF pass comes first after a
                 // new slice geometry -- pass 2 of the Gaussian reconstruction in the reconstruction loop, the scatter in bench.py's steps)
-                if (valid && y < NS) {
-                  float4 *dstp = const_cast<float4 *>(a.coeff) + ((size_t)(uint32_t)u.pid * NS + (size_t)(P - u.cz + NC)) * (NS / 4 * 16) + y;
-#pragma unroll
-                  for (int q = 0; q < NS / 4; ++q) store_stream(dstp + q * 16, out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
-                }
+                if (valid && y < NS) coeff_store_row<NS>(coeff_row<NS>(a.coeff, (uint32_t)u.pid, P - u.cz + NC, y), out);
               }
               // all NS x positions are inside the box by construction: unconditional read-add-write (skipped taps add 0);
               // the reads first, together, then the sums, then the writes.  (Issued before the epsilon-walk instead of after it --
@@ -1101,10 +1093,8 @@ void fwd_cell_kernel(PsfArgs a, CellArgs ca, const float *gf, f2 *part, uint32_t
             const int pid = __shfl(pid0, src, 64), czk = __shfl((int)r0.cz, src, 64);
             // (lanes without a unit read the table's first bytes into their part of the stage: the loads are issued whatever the lanes hold, so
             // that the wavefront's count of operations in flight does not depend on them)
-            const float4 *srcp = vi ? a.coeff + ((size_t)(uint32_t)pid * NS + (size_t)(P - czk + NC)) * (HQ * 16) + y : a.coeff + lane;
-            const uint32_t dst = stage_lds + (uint32_t)s_issue * (HQ * 1024u);
-#pragma unroll
-            for (int q = 0; q < HQ; ++q) glds16(srcp + q * 16, dst + q * 1024u);
+            const float4 *srcp = vi ? coeff_row<NS>(a.coeff, (uint32_t)pid, P - czk + NC, y) : a.coeff + lane;
+            coeff_dma_row<NS>(srcp, stage_lds + (uint32_t)s_issue * CoeffLayout<NS>::STAGE_BYTES);
             s_issue = s_issue + 1 == DD ? 0 : s_issue + 1;
             return true;
           };
@@ -1131,11 +1121,11 @@ void fwd_cell_kernel(PsfArgs a, CellArgs ca, const float *gf, f2 *part, uint32_t
               // this step's stage: DD - 1 younger steps of HQ loads each stay in flight (or, at the end of the lists, everything is waited for).
               // The wavefront's own stores (one per step, younger than the loads waited for) only make the count stricter: vmcnt is in order.
               if (ahead) glds_wait<(DD - 1) * HQ>(); else glds_wait<0>();
-              const float4 *st = stage + s_use * (HQ * 64);
+              const float4 *st = stage + s_use * (HQ * CoeffLayout<NS>::STAGE_QUAD_F4);
               s_use = s_use + 1 == DD ? 0 : s_use + 1;
 #pragma unroll
               for (int qq = 0; qq < HQ; ++qq) {
-                const float4 c = st[qq * 64];
+                const float4 c = st[qq * CoeffLayout<NS>::STAGE_QUAD_F4];
                 acc = fma2(bc2(c.x), q[4 * qq], acc);
                 acc = fma2(bc2(c.y), q[4 * qq + 1], acc);
                 acc = fma2(bc2(c.z), q[4 * qq + 2], acc);
@@ -1157,11 +1147,7 @@ void fwd_cell_kernel(PsfArgs a, CellArgs ca, const float *gf, f2 *part, uint32_t
             const int j = valid ? __builtin_ctz(ml) : 0;
             ml &= ml - 1u;
             u = fetch(j);
-            if (valid) {
-              const float4 *src = a.coeff + ((size_t)(uint32_t)u.pid * NS + (size_t)(P - u.cz + NC)) * (NS / 4 * 16) + (y < NS ? y : 0);
-#pragma unroll
-              for (int q = 0; q < NS / 4; ++q) dst[q] = load_stream(src + q * 16);
-            }
+            if (valid) coeff_load_row<NS>(coeff_row<NS>(a.coeff, (uint32_t)u.pid, P - u.cz + NC, y < NS ? y : 0), dst);
           };
 #pragma unroll
           for (int r3 = 0; r3 < RING; ++r3) request(ru[r3], rv[r3], ring[r3]);
@@ -1214,11 +1200,7 @@ void fwd_cell_kernel(PsfArgs a, CellArgs ca, const float *gf, f2 *part, uint32_t
             // Round 6: the pass that evaluates WRITES the table (what k_coeff_build writes: the unit's taps as [tap quad][row] float4): the first
             // gather after a new slice geometry is CoeffInit (irtkReconstruction::CoeffInit, RG.cc:2617-2673), and the evaluation it needs anyway
             // is the table's -- no second evaluation of every tap, the stores leave while the next unit is evaluated
-            if (valid && y < NS) {
-              float4 *dstp = const_cast<float4 *>(a.coeff) + ((size_t)(uint32_t)u.pid * NS + (size_t)(P - u.cz + NC)) * (NS / 4 * 16) + y;
-#pragma unroll
-              for (int q = 0; q < NS / 4; ++q) store_stream(dstp + q * 16, out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
-            }
+            if (valid && y < NS) coeff_store_row<NS>(coeff_row<NS>(a.coeff, (uint32_t)u.pid, P - u.cz + NC, y), out);
           }
           f2 acc = (f2){0.0f, 0.0f};
           double accd = 0.0;
@@ -1861,7 +1843,7 @@ int launch_cell_gather(svr_ctx *ctx, CellState &cs, const PsfArgs &a, bool store
     cs.gf_valid = !a.flag;
   }
   const bool dma = a.coeff && !ctx->pvr && !store;         // support 16: the table's rows land in the LDS (COEFF == 2)
-  const size_t lds = (size_t)ca.PP * sizeof(f2) + (dma ? 16 + (size_t)SVR_CELL_DMA_DEPTH * 4096 : 0);
+  const size_t lds = (size_t)ca.PP * sizeof(f2) + (dma ? 16 + (size_t)SVR_CELL_DMA_DEPTH * CoeffLayout<PSF_SUPPORT>::STAGE_BYTES : 0);
   r = in_pieces(ca.nents, 64, [&](uint32_t off, uint32_t cnt) {
     if (ctx->pvr && a.coeff) hipLaunchKernelGGL((fwd_cell_kernel<PVR_N, true, 1>), dim3(cnt), dim3(64), lds, ctx->stream, a, ca, cs.d_gf, cs.d_part, (uint32_t)cs.n_sorted, off);
     else if (ctx->pvr) hipLaunchKernelGGL((fwd_cell_kernel<PVR_N, true>), dim3(cnt), dim3(64), lds, ctx->stream, a, ca, cs.d_gf, cs.d_part, (uint32_t)cs.n_sorted, off);

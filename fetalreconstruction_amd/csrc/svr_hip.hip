@@ -801,14 +801,12 @@ __device__ __forceinline__ void store_stream(float4 *p, float a, float b, float 
   *p = make_float4(a, b, c, d);
 #endif
 }
-// The coefficient table (svr_ctx::d_coeff): one wavefront per PSF pixel, four of its NS units per pass -- slot = unit,
-// lane = row, exactly the decomposition of the scatter and the gather.  A unit's NS x NS taps (skipped ones as -0.0f) go
-// out as NS/4 x 16 float4: [tap quad q][row y], so that the 16 lanes of a slot write and later read 256 contiguous bytes
-// per instruction (SVR: 16 units of 1 KiB per pixel; PVR, support 12: 12 units of 768 bytes).  Dead units (unit_is_dead) are not stored: the kernels evaluate their first taps themselves.
+#include "svr_coeff.h"     // the coefficient table's layout: CoeffLayout, coeff_row and the row loads / stores on the three functions above
+
+// The coefficient table's writer: one wavefront per pixel, four of its NS units per pass -- slot = unit, lane = row.
 template <int NS, bool PVR>
 __global__ __launch_bounds__(256) void k_coeff_build(PsfArgs a, float4 *coeff, uint32_t *coeff_id, uint32_t base) {
-  constexpr int NC = (NS - 1) / 2, QUADS = NS / 4;
-  static_assert(NS % 4 == 0 && NS <= 16, "tap quads, one row per lane of a 16-lane slot");
+  constexpr int NC = (NS - 1) / 2;
   const uint32_t wl = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (wl >= a.n) return;
   const int lane = threadIdx.x & 63;
@@ -832,11 +830,7 @@ __global__ __launch_bounds__(256) void k_coeff_build(PsfArgs a, float4 *coeff, u
     if (__all(dead)) continue;
     float out[NS];
     eval_row_t<NS, PVR, true>(RC, P.bx, P.by, P.bz, swap ? fu : fyl, swap ? fyl : fu, out);
-    if (!dead && u < NS && y < NS) {
-      float4 *dst = coeff + ((size_t)w * NS + u) * (QUADS * 16) + y;
-#pragma unroll
-      for (int q = 0; q < QUADS; ++q) store_stream(dst + q * 16, out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
-    }
+    if (!dead && u < NS && y < NS) coeff_store_row<NS>(coeff_row<NS>(coeff, w, u, y), out);
   }
 }
 
@@ -1698,8 +1692,7 @@ int coeff_prepare(svr_ctx *ctx, const uint32_t **list) {
     free_dev(ctx->d_coeff);
     ctx->coeff_cap = 0;
     size_t fr = 0, tot = 0;
-    const size_t per_px = ctx->pvr ? (size_t)PVR_N * (PVR_N / 4) * 16 : (size_t)PSF_SUPPORT * (PSF_SUPPORT / 4) * 16;   // float4 per pixel
-    const size_t bytes = npx * per_px * sizeof(float4);
+    const size_t bytes = npx * (ctx->pvr ? CoeffLayout<PVR_N>::PIXEL_BYTES : CoeffLayout<PSF_SUPPORT>::PIXEL_BYTES);
     const char *cap_gb = getenv("SVR_COEFF_MAX_GB");     // optional ceiling on the table (GiB): a deployment knob, and how the tests reach the fallback
     const bool over = cap_gb && (double)bytes > atof(cap_gb) * 1073741824.0;
     // the bias buffers are allocated before the first pass (svr_set_flags / ready); any still missing count in the headroom

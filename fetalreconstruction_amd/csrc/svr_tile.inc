@@ -626,9 +626,7 @@ void back_wave_kernel(PsfArgs a, TileArgs ta, int groups, uint32_t *fallback_til
         float4 ring[3][NS / 4];
         auto request = [&](int i, float4 (&dst)[NS / 4]) {
           const int k1 = sh_list[slot][i];
-          const float4 *src = a.coeff + ((size_t)sh_pid[k1] * NS + (size_t)(P - sh_px[k1].cz + NC)) * (NS / 4 * 16) + (y < NS ? y : 0);
-#pragma unroll
-          for (int q = 0; q < NS / 4; ++q) dst[q] = load_stream(src + q * 16);
+          coeff_load_row<NS>(coeff_row<NS>(a.coeff, sh_pid[k1], P - sh_px[k1].cz + NC, y < NS ? y : 0), dst);
         };
 #pragma unroll
         for (int r3 = 0; r3 < 3; ++r3) if (r3 < mynl) request(r3, ring[r3]);
@@ -646,7 +644,7 @@ void back_wave_kernel(PsfArgs a, TileArgs ta, int groups, uint32_t *fallback_til
               for (int x = 0; x < NS; ++x) acc[x] = pb[rb + x];
               float out[NS];
 #pragma unroll
-              for (int q = 0; q < NS / 4; ++q) { out[4 * q] = ring[r3][q].x; out[4 * q + 1] = ring[r3][q].y; out[4 * q + 2] = ring[r3][q].z; out[4 * q + 3] = ring[r3][q].w; }
+              for (int x = 0; x < NS; ++x) out[x] = coeff_tap<NS>(ring[r3], x);
               if (i + 3 < mynl) request(i + 3, ring[r3]);
               add_unit(R, out, acc, rowok, rb);
             }
@@ -974,12 +972,10 @@ __global__ __launch_bounds__(FWDU_WAVES * 64) void fwd_unit_kernel(PsfArgs a, Ti
       // the unit's taps from the coefficient table (what eval_row_t returns, written by k_coeff_build).  Sixteen
       // wavefronts per CU keep enough of these 1 KiB reads in flight; a three-round prefetch ring was measured and lost
       // (3.55 against 3.43 ms)
-      const float4 *src = a.coeff + ((size_t)sh_pid[k] * NS + (size_t)u) * (NS / 4 * 16) + (y < NS ? y : 0);
+      float4 row[NS / 4];
+      coeff_load_row<NS>(coeff_row<NS>(a.coeff, sh_pid[k], u, y < NS ? y : 0), row);
 #pragma unroll
-      for (int q = 0; q < NS / 4; ++q) {
-        const float4 c = load_stream(src + q * 16);
-        out[4 * q] = c.x; out[4 * q + 1] = c.y; out[4 * q + 2] = c.z; out[4 * q + 3] = c.w;
-      }
+      for (int x = 0; x < NS; ++x) out[x] = coeff_tap<NS>(row, x);
     } else {
       eval_row_t<NS, PVR, true>(RC, R.bx, R.by, R.bz, swap ? fu : fyl, swap ? fyl : fu, out);
     }
