@@ -1027,6 +1027,32 @@ int svrh_irtk_blur_with_padding(const svr_image_attr *attr, int16_t *data, doubl
   return 0;
 }
 
+int svrh_irtk_blur_kernel(double sigma, double voxel, double *out_or_null, int capacity) {
+  const std::vector<double> ker = blur_kernel(sigma, voxel);
+  if (out_or_null) {
+    if ((int)ker.size() > capacity) return -1;
+    memcpy(out_or_null, ker.data(), sizeof(double) * ker.size());
+  }
+  return (int)ker.size();
+}
+
+int svrh_irtk_prepare_level(const svr_image_attr *attr, const int16_t *data, double blur, const double res[3], const double res0[3], int level,
+                            int padding, svr_image_attr *out_attr, int16_t *out_or_null, long capacity, int *min_out, int *max_out,
+                            char err[256]) {
+  if (!attr || !data || !res || !res0 || !out_attr) { set_err(err, "svrh_irtk_prepare_level: bad arguments"); return 2; }
+  Vol<short> v, o;
+  v.a = *attr;
+  v.d.assign(data, data + v.n());
+  std::string e;
+  if (int rc = prepare_level(v, blur, res, res0, level, (short)padding, o, e, min_out, max_out)) { set_err(err, e); return rc; }
+  *out_attr = o.a;
+  if (out_or_null) {
+    if ((long)o.d.size() > capacity) { set_err(err, "svrh_irtk_prepare_level: the output does not fit"); return 2; }
+    memcpy(out_or_null, o.d.data(), sizeof(int16_t) * o.d.size());
+  }
+  return 0;
+}
+
 int svrh_irtk_number_of_bins(int16_t *data_or_null, long n, int min, int max, int *width_or_null) {
   int width = 1;
   const int nbins = nmi_number_of_bins(min, max, width);

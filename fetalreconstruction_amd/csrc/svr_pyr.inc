@@ -5,7 +5,9 @@
 // levels.  csrc/irtk_reg.cpp restates that on the host (blur_with_padding, resample_with_padding, prepare_level) and stays
 // the definition: the kernels below do the same double arithmetic operation for operation (the library is built with
 // -ffp-contract=off, double division and the conversions are IEEE on gfx950), so a level made here is the level made
-// there bit for bit (tests/test_irtk_registration.py::test_device_pyramid_is_the_host_pyramid).  What it buys: the host of
+// there bit for bit (every voxel of every level against an independent reference: tests/test_pyramid_gpu.py, the host code
+// against the same reference: tests/test_pyramid_ref.py; end to end: tests/test_irtk_registration.py::
+// test_device_pyramid_is_the_host_pyramid).  What it buys: the host of
 // a gpurun box has 16 CPUs' worth of quota -- the pyramids of 512 slices of 256 x 256 took 0.5 s of a 0.87 s pass, the
 // pyramid of a 400 x 400 x 320 source 0.5 s of a 1.4 s pass -- and the levels no longer travel host -> device.
 
@@ -256,6 +258,29 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
     if (min_out) min_out[i] = mm[i];
     if (max_out) max_out[i] = mm[n_images + i];
   }
+  return SVR_OK;
+}
+
+// what svr_ncc_evaluate reads, copied to the host for the tests: which 0 = the source, short [vz][vy][vx], dims = {vx, vy, vz};
+// 1 = the target planes, short [n][ty][tx], dims = {tx, ty, n}.  Reads only: no buffer, size or cached state changes.
+int svr_ncc_get(svr_ctx *ctx, int which, int dims[3], int16_t *out_or_null, size_t count) {
+  SVR_ENTER(ctx);
+  if (!ctx || !dims || which < 0 || which > 1) return SVR_E_ARG;
+  const short *src;
+  if (which == 0) {
+    NEED(ctx->d_reg_source, "no source: svr_ncc_set_source or svr_pyr_level (slot 0) first");
+    dims[0] = (int)ctx->reg_vx; dims[1] = (int)ctx->reg_vy; dims[2] = (int)ctx->reg_vz;
+    src = ctx->d_reg_source;
+  } else {
+    NEED(ctx->d_reg_targets, "no targets: svr_ncc_set_targets or svr_ncc_alloc_targets first");
+    dims[0] = ctx->reg_tx; dims[1] = ctx->reg_ty; dims[2] = ctx->reg_n;
+    src = ctx->d_reg_targets;
+  }
+  if (!out_or_null) return SVR_OK;
+  const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+  if (count != n) return fail(ctx, SVR_E_ARG, "svr_ncc_get: size mismatch");
+  HIPCHK(hipMemcpyAsync(out_or_null, src, n * sizeof(short), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
 

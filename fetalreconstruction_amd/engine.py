@@ -41,7 +41,7 @@ EXPORTS = [
     "svr_superresolution_backproject", "svr_superresolution_update", "svr_robust_statistics_sums",
     "svr_mstep_sums", "svr_scale_volume_sums", "svr_scale_volume_apply", "svr_timer_get",
     "svr_unit_counts", "svr_fallbacks", "svr_clock_probe", "svr_slice_em_setup", "svr_slice_em_set_state", "svr_mstep_estep_device", "svr_slice_em_run", "svr_slice_em_apply_weights", "svr_slice_em_fetch", "svr_slice_em_set_patch_form", "svr_cell_stats", "svr_pair_pack", "svr_pair_unpack", "svr_timer_reset", "svr_timer_enable", "svr_timer_begin", "svr_timer_end", "svr_timer_add", "svr_counters", "svr_get_stream", "svr_device", "svr_device_count", "svr_combine_weights", "svr_update_stack_sizes", "svr_ncc_set_targets", "svr_ncc_set_source",
-    "svr_ncc_evaluate", "svr_ncc_alloc_targets", "svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
+    "svr_ncc_evaluate", "svr_ncc_get", "svr_ncc_alloc_targets","svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_pvr_cc_patches", "svr_pvr_register_patches",
@@ -52,6 +52,11 @@ EXPORTS = [
 
 class SvrError(RuntimeError):
     pass
+
+
+class _PyrImage(C.Structure):
+    """struct svr_pyr_image (include/svr_hip.h)"""
+    _fields_ = [("i2w_out", C.c_double * 12), ("w2i_in", C.c_double * 12), ("pad", C.c_int)]
 
 
 _lib = None
@@ -367,6 +372,52 @@ class Reconstruction:
         ncc = np.zeros(len(idx), np.float64)
         self._ck(self._lib.svr_ncc_evaluate(self._h, len(idx), _p(idx), _p(m), _p(sums), _p(ncc)))
         return ncc, sums
+
+    # ---- the image pyramid of that registration on the device (csrc/svr_pyr.inc) ------------------------------------------
+    def ncc_alloc_targets(self, n, tx, ty):
+        """n target planes of ty x tx, all -1, for pyr_level(slot 1) to write into"""
+        self._ck(self._lib.svr_ncc_alloc_targets(self._h, int(n), int(tx), int(ty)))
+
+    def pyr_upload(self, slot, images):
+        """the unprocessed images of a registration pass: slot 0 the source volume, slot 1 the targets back to back (int16)"""
+        a = np.ascontiguousarray(images, np.int16).reshape(-1)
+        self._ck(self._lib.svr_pyr_upload(self._h, int(slot), _p(a), C.c_size_t(a.size)))
+
+    def pyr_level(self, slot, offset, in_dims, kernels, resample, out_dims, i2w_out, w2i_in, pads, first_plane=0):
+        """svr_pyr_level: one level of len(pads) images of one grid that start at element `offset` of the slot -> (min [n], max [n])
+        int32, the range above each padding before the shift (max < min: none).  in_dims / out_dims: (nx, ny, nz); kernels: the
+        three blur kernels (None or empty = no pass on that axis); i2w_out / w2i_in: per image the 4x4 (or its first three rows) of
+        the level's image-to-world and of the unprocessed grid's world-to-image matrix."""
+        n = len(pads)
+        imgs = (_PyrImage * n)()
+        a = np.asarray(i2w_out, np.float64).reshape(n, -1)[:, :12]
+        b = np.asarray(w2i_in, np.float64).reshape(n, -1)[:, :12]
+        for i in range(n):
+            imgs[i].i2w_out[:] = a[i].tolist()
+            imgs[i].w2i_in[:] = b[i].tolist()
+            imgs[i].pad = int(pads[i])
+        ker = [np.zeros(0) if k is None else np.ascontiguousarray(k, np.float64) for k in kernels]
+        mn, mx = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._ck(self._lib.svr_pyr_level(self._h, int(slot), C.c_size_t(offset), n, (C.c_int * 3)(*[int(v) for v in in_dims]),
+                                         _p(ker[0]) if ker[0].size else None, int(ker[0].size), _p(ker[1]) if ker[1].size else None,
+                                         int(ker[1].size), _p(ker[2]) if ker[2].size else None, int(ker[2].size), int(bool(resample)),
+                                         (C.c_int * 3)(*[int(v) for v in out_dims]), imgs, int(first_plane), _p(mn), _p(mx)))
+        return mn, mx
+
+    def _ncc_get(self, which):
+        dims = (C.c_int * 3)()
+        self._ck(self._lib.svr_ncc_get(self._h, which, dims, None, C.c_size_t(0)))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int16)
+        self._ck(self._lib.svr_ncc_get(self._h, which, dims, _p(out), C.c_size_t(out.size)))
+        return out
+
+    def ncc_get_source(self):
+        """the source svr_ncc_evaluate reads, int16 [vz][vy][vx] (read-only copy)"""
+        return self._ncc_get(0)
+
+    def ncc_get_targets(self):
+        """the whole allocation of target planes svr_ncc_evaluate reads, int16 [n][ty][tx] (read-only copy)"""
+        return self._ncc_get(1)
 
     def nmi_bin_source(self, width):
         """irtkCalculateNumberOfBins' rescaling of the current source, in place (v > 0 -> v // width)"""

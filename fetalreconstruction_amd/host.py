@@ -30,7 +30,7 @@ PVR_HOST_EXPORTS = ["pvrh_create", "pvrh_destroy", "pvrh_last_error", "pvrh_init
                     "pvrh_create_sharded", "pvrh_force_collectives", "pvrh_set_slab_update", "pvrh_sr_iteration", "pvrh_set_unit_order"]      # csrc/pvr_host.cpp
 IRTK_EXPORTS = ["svrh_stack_registrations", "svrh_slice_to_volume_registration", "svrh_package_to_volume", "svrh_irtk_resample_with_padding",
                 "svrh_irtk_blur_with_padding", "svrh_irtk_rigid_parameters", "svrh_slice_to_volume_registration_ex", "svrh_package_to_volume_ex",
-                "svrh_irtk_number_of_bins", "svrh_nmi_sums"]                                                  # csrc/irtk_reg.cpp
+                "svrh_irtk_number_of_bins", "svrh_nmi_sums", "svrh_irtk_blur_kernel", "svrh_irtk_prepare_level"]   # csrc/irtk_reg.cpp
 IO_EXPORTS = ["svr_nifti_read", "svr_nifti_write", "svr_free", "svr_dof_read", "svr_dof_write", "svr_host_threads",
               "svr_slice_quality_derive", "svr_slice_report_write"]      # csrc/svr_io.cpp, declared in svr_host.h
 
@@ -651,6 +651,32 @@ def irtk_blur_with_padding(data, attr, sigma, padding):
     d = np.ascontiguousarray(data, np.int16).copy()
     _reg_lib().svrh_irtk_blur_with_padding(C.byref(ImageAttr.of(attr)), d.ctypes.data_as(C.c_void_p), C.c_double(sigma), int(padding))
     return d
+
+
+def irtk_blur_kernel(sigma, voxel):
+    """the sampled Gaussian of one pass of irtk_blur_with_padding (sigma in mm, voxel size along the axis) -> float64 [2 r + 1]"""
+    lib = _reg_lib()
+    n = lib.svrh_irtk_blur_kernel(C.c_double(sigma), C.c_double(voxel), None, 0)
+    k = np.zeros(n, np.float64)
+    assert lib.svrh_irtk_blur_kernel(C.c_double(sigma), C.c_double(voxel), k.ctypes.data_as(C.c_void_p), n) == n
+    return k
+
+
+def irtk_prepare_level(data, attr, blur, res, res0, level, padding):
+    """irtkImageRegistrationWithPadding::Initialize(level) for one image, the host code (csrc/irtk_reg.cpp prepare_level)
+    -> (int16 [nz'][ny'][nx'], its ImageAttr, min, max): blur, resample when level > 0 or res0 is not the voxel size, the range
+    above `padding` (max < min: no such voxel), values shifted to v - min and everything else -1."""
+    lib = _reg_lib()
+    d = np.ascontiguousarray(data, np.int16)
+    r, r0 = (C.c_double * 3)(*[float(v) for v in res]), (C.c_double * 3)(*[float(v) for v in res0])
+    oa, mn, mx, err = ImageAttr(), C.c_int(0), C.c_int(0), C.create_string_buffer(256)
+    args = (C.byref(ImageAttr.of(attr)), d.ctypes.data_as(C.c_void_p), C.c_double(blur), r, r0, int(level), int(padding), C.byref(oa))
+    if lib.svrh_irtk_prepare_level(*args, None, C.c_long(0), C.byref(mn), C.byref(mx), err):
+        raise _engine.SvrError(f"svrh_irtk_prepare_level: {err.value.decode()}")
+    out = np.zeros((oa.nz, oa.ny, oa.nx), np.int16)
+    if lib.svrh_irtk_prepare_level(*args, out.ctypes.data_as(C.c_void_p), C.c_long(out.size), C.byref(mn), C.byref(mx), err):
+        raise _engine.SvrError(f"svrh_irtk_prepare_level: {err.value.decode()}")
+    return out, oa, mn.value, mx.value
 
 
 def irtk_number_of_bins(mn, mx, data=None):

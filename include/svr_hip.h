@@ -288,6 +288,11 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
 int svr_ncc_set_source(svr_ctx *ctx, const uint32_t size[3], const int16_t *source_or_null);
 int svr_ncc_evaluate(svr_ctx *ctx, int n_eval, const int *target_index, const double *matrices,
                      int64_t *sums6_or_null, double *ncc_or_null);
+/* Read-back of what svr_ncc_evaluate reads, for the tests that look at a level (tests/test_pyramid_gpu.py).  which 0: the
+ * source, short [vz][vy][vx], dims = {vx, vy, vz}; which 1: the whole allocation of target planes, short [n][ty][tx],
+ * dims = {tx, ty, n}.  out_or_null NULL returns the dims only; otherwise count must be their product.  Fails with a message
+ * (SVR_E_STATE) while the buffer does not exist.  Read-only: it changes no buffer and invalidates nothing. */
+int svr_ncc_get(svr_ctx *ctx, int which, int dims[3], int16_t *out_or_null, size_t count);
 /* Normalised mutual information of the same registration (csrc/svr_nmi.inc; the reference's --useNMI, which IRTK evaluates with
  * irtkNormalisedMutualInformationSimilarityMetric over irtkHistogram_2D: IRRWP.cc:534-610, H2D.cc:443-623).  The targets and
  * the source are the ones svr_ncc_evaluate reads (svr_ncc_set_targets / svr_ncc_alloc_targets + svr_pyr_level, svr_ncc_set_source

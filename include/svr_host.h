@@ -272,6 +272,16 @@ double svrh_nmi_sums(const uint32_t *hist64, int target_nbins, int source_nbins,
 int svrh_irtk_resample_with_padding(const svr_image_attr *attr, const int16_t *data, double rx, double ry, double rz, int padding,
                                     svr_image_attr *out_attr, int16_t *out_or_null, long capacity);
 int svrh_irtk_blur_with_padding(const svr_image_attr *attr, int16_t *data, double sigma, int padding);
+/* the sampled Gaussian of one pass of that blur (sigma in mm, voxel = the voxel size along the axis): returns its (odd) number
+ * of taps and writes them when out_or_null holds `capacity` >= that many doubles (-1 when it does not) */
+int svrh_irtk_blur_kernel(double sigma, double voxel, double *out_or_null, int capacity);
+/* irtkImageRegistrationWithPadding::Initialize(level) for one image, the host definition that svr_pyr_level restates: blur
+ * (sigma `blur` mm, none when 0), resample to res[3] when level > 0 or res0[3] is not the image's voxel size, the range
+ * [*min_out, *max_out] of the values above `padding` (max < min: none), and the shift to v - min / -1.  out_or_null NULL gives
+ * the attributes and the range only.  Returns 1 with a message when the range exceeds 32767, 2 on bad arguments. */
+int svrh_irtk_prepare_level(const svr_image_attr *attr, const int16_t *data, double blur, const double res[3], const double res0[3], int level,
+                            int padding, svr_image_attr *out_attr, int16_t *out_or_null, long capacity, int *min_out, int *max_out,
+                            char err[256]);
 void svrh_irtk_rigid_parameters(const double matrix16[16], double params6[6], double *rebuilt16_or_null);
 
 /* ---- patch-to-volume reconstruction loop (csrc/pvr_host.cpp) ---------------------------

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from fetalreconstruction_amd import geometry as geo
+from fetalreconstruction_amd import host
 
 
 def _case(tiny, oracle_mod, n_eval=24, seed=0):
@@ -100,3 +101,152 @@ def test_device_ncc_source_from_reconstruction(tiny, oracle_mod):
     for e, (k, M) in enumerate(zip(idx, mats)):
         _, s = oracle_mod.ncc_evaluate(targets[k], M, src)
         assert np.array_equal(sums[e], s.astype(np.int64))
+
+
+# ---- k_ncc and k_nmi_bin at their edges ---------------------------------------------------------------------------------------
+# The independent reference is _numpy_ncc above, the oracle the second opinion; the six moments are integers and must be equal.
+def _shift(tx=0.0, ty=0.0, tz=0.0, m=None):
+    M = np.eye(4)
+    if m is not None:
+        M[:3, :3] = m
+    M[:3, 3] = (tx, ty, tz)
+    return M
+
+
+_DYADIC = np.array([[0.5, 0.25, 0.0], [-0.25, 0.75, 0.0], [0.25, 0.25, 1.0]])      # every entry a multiple of 1/4
+
+
+def _edge_cases():
+    """name -> (targets int16 [n][ty][tx], source int16 [vz][vy][vx], target index [e], matrices [e][4][4])"""
+    rng = np.random.default_rng(17)
+    out = {}
+    src = rng.integers(-60, 900, (17, 31, 23)).astype(np.int16)                    # negative voxels: value < 0 is dropped
+    thin = rng.integers(-60, 900, (2, 31, 23)).astype(np.int16)                     # vz = 2: only 0 < Z < 1 is inside
+    small = rng.integers(-3, 4, (17, 31, 23)).astype(np.int16)                      # -0.5 < value < 0 and 0 < value < 0.5 occur
+    for tx, ty in ((7, 5), (37, 29), (256, 256)):
+        t = rng.integers(-1, 3000, (3, ty, tx)).astype(np.int16)
+        t[:, :, -1] = -1
+        mats = [
+            # multiples of 1/4 throughout: every product and sum is exact in double, the interpolated values are multiples of
+            # 1/64 and many are x.5 exactly -- any correct implementation agrees whatever its order of operations, so this
+            # checks IRTK's rounding rule (half away from zero) itself
+            _shift(1.25, 3.5, 2.75, _DYADIC), _shift(0.75, 8.25, 4.5, _DYADIC * 0.5), _shift(2.5, 2.5, 0.25, _DYADIC.T * 0.25),
+            # samples exactly on X = 0 (i = 0) and X = vx - 1 (i = 22), on Y = 0 and on Z = vz - 1: all excluded
+            _shift(0.0, 1.0, 1.0), _shift(3.0, 0.0, 2.5), _shift(1.0, 2.0, 16.0),
+            # every sample outside: n = 0, ncc = 0
+            _shift(1000.0, 1.0, 1.0), _shift(1.0, 1.0, -3.0),
+        ]
+        idx = np.arange(len(mats)) % 3
+        out[f"{tx}x{ty} on 23x31x17"] = (t, src, idx, np.stack(mats))
+        out[f"{tx}x{ty} on 23x31x17, values -3..3"] = (t, small, idx[:3], np.stack(mats[:3]))
+        flat = [_shift(1.25, 3.5, 0.5, _DYADIC * np.array([[1], [1], [0]])), _shift(0.5, 0.75, 0.25, _DYADIC * 0.5 * np.array([[1], [1], [0]])),
+                _shift(0.0, 1.0, 0.5), _shift(1.0, 1.0, 1.0), _shift(1.0, 1.0, 0.0)]
+        out[f"{tx}x{ty} on 23x31x2"] = (t, thin, np.arange(len(flat)) % 3, np.stack(flat))
+    # the largest sums: 65536 pixels of 32767 against 32767 -- sum t s = 2^16 32767^2 = 7.04e13, far beyond int32 and float
+    big = np.full((1, 256, 256), 32767, np.int16)
+    out["256x256 at 32767 on 258x258x3 at 32767"] = (big, np.full((3, 258, 258), 32767, np.int16), np.zeros(2, int),
+                                                     np.stack([_shift(1.0, 1.0, 1.0), _shift(0.5, 0.75, 0.25)]))
+    return out
+
+
+_EDGE = _edge_cases()
+_EDGE_REF = {}
+
+
+def _edge_ref(name):
+    """the numpy moments of a case, computed once"""
+    if name not in _EDGE_REF:
+        t, s, idx, mats = _EDGE[name]
+        _EDGE_REF[name] = np.stack([_numpy_ncc(t[k], M, s) for k, M in zip(idx, mats)])
+    return _EDGE_REF[name]
+
+
+def test_edge_cases_reach_their_edges():
+    r = _edge_ref("37x29 on 23x31x17")
+    assert (r[:5, 0] > 0).all() and (r[5:, 0] == 0).all()                          # (Z = vz - 1 for every sample: nothing is inside)
+    t, s, idx, mats = _EDGE["37x29 on 23x31x17"]
+    # X = i, Y = j + 1, Z = 1: the samples are the voxels themselves; i = 0 (X = 0) and i = 22 (X = vx - 1) are out, negative voxels dropped
+    assert r[3, 0] == ((t[idx[3]] >= 0)[:, 1:22] & (s[1, 1:30, 1:22] >= 0)).sum()
+    assert _edge_ref("7x5 on 23x31x2")[2:, 0].tolist() == [(_EDGE["7x5 on 23x31x2"][0][2] >= 0)[:, 1:].sum(), 0, 0]     # Z = 1 = vz - 1 and Z = 0: out
+    big = _edge_ref("256x256 at 32767 on 258x258x3 at 32767")
+    assert (big[:, 0] == 65536).all() and (big[:, 5] == 65536 * 32767 ** 2).all() and big[0, 5] > 7e13
+
+
+@pytest.mark.parametrize("name", sorted(_EDGE))
+def test_oracle_ncc_at_the_edges(oracle_mod, name):
+    t, s, idx, mats = _EDGE[name]
+    for e, (k, M) in enumerate(zip(idx, mats)):
+        v, sums = oracle_mod.ncc_evaluate(t[k], M, s)
+        assert np.array_equal(sums.astype(np.int64), _edge_ref(name)[e]), (name, e)
+        if _edge_ref(name)[e][0] == 0:
+            assert v == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(_EDGE))
+def test_device_ncc_at_the_edges(name):
+    from fetalreconstruction_amd import engine
+    t, s, idx, mats = _EDGE[name]
+    rec = engine.Reconstruction(0)
+    rec.ncc_set_targets(t)
+    rec.ncc_set_source(s)
+    ncc, sums = rec.ncc_evaluate(idx, mats)
+    want = _edge_ref(name)
+    assert np.array_equal(sums, want), (name, np.argwhere(sums != want)[:4].tolist())
+    assert (ncc[want[:, 0] == 0] == 0).all()
+    rec.close()
+
+
+@pytest.mark.gpu
+def test_device_ncc_scratch_growth():
+    """svr_ncc_evaluate's device scratch grows past 256 evaluations (200 fit the first allocation, 300 and 700 each replace
+    it): every call equals the per-evaluation reference, with repeated and permuted target indices, and the first call's
+    results come out again afterwards."""
+    from fetalreconstruction_amd import engine
+    rng = np.random.default_rng(23)
+    t = rng.integers(-1, 3000, (6, 29, 37)).astype(np.int16)
+    s = rng.integers(0, 900, (17, 31, 23)).astype(np.int16)
+    n = 700
+    idx = rng.integers(0, 6, n)
+    mats = np.stack([_shift(*rng.uniform(-2, 6, 3), geo.rigid_matrix(0, 0, 0, *rng.uniform(-8, 8, 3))[:3, :3] * rng.uniform(0.4, 0.7)) for _ in range(n)])
+    want = np.stack([_numpy_ncc(t[k], M, s) for k, M in zip(idx, mats)])
+    assert (want[:, 0] > 0).mean() > 0.8 and (want[:, 0] == 0).any()            # (the inputs: most evaluations overlap the source, some do not)
+    rec = engine.Reconstruction(0)
+    rec.ncc_set_targets(t)
+    rec.ncc_set_source(s)
+    first = rng.permutation(n)[:200]
+    calls = [first, rng.permutation(n)[:300], rng.permutation(n), first]
+    for sel in calls:
+        ncc, sums = rec.ncc_evaluate(idx[sel], mats[sel])
+        assert np.array_equal(sums, want[sel]), len(sel)
+    rec.close()
+
+
+_NMI_WIDTHS = (1, 2, 3, 7, 64, 511, 512)
+
+
+def _every_short():
+    return np.arange(-1, 32767, dtype=np.int16).reshape(32, 32, 32)          # every value a level can hold: -1 (padding) .. 32766
+
+
+@pytest.mark.parametrize("width", _NMI_WIDTHS)
+def test_host_nmi_bin_is_the_integer_quotient(width):
+    """irtkCalculateNumberOfBins' rescaling int(v / (double)width) of every v > 0 is v // width; -1 and 0 stay"""
+    v = _every_short()
+    nb, w, binned = host.irtk_number_of_bins(0, 64 * width - 1, v)             # a range of 64 width values: the smallest width that fits is `width`
+    assert (nb, w) == (64, width)
+    assert np.array_equal(binned, np.where(v > 0, v // width, v))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", _NMI_WIDTHS)
+def test_device_nmi_bin_is_the_host_s(width):
+    from fetalreconstruction_amd import engine
+    v = _every_short()
+    rec = engine.Reconstruction(0)
+    rec.ncc_set_source(v)
+    rec.nmi_bin_source(width)
+    got = rec.ncc_get_source()
+    assert np.array_equal(got, host.irtk_number_of_bins(0, 64 * width - 1, v)[2])
+    assert np.array_equal(got, np.where(v > 0, v // width, v))
+    rec.close()
