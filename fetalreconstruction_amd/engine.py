@@ -82,6 +82,23 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+_hip = None
+
+
+def _hip_memcpy(dst, src, nbytes, kind):
+    """hipMemcpy (kind 1: host to device, 2: device to host; it returns when the copy is done) on the HIP runtime libsvr_hip.so
+    is linked to: opened by its soname, the loader hands back the runtime that is already loaded"""
+    global _hip
+    if _hip is None:
+        load_library()
+        _hip = C.CDLL("libamdhip64.so")
+        _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hip.hipMemcpy.restype = C.c_int
+    rc = _hip.hipMemcpy(dst, src, nbytes, kind)
+    if rc != 0:
+        raise SvrError(f"hipMemcpy: HIP error {rc}")
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -593,6 +610,50 @@ class Reconstruction:
         a, b = C.c_size_t(0), C.c_size_t(0)
         self._ck(self._lib.svr_slab_plan(self._h, int(world), int(rank), C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def pair_pack(self, which, n_floats):
+        """svr_pair_pack: the mask's bounding box of the n_floats / Nv volumes that start at buffer `which`, packed -> (device
+        pointer, floats), or (None, 0) where nothing is gained (no mask box, a box over 80 % of the volume): the caller then
+        exchanges the whole buffer"""
+        ptr, n = C.c_void_p(), C.c_size_t(0)
+        self._ck(self._lib.svr_pair_pack(self._h, int(which), C.c_size_t(n_floats), C.byref(ptr), C.byref(n)))
+        return ptr.value, int(n.value)
+
+    def pair_unpack(self, which, n_floats):
+        """svr_pair_unpack: the packed box (after the collective) back into the volumes"""
+        self._ck(self._lib.svr_pair_unpack(self._h, int(which), C.c_size_t(n_floats)))
+
+    def slab_rs_pack(self):
+        """svr_slab_rs_pack: addon | cmap at the mask voxels of every rank's slab + halo -> (send, recv) device pointers: send holds
+        [world][2][rs_chunk] floats; the reduce-scatter's result, [2][rs_chunk], belongs at recv"""
+        s, r = C.c_void_p(), C.c_void_p()
+        self._ck(self._lib.svr_slab_rs_pack(self._h, C.byref(s), C.byref(r)))
+        return s.value, r.value
+
+    def slab_update(self, adaptive, alpha, min_intensity, max_intensity, delta, lam):
+        """svr_slab_update: the reduced sums at recv -> the rank's planes of the volume update -> (send, recv): send holds the rank's
+        all-gather part, [ag_chunk] floats; every rank's part, [world][ag_chunk], belongs at recv"""
+        s, r = C.c_void_p(), C.c_void_p()
+        self._ck(self._lib.svr_slab_update(self._h, int(bool(adaptive)), C.c_float(alpha), C.c_float(min_intensity),
+                                           C.c_float(max_intensity), C.c_float(delta), C.c_float(lam), C.byref(s), C.byref(r)))
+        return s.value, r.value
+
+    def slab_finish(self):
+        """svr_slab_finish: the other ranks' parts at recv go into the new volume, which becomes the current one"""
+        self._ck(self._lib.svr_slab_finish(self._h))
+
+    def read_floats(self, ptr, n):
+        """n floats at a raw device pointer of this engine (slab_rs_pack, slab_update, device_ptr), behind everything queued on its stream"""
+        out = np.empty(int(n), np.float32)
+        self.stream_sync()
+        _hip_memcpy(_p(out), ptr, out.nbytes, 2)
+        return out
+
+    def write_floats(self, ptr, arr):
+        """a float32 array to a raw device pointer of this engine, behind everything queued on its stream and complete on return"""
+        a = _f32(arr).reshape(-1)
+        self.stream_sync()
+        _hip_memcpy(ptr, _p(a), a.nbytes, 1)
 
     def cell_stats(self):
         o = (C.c_uint64 * 8)()

@@ -100,20 +100,36 @@ def test_slab_update_is_the_replicated_update_bit_for_bit(world):
 
 def test_slab_plan_covers_every_voxel_once():
     """slab boundaries by mask-voxel count; reduce-scatter ranges = slab + one halo plane either side; all-gather ranges partition
-    the dilated mask"""
+    the dilated mask.  Over the masks the device plan is compared against (tests/test_slab_gpu.py; `a` is the ellipsoid with 40
+    voxels knocked out): touching the faces, with empty planes, one fat plane, one plane, one voxel, empty, with negative entries;
+    worlds up to vz and vz + 3 (empty slabs)."""
+    from tests import slab_ranks
+    for name in slab_ranks.MASKS:
+        _slab_plan_checks(name, slab_ranks.make_mask((19, 17, 23), name))
+
+
+def _slab_plan_checks(name, mask):
+    from tests import slab_ranks
     from tests.twins.reconstruction import slab_plan_numpy
-    rng = np.random.default_rng(3)
-    z, y, x = np.mgrid[:23, :17, :19]
-    mask = (((z - 11) / 9.0) ** 2 + ((y - 8) / 6.5) ** 2 + ((x - 9) / 7.0) ** 2 < 1).astype(np.float32)
-    mask[rng.integers(0, 23, 40), rng.integers(0, 17, 40), rng.integers(0, 19, 40)] = 0
-    for world in (1, 2, 3, 5, 8, 23, 40):
+    if name == "a":
+        rng = np.random.default_rng(3)
+        z, y, x = np.mgrid[:23, :17, :19]
+        want = (((z - 11) / 9.0) ** 2 + ((y - 8) / 6.5) ** 2 + ((x - 9) / 7.0) ** 2 < 1).astype(np.float32)
+        want[rng.integers(0, 23, 40), rng.integers(0, 17, 40), rng.integers(0, 19, 40)] = 0
+        assert np.array_equal(mask, want)
+    m = mask != 0
+    for world in (1, 2, 3, 5, 8, 23, 26, 40):
         p = slab_plan_numpy(mask, world)
         zb = p["zb"]
         assert zb[0] == 0 and zb[-1] == 23 and all(a <= b for a, b in zip(zb, zb[1:]))
+        assert np.array_equal(p["midx"], np.flatnonzero(m)) and np.array_equal(p["didx"], np.flatnonzero(slab_ranks.dilate(m)))
         cover = np.zeros(len(p["didx"]), int)
         for st, cnt in p["ag"]:
             cover[st:st + cnt] += 1
         assert (cover == 1).all()
+        dplanes = p["didx"] // (17 * 19)
+        for r, (st, cnt) in enumerate(p["ag"]):                      # a rank's all-gather range: the dilated voxels of its planes
+            assert cnt == ((dplanes >= zb[r]) & (dplanes < zb[r + 1])).sum() and (dplanes[st:st + cnt] >= zb[r]).all() and (dplanes[st:st + cnt] < zb[r + 1]).all()
         planes = p["midx"] // (17 * 19)
         for r, (st, cnt) in enumerate(p["rs"]):
             if zb[r] < zb[r + 1]:
@@ -122,9 +138,10 @@ def test_slab_plan_covers_every_voxel_once():
                 assert cnt == want.sum() and (len(pl) == 0 or (pl.min() >= zb[r] - 1 and pl.max() <= zb[r + 1]))
             else:
                 assert cnt == 0
+        assert p["rs_chunk"] == max(1, max(c for _, c in p["rs"])) and p["ag_chunk"] == max(1, max(c for _, c in p["ag"]))
         counts = [((planes >= zb[r]) & (planes < zb[r + 1])).sum() for r in range(world)]
         if world <= 8:
-            assert max(counts) - min(counts) <= 2 * (mask != 0).reshape(23, -1).sum(1).max()      # equal shares up to whole planes
+            assert max(counts) - min(counts) <= 2 * m.reshape(23, -1).sum(1).max()      # equal shares up to whole planes
 
 
 # ---- the patch-to-volume loop sharded by patches ("PVR: identical with patches as the unit") ----------------
