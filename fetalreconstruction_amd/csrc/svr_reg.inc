@@ -24,7 +24,7 @@ struct RegState {
   // batched gradient: the twelve variants of every slice in one launch sequence
   float *regv = nullptr, *tmpv = nullptr, *matv = nullptr, *simv = nullptr, *sumBv = nullptr, *momv = nullptr;   // [36][ns][H][W] x 2, [12][ns][16], [12][ns], [36][ns], [36][ns][3]
   int *cntBv = nullptr;
-  long long *dctr = nullptr;                                                       // [4] device part of `counters` (blind line-search steps)
+  long long *dctr = nullptr;                                                       // [5] device part of `counters` (blind line-search steps); [4]: ls_max
   int red_threads = 0;                                                             // 0: by image size; 256 / 1024 (option reg_red_threads, tests)
   int batch_state = 0;                                                             // 0 not tried, 1 ready, -1 no memory: literal sequence
   float *sumA = nullptr, *sumB = nullptr, *mom = nullptr, *half = nullptr;         // [ns], [3][ns], [3][ns][3], [8][32]
@@ -35,6 +35,10 @@ struct RegState {
   float blurring[8], length_of_steps[8];
   int klen[8];
   long long counters[4] = {0, 0, 0, 0};
+  // svr_reg_get: the length of the active list the last evaluation / run left, and the most slices any line-search step of
+  // the last run kept
+  int last_active = 0, ls_max = 0;
+  int red_used = 0;                                                                // the workgroup size the per-image reductions last ran with
 };
 
 struct RegVol {
@@ -425,7 +429,7 @@ __global__ __launch_bounds__(1024) void k_reg_line_check(int *new_mask, const in
   const int n = *count;
   if (n == 0) return;
   const int c = reg_compact(new_mask, mask, n, s, sim, 0, 2, eps);
-  if (threadIdx.x == 0) { *count = c; dctr[0] += 1; dctr[1] += 1; dctr[3] += n; }
+  if (threadIdx.x == 0) { *count = c; dctr[0] += 1; dctr[1] += 1; dctr[3] += n; if (c > dctr[4]) dctr[4] = c; }
   __syncthreads();
   for (int i = threadIdx.x; i < c; i += 1024) {
     const int sl = new_mask[i];
@@ -692,6 +696,7 @@ int reg_begin_level(svr_ctx *ctx, int level) {
                         ctx->stream));
   int rc = reg_blur_layers(ctx, r->target, r->ns, 1, level);
   if (rc) return rc;
+  r->red_used = reg_red_threads(r);
   hipLaunchKernelGGL(k_reg_sums, dim3(r->ns, 1), dim3(reg_red_threads(r)), 0, ctx->stream, r->target, (const int *)nullptr, r->ns,
                      (int)r->wh, r->sumA, r->cntA, r->ns);
   KCHK("k_reg_sums(target)");
@@ -802,7 +807,7 @@ int svr_init_reg_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const flo
   HIPCHK(hipMalloc(&r->active2, sizeof(int) * r->ns));
   HIPCHK(hipMalloc(&r->active_prev, sizeof(int) * r->ns));
   HIPCHK(hipMalloc(&r->count, sizeof(int)));
-  HIPCHK(hipMalloc(&r->dctr, 4 * sizeof(long long)));
+  HIPCHK(hipMalloc(&r->dctr, 5 * sizeof(long long)));
   HIPCHK(hipMalloc(&r->sumA, sizeof(float) * r->ns));
   HIPCHK(hipMalloc(&r->cntA, sizeof(int) * r->ns));
   HIPCHK(hipMalloc(&r->sumB, 3 * sizeof(float) * r->ns));
@@ -886,7 +891,8 @@ int svr_register_slices_to_volume(svr_ctx *ctx, float *transf) {
   r->red_threads = ctx->reg_red_threads;
   const bool batch = ctx->reg_batch && reg_batch_ready(ctx);   // the gradient's twelve evaluations as one launch sequence
   const int blind = std::max(0, ctx->reg_blind);               // line-search steps per host round trip (0: the literal loop)
-  HIPCHK(hipMemsetAsync(r->dctr, 0, 4 * sizeof(long long), ctx->stream));
+  HIPCHK(hipMemsetAsync(r->dctr, 0, 5 * sizeof(long long), ctx->stream));
+  r->ls_max = 0;
 #define RCHK(x) do { rc = (x); if (rc) return rc; } while (0)
   for (int level = r->levels - 1; level >= 0; --level) {
     float step = r->length_of_steps[level];
@@ -941,6 +947,7 @@ int svr_register_slices_to_volume(svr_ctx *ctx, float *transf) {
           RCHK(reg_evaluate(ctx, active, level, 0, 1, 1));
           r->counters[1] += 1;
           RCHK(reg_check(ctx, r->active2, r->active, active, 0, 2, &active));
+          r->ls_max = std::max(r->ls_max, active);
           std::swap(r->active, r->active2);
         } while (active > 0);
         // the last step did not improve: back track (RC.cu:4118-4122)
@@ -949,17 +956,19 @@ int svr_register_slices_to_volume(svr_ctx *ctx, float *transf) {
         KCHK("k_reg_step");
         HIPCHK(hipMemcpyAsync(r->mat_orig, r->mat, mb, hipMemcpyDeviceToDevice, ctx->stream));
         RCHK(reg_check(ctx, r->active, r->active_prev, prev_active, 2, 1, &active));
+        r->last_active = active;
         if (active == 0) break;
       }
       step /= 2.0f;
     }
   }
 #undef RCHK
-  long long dc[4] = {0, 0, 0, 0};
+  long long dc[5] = {0, 0, 0, 0, 0};
   HIPCHK(hipMemcpyAsync(dc, r->dctr, sizeof(dc), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipMemcpyAsync(transf, r->mat, mb, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (int k = 0; k < 4; ++k) r->counters[k] += dc[k];
+  r->ls_max = std::max(r->ls_max, (int)dc[4]);
   t.stop();
   return SVR_OK;
 }
@@ -978,12 +987,14 @@ int svr_reg_evaluate_costs(svr_ctx *ctx, const float *transf, int level, const i
   r->red_threads = ctx->reg_red_threads;
   const int s = r->ns;
   int a = s;
-  HIPCHK(hipMemcpyAsync(r->mat, transf, 16 * sizeof(float) * s, hipMemcpyHostToDevice, ctx->stream));
   if (active_or_null) {
     if (n_active < 0 || n_active > s) return fail(ctx, SVR_E_ARG, "active list too long");
     for (int i = 0; i < n_active; ++i)
       if (active_or_null[i] < 0 || active_or_null[i] >= s) return fail(ctx, SVR_E_ARG, "active slice out of range");
     a = n_active;
+  }
+  HIPCHK(hipMemcpyAsync(r->mat, transf, 16 * sizeof(float) * s, hipMemcpyHostToDevice, ctx->stream));   // (nothing is touched before the arguments are checked)
+  if (active_or_null) {
     HIPCHK(hipMemcpyAsync(r->active, active_or_null, sizeof(int) * a, hipMemcpyHostToDevice, ctx->stream));
   } else {
     hipLaunchKernelGGL(k_reg_iota, dim3(nblk(s)), dim3(256), 0, ctx->stream, r->active, s);
@@ -991,6 +1002,7 @@ int svr_reg_evaluate_costs(svr_ctx *ctx, const float *transf, int level, const i
   HIPCHK(hipMemsetAsync(r->sim, 0, 5 * sizeof(float) * s, ctx->stream));
   int rc = reg_begin_level(ctx, level);
   if (rc) return rc;
+  r->last_active = a;
   rc = reg_evaluate(ctx, a, level, 0, 1, 1);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(similarities_out, r->sim, sizeof(float) * s, hipMemcpyDeviceToHost, ctx->stream));
@@ -998,6 +1010,40 @@ int svr_reg_evaluate_costs(svr_ctx *ctx, const float *transf, int level, const i
     for (int o = 0; o < 3; ++o)
       HIPCHK(hipMemcpyAsync(reg_slices_out + (size_t)o * a * r->wh, r->reg + (size_t)o * s * r->wh,
                             (size_t)a * r->wh * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return SVR_OK;
+}
+
+/* test hook: a copy of the state the last svr_reg_evaluate_costs / svr_register_slices_to_volume left on the device.
+ * which (enum svr_reg_state, include/svr_hip.h) picks the array; `bytes` must be its exact size.  Reads only. */
+int svr_reg_get(svr_ctx *ctx, int which, void *out, size_t bytes) {
+  SVR_ENTER(ctx);
+  if (!ctx || !out) return SVR_E_ARG;
+  NEED(ctx->reg && ctx->reg->prepared, "no registration state (svr_prepare_slice_to_volume_reg first)");
+  RegState *r = ctx->reg;
+  const size_t s = (size_t)r->ns;
+  const void *src = nullptr;
+  size_t n = 0;
+  switch (which) {
+    case SVR_REG_TARGETS: src = r->target; n = s * r->wh * sizeof(float); break;
+    case SVR_REG_SUM_A: src = r->sumA; n = s * sizeof(float); break;
+    case SVR_REG_CNT_A: src = r->cntA; n = s * sizeof(int); break;
+    case SVR_REG_SUM_B: src = r->sumB; n = 3 * s * sizeof(float); break;
+    case SVR_REG_CNT_B: src = r->cntB; n = 3 * s * sizeof(int); break;
+    case SVR_REG_MOMENTS: src = r->mom; n = 9 * s * sizeof(float); break;
+    case SVR_REG_SIMILARITIES: src = r->sim; n = 5 * s * sizeof(float); break;
+    case SVR_REG_GRADIENT: src = r->grad; n = 7 * s * sizeof(float); break;
+    case SVR_REG_ACTIVE: src = r->active; n = (3 + s) * sizeof(int); break;
+    default: return fail(ctx, SVR_E_ARG, "svr_reg_get: unknown array");
+  }
+  if (bytes != n) return fail(ctx, SVR_E_ARG, "svr_reg_get: size mismatch");
+  if (which == SVR_REG_ACTIVE) {
+    int *o = (int *)out;
+    o[0] = r->last_active; o[1] = r->ls_max; o[2] = r->red_used;
+    HIPCHK(hipMemcpyAsync(o + 3, src, s * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    HIPCHK(hipMemcpyAsync(out, src, n, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }

@@ -25,6 +25,7 @@ BUF_SLICES, BUF_WEIGHTS, BUF_SIMSLICES, BUF_SIMWEIGHTS, BUF_PSF_SUMS, BUF_BIAS =
 BUF_SIMINSIDE, BUF_VOXEL_COUNT = 20, 21
 T_BACKPROJECT, T_FORWARD, T_GAUSS, T_REGULARIZE, T_ESTEP, T_MSTEP, T_SCALE, T_REGISTER = range(8)
 RESAMPLE_INSTALL, RESAMPLE_SCALE = 1, 2                # SVR_RESAMPLE_* (include/svr_hip.h)
+REG_TARGETS, REG_SUM_A, REG_CNT_A, REG_SUM_B, REG_CNT_B, REG_MOMENTS, REG_SIMILARITIES, REG_GRADIENT, REG_ACTIVE = range(9)   # enum svr_reg_state
 TIMER_NAMES = ("backproject", "forward", "gauss", "regularize", "estep", "mstep", "scale", "register", "allreduce", "exchange_host", "coeff_build", "reduce_scatter", "allgather",
                "backproject_table", "forward_table", "forward_store", "backproject_store")
 
@@ -44,7 +45,7 @@ EXPORTS = [
     "svr_ncc_evaluate", "svr_ncc_get", "svr_ncc_alloc_targets","svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
-    "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_pvr_cc_patches", "svr_pvr_register_patches",
+    "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_reg_get", "svr_pvr_cc_patches", "svr_pvr_register_patches",
     "svr_slab_plan", "svr_slab_rs_pack", "svr_slab_update", "svr_slab_finish", "svr_stream_sync",
     "svr_get_scale_vector", "svr_adopt_scale_vector", "svr_get_slice_inside", "svr_mstep_estep", "svr_mstep_sums_fetch", "svr_mstep_partial", "svr_mstep_estep_ranks",
 ]
@@ -558,6 +559,21 @@ class Reconstruction:
         c = np.zeros(3, np.int64)
         self._ck(self._lib.svr_pvr_register_patches(self._h, _p(r), _p(m), _p(mi), _p(t), _p(ti), _p(c)))
         return t, ti, c
+
+    def reg_get(self, which):
+        """svr_reg_get: a copy of the state the last evaluate_costs / registerSlicesToVolume left (REG_* above; read-only).
+        REG_ACTIVE -> (the active list, the most slices a line-search step of the last run kept, the workgroup size of the
+        per-image reductions)."""
+        ns, H, W = self._reg_grid
+        shape, dt = {REG_TARGETS: ((ns, H, W), np.float32), REG_SUM_A: ((ns,), np.float32), REG_CNT_A: ((ns,), np.int32),
+                     REG_SUM_B: ((3, ns), np.float32), REG_CNT_B: ((3, ns), np.int32), REG_MOMENTS: ((3, ns, 3), np.float32),
+                     REG_SIMILARITIES: ((5, ns), np.float32), REG_GRADIENT: ((7, ns), np.float32),
+                     REG_ACTIVE: ((3 + ns,), np.int32)}[which]
+        out = np.zeros(shape, dt)
+        self._ck(self._lib.svr_reg_get(self._h, int(which), _p(out), C.c_size_t(out.nbytes)))
+        if which == REG_ACTIVE:
+            return out[3:3 + out[0]].copy(), int(out[1]), int(out[2])
+        return out
 
     def reg_counters(self):
         c = np.zeros(4, np.int64)

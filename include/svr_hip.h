@@ -377,6 +377,24 @@ int svr_reg_set_schedule(svr_ctx *ctx, int levels, int steps, int iterations);
 int svr_reg_evaluate_costs(svr_ctx *ctx, const float *transf, int level, const int *active_or_null, int n_active,
                            float *similarities_out, float *reg_slices_out_or_null);
 int svr_reg_counters(svr_ctx *ctx, long long out4[4]);
+/* Read-back of the state the last svr_reg_evaluate_costs or svr_register_slices_to_volume left on the device, for the tests
+ * that look at a stage (tests/test_reg_shapes_gpu.py).  `bytes` must be the exact size of the array; fails with a message
+ * (SVR_E_STATE before svr_prepare_slice_to_volume_reg, SVR_E_ARG for an unknown array or a wrong size).  Read-only.
+ * Rows indexed by slot follow the active list of the call; sumA / cntA / similarities / gradient are indexed by slice. */
+enum svr_reg_state {
+  SVR_REG_TARGETS = 0,       /* float [slices][H][W]: the blurred targets of the level */
+  SVR_REG_SUM_A = 1,         /* float [slices]: their sums over values > -1 */
+  SVR_REG_CNT_A = 2,         /* int   [slices]: and counts */
+  SVR_REG_SUM_B = 3,         /* float [3][slices]: per offset and slot, sum of the blurred sampled slice over values > -1 */
+  SVR_REG_CNT_B = 4,         /* int   [3][slices] */
+  SVR_REG_MOMENTS = 5,       /* float [3][slices][3]: per offset and slot {sum sa*sb, sum sa*sa, sum sb*sb} */
+  SVR_REG_SIMILARITIES = 6,  /* float [5][slices] */
+  SVR_REG_GRADIENT = 7,      /* float [7][slices] */
+  SVR_REG_ACTIVE = 8         /* int   [3 + slices]: {length of the active list, the most slices a line-search step of the last
+                                run kept, the workgroup size the per-image reductions ran with, the list} (entries behind the
+                                length are stale) */
+};
+int svr_reg_get(svr_ctx *ctx, int which, void *out, size_t bytes);
 
 /* PVR patch-to-volume registration cost (second variant): computeCCpatch
  * (patchBased2D3DRegistration_gpu2.cu:130-190) for every patch of the slice grid with its own

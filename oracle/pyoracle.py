@@ -371,6 +371,8 @@ class RegState(C.Structure):
         ("levels", C.c_int), ("steps", C.c_int), ("iterations", C.c_int), ("epsilon", C.c_float),
         ("blurring", C.c_float * 8), ("length_of_steps", C.c_float * 8),
         ("reg_dbg", C.c_void_p),
+        ("last_active", C.c_int), ("ls_max", C.c_int),
+        ("stage_dbg", C.c_void_p),
     ]
 
 
@@ -400,6 +402,7 @@ class OracleRegistration:
         for nm in ("resampled", "resampled_float", "reg", "tmp"):
             self._bind(nm, np.zeros(n, np.float32))
         self._bind("reg_dbg", np.full(3 * n, -1, np.float32))
+        self._bind("stage_dbg", np.zeros(12 * int(ns), np.float32))
         self._bind("matrices", np.zeros(16 * ns, np.float32))
         self._bind("matrices_orig", np.zeros(16 * ns, np.float32))
         self._bind("similarities", np.zeros(5 * ns, np.float32))
@@ -434,6 +437,11 @@ class OracleRegistration:
         lib().orc_reg_register(C.byref(self.st), _p(t), _p(self.counters))
         return t.reshape(-1, 4, 4)
 
+    def final_active(self):
+        """after registerSlicesToVolume: (the active list the run left, the most slices any line-search step kept)"""
+        buf = self._active if self.st.active == self._active.ctypes.data else self._active2
+        return buf[:self.st.last_active].copy(), int(self.st.ls_max)
+
     def evaluate_costs(self, transf, level, active=None):
         """One evaluateCostsMultipleSlices(…, 0, 1, 1) on the blurred targets of `level` for the given
         matrices and active list; returns (similarity[slices], blurred sampled slices [3][a][H][W])."""
@@ -442,6 +450,7 @@ class OracleRegistration:
         self._matrices[:] = _f32(transf).reshape(-1)
         act = np.arange(ns, dtype=np.int32) if active is None else np.asarray(active, np.int32)
         self._active[:len(act)] = act
+        self._last_act = act
         st.active = self._active.ctypes.data
         lib().orc_reg_begin_level(C.byref(st), C.c_int(level))
         self._similarities[:] = 0
@@ -449,6 +458,12 @@ class OracleRegistration:
                                      C.c_int(0), C.c_int(1), C.c_int(1))
         dbg = self._reg_dbg.reshape(3, ns, st.H, st.W)[:, :len(act)].copy()
         return self._similarities[:ns].copy(), dbg
+
+    def last_stages(self):
+        """of the last evaluate_costs: per offset and slot (sum of the blurred sampled slice [3][a], the three moments [3][a][3])"""
+        a = len(self._last_act)
+        d = self._stage_dbg.reshape(3, self.st.slices, 4)[:, :a]
+        return d[..., 0].copy(), d[..., 1:].copy()
 
 
 def reg_gauss_kernel(sigma):

@@ -66,6 +66,8 @@ typedef struct orc_reg {
   float epsilon;
   float blurring[8], length_of_steps[8];
   float *reg_dbg;             /* optional [3][slices][H][W]: blurred sampled slices of the last evaluate */
+  int last_active, ls_max;    /* after orc_reg_register: length of the list in `active`; the most slices a line-search step kept */
+  float *stage_dbg;           /* optional [3][slices][4]: per offset and slot {sum of the blurred sampled slice, the three moments} */
 } orc_reg;
 
 static void matvec3(const float *M, const float v[3], float out[3]) {   /* RVH:134-145 */
@@ -210,6 +212,13 @@ void orc_reg_evaluate_costs(orc_reg *r, int active_slices, int level, float blur
     if (r->reg_dbg)
       memcpy(r->reg_dbg + (size_t)(insofs + 1) * s * W * H, r->reg, sizeof(float) * (size_t)a * W * H);
     average_if(r->reg, NULL, a, W, H, F + a, I + a);                          /* :4195, no reset */
+    if (r->stage_dbg)
+      for (int slot = 0; slot < a; ++slot) {
+        const float *p = r->reg + (size_t)slot * W * H;
+        double acc = 0;
+        for (int i = 0; i < W * H; ++i) if (p[i] > -1.0f) acc += p[i];
+        r->stage_dbg[((size_t)(insofs + 1) * s + slot) * 4] = (float)acc;
+      }
     for (int i = 2 * s; i < 5 * s; ++i) F[i] = 0;                             /* :4200, `slices` not `active_slices` */
     /* computeNCCAndReduce RC.cu:4498-4550 */
     const int lv = level + 1;
@@ -228,6 +237,10 @@ void orc_reg_evaluate_costs(orc_reg *r, int active_slices, int level, float blur
           m1 += (double)(sa * sa);
           m2 += (double)(sb * sb);
         }
+      }
+      if (r->stage_dbg) {
+        float *D = r->stage_dbg + ((size_t)(insofs + 1) * s + slot) * 4;
+        D[1] = (float)m0; D[2] = (float)m1; D[3] = (float)m2;
       }
       float *R = F + 3 * a + 3 * slot;
       R[0] = R[0] + (float)m0;
@@ -341,6 +354,7 @@ void orc_reg_register(orc_reg *r, float *transf, long long *counters) {
   memcpy(r->matrices, transf, sizeof(float) * 16 * s);
   memcpy(r->matrices_orig, transf, sizeof(float) * 16 * s);
   long long n_eval = 0, n_ls = 0, n_it = 0, n_slot = 0;
+  r->last_active = 0; r->ls_max = 0;
   for (int level = r->levels - 1; level >= 0; --level) {
     float blur = r->blurring[level];
     float step = r->length_of_steps[level];
@@ -391,6 +405,7 @@ void orc_reg_register(orc_reg *r, float *transf, long long *counters) {
           }
           orc_reg_evaluate_costs(r, active, level, blur, 0, 1, 1); ++n_eval; ++n_ls; n_slot += active;
           active = check_improvement(r, r->active2, active, r->active, 0, 2, r->epsilon);
+          if (active > r->ls_max) r->ls_max = active;
           int *t = r->active; r->active = r->active2; r->active2 = t;
         } while (active > 0);
         for (int i = 0; i < prev_active; ++i) {                                       /* back track */
@@ -401,6 +416,7 @@ void orc_reg_register(orc_reg *r, float *transf, long long *counters) {
         }
         memcpy(r->matrices_orig, r->matrices, sizeof(float) * 16 * s);
         active = check_improvement(r, r->active, prev_active, r->active_prev, 2, 1, r->epsilon);
+        r->last_active = active;
         if (active == 0) break;
       }
       step /= 2.0f;
