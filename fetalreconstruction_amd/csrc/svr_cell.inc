@@ -361,12 +361,26 @@ __global__ void k_cell_entries(CellArgs ca, uint32_t nitems, const uint32_t *ite
 // ---- per launch ------------------------------------------------------------------------------------------------------
 // the factors of every sorted pixel: what back_wave_kernel's "lane = pixel" part works out (RC.cu:439-447 / 278-282).
 // gauss: 0 = the SR scatter, 1 = pass 2 of the Gaussian reconstruction, 2 = NormaliseBias (normalizeBiasKernel3D_tex RC.cu:544-550, 591:
-// weight psf / sume, value the pixel's log bias minus the log of its slice's scale)
+// weight psf / sume, value the pixel's log bias minus the log of its slice's scale), 3 = a channel (svr_channel_scatter: the SR scatter's weight, the
+// value read from a.channel)
 __global__ void k_cell_factors(PsfArgs a, int gauss, CellRec *recs, uint32_t n, unsigned char *act) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t idx = recs[i].idx;
   float f0 = 0.0f, f1 = 0.0f;
+  if (gauss == 3) {
+    // a channel (svr_channel.inc): the SR scatter's pixel set without the flag, minus the slices switched off; the SR scatter's own weight; the value
+    // is the channel's (or the indicator of one label), never the primary image's -- no scale, no bias, no simulated slice
+    const uint32_t sl = idx / (uint32_t)(a.sx * a.sy);
+    if (pixel_active(a.slices, a.psf_sums, nullptr, idx) && (!a.unit_on || a.unit_on[sl] != 0)) {
+      const float c = a.channel[idx];
+      const float x = (a.ch_flags & SVR_CHANNEL_INDICATOR) ? (c == a.ch_match ? 1.0f : 0.0f) : c;
+      f1 = (a.weights[idx] * a.slice_weights[sl]) / a.psf_sums[idx];
+      f0 = f1 * x;
+    }
+    recs[i].f0 = f0; recs[i].f1 = f1;    // (never the pass that writes the table: act is NULL)
+    return;
+  }
   const bool on = pixel_active(a.slices, a.psf_sums, a.flag, idx);
   // (the table is for the SR iterations' PSF pixels: s != -1 and v_PSF_sums != 0 -- in pass 2 of the Gaussian reconstruction a superset of the
   // flagged ones: v_PSF_sums is never cleared between Gaussian passes, RC.cu:2401-2411)

@@ -32,8 +32,14 @@
 // deviation: the reference reads the file, main.cc:253-258, lets iteration 0 register, :826, and outside its T1 experiment never hands
 // the voxels to the registration) seeds the run with a volume in the template's world space on any grid: resampled onto the
 // reconstruction grid on the device (svr_resample_to_reconstruction, csrc/svr_seed.inc), brought to the stacks' intensity scale, it is
-// every rank's reconstructed volume when the loop starts, and iteration 0 registers against it like any later one.  Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
+// every rank's reconstructed volume when the loop starts, and iteration 0 registers against it like any later one.  --channelStacks /
+// --labelStacks (deviations) and the reference's --manualMask (reconstruction.cc:1240-1250) carry a second image per stack -- another
+// co-registered acquisition, a label map, a manual mask -- into the reconstructed space after the volume has been written, with the final
+// slice transformations and the EM's weights (svr_channel_scatter, csrc/svr_channel.inc): cropped with their stack, cut into slices and
+// packed like the primaries, scattered through the SR iteration's scatter, divided by the weights (channels) or voted label by label.
+// Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
 #include <functional>
+#include <set>
 #include <thread>
 
 #include <future>
@@ -57,6 +63,9 @@ int main(int argc, char **argv) {
   bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
   std::string reference_name;                                             // --referenceVolume (main.cc:207; takes effect here)
   std::string report_name, sim_prefix;                                   // --sliceReport, --simulatedStacks (not reference options)
+  std::vector<std::string> channel_names, label_names;                   // --channelStacks, --labelStacks (not reference options): a file or `none` per -i stack
+  std::string channel_out, label_out, label_conf, manual_name, channels_dump;   // --channelOutput, --labelOutput, --labelConfidence, --manualMask, --dumpChannels
+  bool have_channel_opt = false, have_label_opt = false;
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
   // ---- options (main.cc:164-211) ---------------------------------------------------------------------
   auto is_opt = [](const char *s) { return s[0] == '-' && !(s[1] >= '0' && s[1] <= '9') && s[1] != '.'; };
@@ -114,6 +123,13 @@ int main(int argc, char **argv) {
     else if (o == "--sliceReport") report_name = one();                   // not reference options: the reference's main() never calls SlicesInfo / SimulateStacks
     else if (o == "--simulatedStacks") sim_prefix = one();
     else if (o == "--referenceVolume") reference_name = one();            // main.cc:207, 253-258: read there and (outside the T1 experiment) never used
+    else if (o == "--channelStacks") { have_channel_opt = true; multi(channel_names); }   // not reference options: a second image per stack through the run's motion and weights
+    else if (o == "--channelOutput") channel_out = one();
+    else if (o == "--labelStacks") { have_label_opt = true; multi(label_names); }
+    else if (o == "--labelOutput") label_out = one();
+    else if (o == "--labelConfidence") label_conf = one();
+    else if (o == "--manualMask") manual_name = one();                    // main.cc:208; reconstruction.cc:1240-1250 transformManualMaskwithPSF
+    else if (o == "--dumpChannels") channels_dump = one();                // test hook: the packed channel / label grids [--dryRun: stop there]
     else if (o == "--useCPUReg" || o == "--disableBiasCorrection" || o == "--debug_gpu") {}
     else if (o == "-d" || o == "--devices") { std::vector<std::string> v; multi(v); for (auto &s : v) devices.push_back(atoi(s.c_str())); }
     else if (o == "-h" || o == "--help") {
@@ -124,6 +140,27 @@ int main(int argc, char **argv) {
              "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n"
              "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
              "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix] [--referenceVolume file]\n"
+             "       [--channelStacks f_1 .. f_N --channelOutput file] [--labelStacks f_1 .. f_N --labelOutput file [--labelConfidence file]]\n"
+             "       [--manualMask file]\n"
+             "  --channelStacks f_1 .. f_N --channelOutput <file>\n"
+             "                          deviation from the reference, which has no such option: a second image per -i stack (another echo, a\n"
+             "                          quantitative or probability map), on its stack's grid; `none` = the stack has none.  After the volume\n"
+             "                          is written the files, cropped and cut into slices with their stacks, are scattered into the volume with\n"
+             "                          the final slice transformations and the robust weights of the run and divided by the scattered weights:\n"
+             "                          the robust PSF-weighted average of the channel, in its own units (no intensity matching, no bias field,\n"
+             "                          no super-resolution iterations), 0 where no slice with a channel reaches.  Its own value never excludes\n"
+             "                          a pixel: zero and negative values count.  The -o volume is the same with and without it.\n"
+             "  --labelStacks f_1 .. f_N --labelOutput <file> [--labelConfidence <file>]\n"
+             "                          deviation from the reference: a label map per -i stack (integers in 0..65535, at most 64 different\n"
+             "                          ones; 0 competes like any other label; `none` = the stack has none).  Each label's indicator image is\n"
+             "                          scattered like a channel; a voxel gets the label with the largest weighted share (ties: the smallest\n"
+             "                          label) and --labelConfidence that share.  Both are float volumes on the reconstruction grid, 0 where\n"
+             "                          no labelled slice reaches.\n"
+             "  --manualMask <file>     the reference's option: a manual mask on the FIRST stack's grid is written PSF-transformed into the\n"
+             "                          reconstructed space as PSFTransformed_<name> next to <file>.  The same as --channelStacks <file> none ..\n"
+             "                          none.  Deviation from the reference in the weighting: the robust weights of the run instead of one\n"
+             "                          plain Gaussian pass.\n"
+             "                          None of the three with --sfolder (the slices then no longer come from the stacks).\n"
              "  --referenceVolume <file> deviation from the reference (the reference reads the file and, outside its T1 experiment, never uses\n"
              "                          its voxels): use the volume as the initial reconstruction.  It must be in the template stack's world\n"
              "                          space, roughly aligned, like every stack given with -t; its grid (voxel size, field of view, axis\n"
@@ -175,6 +212,48 @@ int main(int argc, char **argv) {
     if (packages.size() > (size_t)num_stacks_tuner) packages.resize(num_stacks_tuner);
   }
   const size_t n = inputs.size();
+  // ---- second images per stack: what can be refused without reading a file -----------------------------
+  struct ExtraSet {
+    std::string what;                    // the option, for messages
+    bool labels = false;
+    std::vector<std::string> names;      // per stack; "none" = the stack has none
+    std::string out, conf;
+    std::vector<Image> imgs;             // per stack (empty image where none)
+    std::vector<float> grid;             // [ns][my][mx], 0 outside a slice's extent
+    std::vector<unsigned char> unit_on;  // [ns]
+    std::vector<float> label_values;     // ascending
+  };
+  std::vector<ExtraSet> extras;
+  {
+    if (have_channel_opt && channel_out.empty()) die("--channelStacks needs --channelOutput <file> for the reconstructed channel");
+    if (!have_channel_opt && !channel_out.empty()) die("--channelOutput needs --channelStacks f_1 .. f_N (a file or `none` per -i stack)");
+    if (have_label_opt && label_out.empty()) die("--labelStacks needs --labelOutput <file> for the reconstructed labels");
+    if (!have_label_opt && !label_out.empty()) die("--labelOutput needs --labelStacks f_1 .. f_N (a file or `none` per -i stack)");
+    if (!have_label_opt && !label_conf.empty()) die("--labelConfidence needs --labelStacks f_1 .. f_N and --labelOutput");
+    auto add = [&](const char *what, bool labels, const std::vector<std::string> &names, const std::string &out, const std::string &conf) {
+      if (!sfolder.empty())
+        die(std::string(what) + " cuts its files into slices with the stacks; with --sfolder the slices come from files of their own and belong to no "
+            "stack: drop one or the other");
+      if (names.size() != n)
+        die(std::string(what) + ": " + std::to_string(names.size()) + " files for " + std::to_string(n) + " stacks: one file (or `none`) per -i stack expected");
+      if (std::all_of(names.begin(), names.end(), [](const std::string &f) { return f == "none"; }))
+        die(std::string(what) + ": every stack is `none`: nothing to reconstruct");
+      ExtraSet e;
+      e.what = what; e.labels = labels; e.names = names; e.out = out; e.conf = conf;
+      extras.push_back(e);
+    };
+    if (have_channel_opt) add("--channelStacks", false, channel_names, channel_out, "");
+    if (have_label_opt) add("--labelStacks", true, label_names, label_out, label_conf);
+    if (!manual_name.empty()) {
+      std::vector<std::string> names(n, "none");
+      names[0] = manual_name;
+      const size_t cut = manual_name.find_last_of('/');                  // reconstruction.cc:1243-1249: "PSFTransformed_" + the file's name, in its directory
+      const std::string out = cut == std::string::npos ? "PSFTransformed_" + manual_name
+                                                       : manual_name.substr(0, cut + 1) + "PSFTransformed_" + manual_name.substr(cut + 1);
+      add("--manualMask", false, names, out, "");
+    }
+    if (!channels_dump.empty() && extras.empty()) die("--dumpChannels writes the packed grids of --channelStacks / --labelStacks / --manualMask: give one of them");
+  }
   if (tspecs.empty()) tspecs.assign(n, "id");
   if (tspecs.size() != n) die("one transformation per stack expected");
   if (!packages.empty() && packages.size() != n) die("one package count per stack expected");
@@ -198,6 +277,24 @@ int main(int argc, char **argv) {
   stacks.resize(n);
   parallel_for((int)n, [&](int k) { stacks[k] = read_image(inputs[k]); });                        // gunzip is serial per file
   for (size_t k = 0; k < n; ++k) ts.push_back(load_transformation(tspecs[k]));
+  for (auto &e : extras) {
+    e.imgs.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      if (e.names[k] == "none") continue;
+      e.imgs[k] = read_image(e.names[k]);
+      // on its stack's grid as read: the same dimensions, the same image-to-world matrix
+      const svr_image_attr &a = e.imgs[k].a, &b = stacks[k].a;
+      bool same = a.nx == b.nx && a.ny == b.ny && a.nz == b.nz;
+      if (same) {
+        const M4 ma = image_to_world(a), mb = image_to_world(b);
+        for (int q = 0; q < 16; ++q) same = same && fabs(ma.m[q] - mb.m[q]) <= 1e-3;
+      }
+      if (!same)
+        die(e.what + ": " + e.names[k] + " is not on the grid of its stack " + inputs[k] + " (" + std::to_string(a.nx) + "x" + std::to_string(a.ny) + "x" +
+            std::to_string(a.nz) + " against " + std::to_string(b.nx) + "x" + std::to_string(b.ny) + "x" + std::to_string(b.nz) +
+            ", or another image-to-world matrix): resample it onto the stack first");
+    }
+  }
   clk.mark("read stacks");
   if (thickness.empty()) for (auto &s : stacks) thickness.push_back(2.0 * s.a.dz);            // main.cc:422-431
   if (thickness.size() != n) die("one thickness per stack expected");
@@ -241,6 +338,7 @@ int main(int argc, char **argv) {
   if (have_mask) {
     const Image m = transform_nn(mask_img, stacks[tmpl].a, ts[tmpl], 0.0);                     // TransformMask RG.cc:805-821
     stacks[tmpl] = crop_image(stacks[tmpl], m);
+    for (auto &e : extras) if (!e.imgs[tmpl].d.empty()) e.imgs[tmpl] = crop_image(e.imgs[tmpl], m);   // (the crop depends on the mask alone)
   }
   const svr_image_attr tattr = create_template(stacks[tmpl].a, resolution);
   const Image vol_mask = set_mask(tattr, have_mask ? &mask_img : nullptr, smooth_mask);
@@ -266,6 +364,7 @@ int main(int argc, char **argv) {
     if (k == tmpl) continue;
     const Image m = transform_nn(vol_mask, stacks[k].a, ts[k], 0.0);
     stacks[k] = crop_image(stacks[k], m);
+    for (auto &e : extras) if (!e.imgs[k].d.empty()) e.imgs[k] = crop_image(e.imgs[k], m);
   }
   stack_registrations();                                                                         // main.cc:707-713
   clk.mark("stack registrations, crops");
@@ -326,6 +425,54 @@ int main(int argc, char **argv) {
       dims[3 * (size_t)sl] = (float)r.a.dx; dims[3 * (size_t)sl + 1] = (float)r.a.dy; dims[3 * (size_t)sl + 2] = (float)r.a.dz;
       sizes_x[sl] = r.a.nx; sizes_y[sl] = r.a.ny; stack_index[sl] = srcs[sl].stack; sattr[sl] = r.a;
   }
+  // the second images, cut and packed like the primaries: slice sl = plane j of stack k, in the same order.  Their values are kept as they
+  // are: no `v < 0.01 -> -1`, no mask, no stack factor -- which pixels count is the primary's business (svr_channel_scatter's pixel set)
+  for (auto &e : extras) {
+    e.grid.assign((size_t)ns * mx * my, 0.0f);
+    e.unit_on.assign(ns, 0);
+    int sl = 0;
+    for (size_t k = 0; k < n; ++k)
+      for (int j = 0; j < stacks[k].a.nz; ++j, ++sl) {
+        const Image &c = e.imgs[k];
+        if (c.d.empty()) continue;
+        if (c.a.nx != stacks[k].a.nx || c.a.ny != stacks[k].a.ny || c.a.nz != stacks[k].a.nz) die(e.what + ": " + e.names[k] + " was not cropped like its stack");
+        e.unit_on[sl] = 1;
+        for (int y = 0; y < c.a.ny; ++y)
+          for (int x = 0; x < c.a.nx; ++x) e.grid[((size_t)sl * my + y) * mx + x] = (float)c.at(x, y, j);
+      }
+    if (e.labels) {
+      // the labels: the distinct values over the pixels that can count (the primary pixel is not -1, the stack has a label map)
+      std::set<float> seen;
+      for (int s = 0; s < ns; ++s) {
+        if (!e.unit_on[s]) continue;
+        for (size_t i = 0; i < (size_t)mx * my; ++i) {
+          const size_t g = (size_t)s * mx * my + i;
+          if (grid[g] == -1.0f) continue;
+          const float v = e.grid[g];
+          if (!(v >= 0.0f && v <= 65535.0f) || v != floorf(v))
+            die(e.what + ": " + e.names[srcs[s].stack] + " holds the value " + std::to_string(v) + ": labels are integers in 0..65535");
+          if (seen.insert(v).second && seen.size() > 64) die(e.what + ": more than 64 different labels");
+        }
+      }
+      e.label_values.assign(seen.begin(), seen.end());                   // ascending: ties go to the smallest label
+      if (e.label_values.empty()) die(e.what + ": no labelled pixel lies inside the mask");
+    }
+  }
+  if (!channels_dump.empty()) {
+    // test hook (tests/test_channel.py): {sets, ns, mx, my}, then per set {labels, number of labels}, unit_on [ns], the packed grid, the labels
+    FILE *f = fopen(channels_dump.c_str(), "wb");
+    if (!f) die("cannot write " + channels_dump);
+    const int hdr[4] = {(int)extras.size(), ns, mx, my};
+    fwrite(hdr, sizeof(int), 4, f);
+    for (auto &e : extras) {
+      const int h2[2] = {e.labels ? 1 : 0, (int)e.label_values.size()};
+      fwrite(h2, sizeof(int), 2, f);
+      fwrite(e.unit_on.data(), 1, e.unit_on.size(), f);
+      fwrite(e.grid.data(), sizeof(float), e.grid.size(), f);
+      fwrite(e.label_values.data(), sizeof(float), e.label_values.size(), f);
+    }
+    fclose(f);
+  }
   if (!dump_name.empty()) {
     // what the engine is about to receive, for the CPU tests (tests/test_prep_oracle.py compares it with the oracle's restatement
     // of CreateTemplate / SetMask / TransformMask / CropImage / MatchStackIntensities / MaskSlices): header, the template's
@@ -385,6 +532,7 @@ int main(int argc, char **argv) {
     svr::permute_rows(i2w, 16, order); svr::permute_rows(w2i, 16, order); svr::permute_rows(st, 16, order); svr::permute_rows(sti, 16, order);
     svr::permute_rows(dims, 3, order); svr::permute_rows(sizes_x, 1, order); svr::permute_rows(sizes_y, 1, order);
     svr::permute_rows(stack_index, 1, order); svr::permute_rows(sattr, 1, order); svr::permute_rows(T, 16, order);
+    for (auto &e : extras) { svr::permute_rows(e.grid, (size_t)mx * my, order); svr::permute_rows(e.unit_on, 1, order); }
     for (int &s : force_excluded) if (s >= 0 && s < ns) s = inv_order[s];
   }
   need_ctx();
@@ -680,6 +828,66 @@ int main(int argc, char **argv) {
       }
     }
     clk.mark("slice report, simulated stacks");
+  }
+  if (!extras.empty()) {
+    // The second images into the reconstructed space (not in the reference's main() but for --manualMask, reconstruction.cc:1240-1250).  The
+    // volume is on disk: nothing from here on can reach it.  Every rank scatters its own slices with the weights the last SR iteration
+    // would scatter with, the ranks' sums are brought together (svrh_channel_reconstruct), and rank 0 divides or votes.
+    const size_t nvv = (size_t)tattr.nx * tattr.ny * tattr.nz;
+    double t_sr = 0.0, t_scatter = 0.0;
+    int n_scatter = 0;
+    if (clk.on) {
+      // the yardstick, from the same run: one SR scatter of rank 0's slices (host clock around the blocking call; addon | cmap are free now)
+      const auto t0 = std::chrono::steady_clock::now();
+      ENG(svr_superresolution_backproject(ctx, nullptr));
+      t_sr = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    auto scatter = [&](ExtraSet &e, int flags, float match) {
+      std::vector<double> t(nr, 0.0);
+      par([&](int r) {
+        const size_t o = (size_t)rlo[r];
+        const auto t0 = std::chrono::steady_clock::now();
+        HOSTR(r, svrh_channel_reconstruct(hosts[r], e.grid.data() + o * mx * my, e.unit_on.data() + o, flags, match));
+        t[r] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      });
+      t_scatter += *std::max_element(t.begin(), t.end());
+      ++n_scatter;
+    };
+    // covered voxels (cover[v] > 0) and the values there, from the downloaded volumes
+    auto say = [&](const std::string &what, const std::string &path, const std::vector<float> &v, const std::vector<float> &cover) {
+      size_t cnt = 0;
+      double lo = INFINITY, hi = -INFINITY, sum = 0;
+      for (size_t i = 0; i < v.size(); ++i)
+        if (cover[i] > 0.0f) { ++cnt; lo = std::min(lo, (double)v[i]); hi = std::max(hi, (double)v[i]); sum += v[i]; }
+      if (cnt) fprintf(stderr, "%s %s: %zu covered voxels, min %.9g max %.9g mean %.9g\n", what.c_str(), path.c_str(), cnt, lo, hi, sum / (double)cnt);
+      else fprintf(stderr, "%s %s: no covered voxel\n", what.c_str(), path.c_str());
+    };
+    for (auto &e : extras) {
+      std::vector<float> out(nvv), cover(nvv);
+      if (!e.labels) {
+        scatter(e, 0, 0.0f);
+        ENG(svr_channel_finish(ctx, 0.0f, out.data()));
+        ENG(svr_debug_get(ctx, SVR_BUF_CONFIDENCE_MAP, cover.data(), nvv * sizeof(float)));          // den: where it is positive a slice reached
+        if (svr_nifti_write(e.out.c_str(), &tattr, out.data(), err)) die(e.out + ": " + err);
+        say(e.what, e.out, out, cover);
+      } else {
+        for (size_t k = 0; k < e.label_values.size(); ++k) {
+          scatter(e, SVR_CHANNEL_INDICATOR, e.label_values[k]);
+          ENG(svr_channel_vote(ctx, e.label_values[k], k == 0));
+        }
+        ENG(svr_channel_vote_fetch(ctx, 0.0f, out.data(), cover.data()));                            // (the confidence is positive exactly where a slice reached)
+        if (svr_nifti_write(e.out.c_str(), &tattr, out.data(), err)) die(e.out + ": " + err);
+        say(e.what + " (" + std::to_string(e.label_values.size()) + " labels)", e.out, out, cover);
+        if (!e.conf.empty()) {
+          if (svr_nifti_write(e.conf.c_str(), &tattr, cover.data(), err)) die(e.conf + ": " + err);
+          say("--labelConfidence", e.conf, cover, cover);
+        }
+      }
+    }
+    if (clk.on)
+      fprintf(stderr, "[timing] %d channel / label scatters, %.3f ms each (upload, scatter%s; slowest rank, host clock); one SR scatter of rank 0's slices %.3f ms\n",
+              n_scatter, 1e3 * t_scatter / std::max(1, n_scatter), nr > 1 ? ", all-reduce" : "", 1e3 * t_sr);
+    clk.mark("channels, labels");
   }
   if (debug) {                                                           // SaveTransformations, RG.cc:4903-4915
     const size_t cut = output.find_last_of('/');

@@ -436,6 +436,7 @@ int svr_mstep_estep_device(svr_ctx *ctx, int iter, float step, void **send, void
                        ctx->d_simweights, ctx->d_scales, ctx->disable_bias ? (const float *)nullptr : ctx->d_bias, 0.0f, 0.0f,
                        0.0f, (int)(ctx->sx * ctx->sy), ctx->d_weights, ctx->d_partial, ctx->pvr, ctx->d_em);
     KCHK("k_estep");
+    ctx->have_em = true;
     hipLaunchKernelGGL(k_potential_pack, dim3(nblk(p.maxn)), dim3(256), 0, ctx->stream, ctx->d_partial, (int)ctx->ns, ctx->chunks, ctx->d_tmp_ns,
                        ctx->d_scales_host_copy, ctx->d_slice_inside, p.maxn, p.d_send);
     KCHK("k_potential_pack");

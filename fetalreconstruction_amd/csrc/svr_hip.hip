@@ -155,6 +155,11 @@ struct PsfArgs {
   // coefficient table (COEFF instantiations): the evaluated taps of every live unit of every PSF pixel, kept in HBM
   const float4 *coeff;        // [pixel id][16 units][4 tap quads][16 rows] float4
   const uint32_t *coeff_id;   // slice-grid index -> pixel id
+  // channel scatter (k_cell_factors mode 3, svr_channel.inc): a float per slice pixel that is not the primary image
+  const float *channel;
+  const unsigned char *unit_on;   // [slice] 0 = the slice has no such channel; NULL = every slice has
+  int ch_flags;                   // SVR_CHANNEL_INDICATOR: the scattered value is (channel == ch_match) ? 1 : 0
+  float ch_match;
 };
 
 // per-pixel state shared by all modes
@@ -1241,6 +1246,10 @@ struct svr_ctx {
   float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
   double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
   double *d_qual_partial = nullptr, *d_qual_sums = nullptr;   // svr_slice_quality (svr_quality.inc): likewise
+  float *d_channel = nullptr;            // svr_channel_scatter (svr_channel.inc): the channel and its per-slice switches, likewise freed before the call returns
+  unsigned char *d_unit_on = nullptr;
+  float *d_vote_best = nullptr, *d_vote_label = nullptr;      // svr_channel_vote: the running maximum and its label, [nv] each, from the first vote to svr_channel_vote_fetch
+  bool have_em = false;                  // d_weights hold EM posteriors (svr_initialize_em_values or a later E-step; a test's svr_debug_set)
   float *d_seed_src = nullptr, *d_seed_out = nullptr;          // svr_resample_to_reconstruction (svr_seed.inc): likewise
   double *d_seed_partial = nullptr;
   int last_quality_chunks = -1;          // chunks per slice of the last svr_slice_quality (read-only option "quality_chunks"; -1 = not launched yet)
@@ -1320,7 +1329,8 @@ void cell_free(CellState *c);
 // The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
 // of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  The buffers of
 // svr_stack_motion (svr_motion.inc) cache nothing between calls -- they are freed before the call returns -- and have no line there;
-// nor have those of svr_slice_quality (svr_quality.inc) and svr_resample_to_reconstruction (svr_seed.inc).
+// nor have those of svr_slice_quality (svr_quality.inc) and svr_resample_to_reconstruction (svr_seed.inc), nor the channel buffer of
+// svr_channel_scatter (svr_channel.inc); the vote arrays of svr_channel_vote live from the first vote to the fetch and have one.
 enum Change : unsigned {
   CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
   CH_TAPS = 1u << 1,              // new slice constants, generatePSFVolume: the table and the cell lists
@@ -1880,6 +1890,7 @@ void invalidate(svr_ctx *ctx, unsigned ch) {
   if (ch & (CH_VOLUME_GRID | CH_MASK_BLUR)) ctx->maskC_valid = false;
   if (ch & CH_VOLUME_VALUES) ctx->vol_clean[ctx->recon_cur == ctx->d_recon_new ? 1 : 0] = false;
   if (ch & (CH_VOLUME_GRID | CH_SCATTER_TARGETS)) ctx->cmap_from_scatter = false;
+  if (ch & CH_VOLUME_GRID) { free_dev(ctx->d_vote_best); free_dev(ctx->d_vote_label); }   // (a vote in flight was over the old grid)
 }
 
 // The tile shape of the unit gather (fwd_unit_kernel: fwd_mode 1, and the coefficient table's gather) from the geometry, not from a
@@ -2287,6 +2298,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
   free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
   free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums);
+  free_dev(ctx->d_channel); free_dev(ctx->d_unit_on); free_dev(ctx->d_vote_best); free_dev(ctx->d_vote_label);
   free_dev(ctx->d_seed_src); free_dev(ctx->d_seed_out); free_dev(ctx->d_seed_partial);
   free_dev(ctx->d_coeff); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff_order);
   reg_free(ctx->reg);
@@ -2468,6 +2480,7 @@ int svr_init_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const float d
   ctx->sx = size[0]; ctx->sy = size[1]; ctx->ns = size[2];
   ctx->np = np;
   ctx->have_slices = false; ctx->have_sim = false; ctx->have_scales = false; ctx->have_dims = false; ctx->have_mats = false;
+  ctx->have_em = false;
   ctx->n_active = ctx->n_psf = 0;
   invalidate(ctx, CH_SLICE_GEOMETRY | CH_SLICE_PIXELS | CH_TABLE_OFF);
   free_dev(ctx->d_coeff_id);
@@ -2829,6 +2842,7 @@ int svr_initialize_em_values(svr_ctx *ctx) {
   NEED(ctx->have_slices, "slices not filled");
   hipLaunchKernelGGL(k_init_em, dim3(nblk(ctx->np)), dim3(256), 0, ctx->stream, ctx->d_slices, ctx->d_weights, ctx->np, ctx->pvr);
   KCHK("k_init_em");
+  ctx->have_em = true;
   if (!ctx->disable_bias) {                              // RC.cu:3305-3309
     int r = ensure_bias_buffers(ctx);
     if (r) return r;
@@ -2870,6 +2884,7 @@ int launch_estep(svr_ctx *ctx, float m, float sigma, float mix, const float *em)
                      ctx->d_simweights, ctx->d_scales, ctx->disable_bias ? (const float *)nullptr : ctx->d_bias, m, sigma,
                      mix, (int)(ctx->sx * ctx->sy), ctx->d_weights, ctx->d_partial, ctx->pvr, em);
   KCHK("k_estep");
+  ctx->have_em = true;
   hipLaunchKernelGGL(k_potential_finish, dim3(nblk(ctx->ns, 64)), dim3(64), 0, ctx->stream, ctx->d_partial,
                      (int)ctx->ns, ctx->chunks, ctx->d_tmp_ns);
   KCHK("k_potential_finish");
@@ -3433,6 +3448,7 @@ int svr_debug_set(svr_ctx *ctx, int which, const void *host_in, size_t bytes) {
   invalidate(ctx, which == SVR_BUF_SLICES ? CH_SLICE_PIXELS : which == SVR_BUF_PSF_SUMS ? CH_PSF_SUMS : which == SVR_BUF_MASK ? CH_MASK
                   : which == SVR_BUF_RECONSTRUCTED ? CH_VOLUME_VALUES : which == SVR_BUF_ADDON || which == SVR_BUF_CONFIDENCE_MAP ? CH_SCATTER_TARGETS : 0u);
   if (which == SVR_BUF_SIMSLICES) ctx->have_sim = true;   // (a test's own forward projection: svr_slice_quality takes it)
+  if (which == SVR_BUF_WEIGHTS) ctx->have_em = true;      // (a test's own posteriors: svr_channel_scatter takes them)
   if (which == SVR_BUF_SLICES) return build_list(ctx, false);
   return SVR_OK;
 }
@@ -3874,4 +3890,5 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 #include "svr_motion.inc"
 #include "svr_quality.inc"
 #include "svr_seed.inc"
+#include "svr_channel.inc"
 #include "svr_em.inc"

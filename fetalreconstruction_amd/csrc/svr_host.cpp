@@ -167,6 +167,16 @@ class irtkReconstruction {
     return 0;
   }
 
+  // A channel through this rank's slices with the weights SuperresolutionGPU would scatter with; sharded, num | den are then summed over
+  // the ranks the way the non-slab SR update sums addon | cmap: every rank holds the same pair and finishes or votes on its own
+  int ChannelReconstruct(const float *channel_local, const unsigned char *unit_on_local, int flags, float match) {
+    const float *sw;
+    if (int rc = em.scatter_weights(&sw)) return rc;
+    ENG(svr_channel_scatter(reconstructionGPU, channel_local, unit_on_local, sw, flags, match));
+    if (sh.on) ENG(sh.allreduce_pair(SVR_BUF_ADDON, 2 * svr_volume_voxels(reconstructionGPU)));
+    return 0;
+  }
+
   int MaskVolumeGPU() { ENG(svr_mask_volume(reconstructionGPU)); return 0; }   // RG.cc:5319-5323
 
   int ScaleVolumeGPU() {
@@ -375,6 +385,10 @@ int svrh_set_bias_options(svrh_recon *r, int global_bias_correction, double low_
 }
 int svrh_bias_gpu(svrh_recon *r) { return r->impl.BiasGPU(); }
 int svrh_normalise_bias_gpu(svrh_recon *r, int iter) { return r->impl.NormaliseBiasGPU(iter); }
+int svrh_channel_reconstruct(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int flags, float match) {
+  if (!r) return SVR_E_ARG;
+  return r->impl.ChannelReconstruct(channel_local, unit_on_local, flags, match);
+}
 int svrh_initialize_em_values_gpu(svrh_recon *r) { return r->impl.InitializeEMValuesGPU(); }
 int svrh_gaussian_reconstruction_gpu(svrh_recon *r) { return r->impl.GaussianReconstructionGPU(); }
 int svrh_simulate_slices_gpu(svrh_recon *r) { return r->impl.SimulateSlicesGPU(); }

@@ -25,6 +25,7 @@ BUF_SLICES, BUF_WEIGHTS, BUF_SIMSLICES, BUF_SIMWEIGHTS, BUF_PSF_SUMS, BUF_BIAS =
 BUF_SIMINSIDE, BUF_VOXEL_COUNT = 20, 21
 T_BACKPROJECT, T_FORWARD, T_GAUSS, T_REGULARIZE, T_ESTEP, T_MSTEP, T_SCALE, T_REGISTER = range(8)
 RESAMPLE_INSTALL, RESAMPLE_SCALE = 1, 2                # SVR_RESAMPLE_* (include/svr_hip.h)
+CHANNEL_INDICATOR = 1                                  # SVR_CHANNEL_INDICATOR
 REG_TARGETS, REG_SUM_A, REG_CNT_A, REG_SUM_B, REG_CNT_B, REG_MOMENTS, REG_SIMILARITIES, REG_GRADIENT, REG_ACTIVE = range(9)   # enum svr_reg_state
 TIMER_NAMES = ("backproject", "forward", "gauss", "regularize", "estep", "mstep", "scale", "register", "allreduce", "exchange_host", "coeff_build", "reduce_scatter", "allgather",
                "backproject_table", "forward_table", "forward_store", "backproject_store")
@@ -48,6 +49,7 @@ EXPORTS = [
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_reg_get", "svr_pvr_cc_patches", "svr_pvr_register_patches",
     "svr_slab_plan", "svr_slab_rs_pack", "svr_slab_update", "svr_slab_finish", "svr_stream_sync",
     "svr_get_scale_vector", "svr_adopt_scale_vector", "svr_get_slice_inside", "svr_mstep_estep", "svr_mstep_sums_fetch", "svr_mstep_partial", "svr_mstep_estep_ranks",
+    "svr_channel_scatter", "svr_channel_finish", "svr_channel_vote", "svr_channel_vote_fetch",
 ]
 
 
@@ -494,6 +496,40 @@ class Reconstruction:
         self._ck(self._lib.svr_resample_to_reconstruction(self._h, _u3(a.shape[::-1]), _p(a), _p(m), C.c_float(padding), int(flags),
                                                           C.c_float(1.0 if scale is None else scale), None if out is None else _p(out), _p(stats)))
         return out, stats
+
+    # ---- a second image through the run's motion and weights (csrc/svr_channel.inc) ------------------------------------------
+    def channel_scatter(self, channel, unit_on=None, slice_weights=None, indicator=False, match=0.0):
+        """svr_channel_scatter: channel float32 [ns][sy][sx] -> num | den in BUF_ADDON | BUF_CONFIDENCE_MAP (read them with debug_get).
+        unit_on: a byte per slice (0 = the slice has no such channel) or None; slice_weights: as SuperresolutionBackproject's;
+        indicator: scatter (channel == match) instead of the channel's value."""
+        if not self.sgrid:
+            raise SvrError("channel_scatter: initStorageVolumes first")
+        c = None if channel is None else _f32(channel)
+        if c is not None and c.size != int(np.prod(self.sgrid)):
+            raise SvrError(f"channel_scatter: expected {self.sgrid}, got {c.shape}")
+        u = None if unit_on is None else np.ascontiguousarray(unit_on, np.uint8)
+        if u is not None and u.size != self.sgrid[0]:
+            raise SvrError("channel_scatter: one unit_on byte per slice expected")
+        w = None if slice_weights is None else _f32(slice_weights)
+        self._ck(self._lib.svr_channel_scatter(self._h, None if c is None else _p(c), None if u is None else _p(u), None if w is None else _p(w),
+                                               CHANNEL_INDICATOR if indicator else 0, C.c_float(match)))
+
+    def channel_finish(self, background=0.0, want_volume=True):
+        """svr_channel_finish: num / den where den > 0, `background` elsewhere, in place in BUF_ADDON -> the volume (flat) or None"""
+        out = np.empty(int(np.prod(self.vsize)), np.float32) if want_volume else None
+        self._ck(self._lib.svr_channel_finish(self._h, C.c_float(background), None if out is None else _p(out)))
+        return out
+
+    def channel_vote(self, label, first):
+        """svr_channel_vote: the label whose indicator scatter is in BUF_ADDON | BUF_CONFIDENCE_MAP takes the voxels where it beats the best so far"""
+        self._ck(self._lib.svr_channel_vote(self._h, C.c_float(label), int(bool(first))))
+
+    def channel_vote_fetch(self, background_label=0.0):
+        """svr_channel_vote_fetch -> (labels, confidence), flat float32; ends the vote"""
+        n = int(np.prod(self.vsize)) if self.vsize else 0
+        lab, conf = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._ck(self._lib.svr_channel_vote_fetch(self._h, C.c_float(background_label), _p(lab), _p(conf)))
+        return lab, conf
 
     # ---- GPU slice-to-volume registration (RC.cuh:326-338) ------------------------------------
     def initRegStorageVolumes(self, W, H, ns, dim=(1.0, 1.0, 1.0)):

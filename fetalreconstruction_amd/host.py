@@ -23,7 +23,7 @@ HOST_EXPORTS = [
     "svrh_superresolution_gpu", "svrh_mstep_gpu", "svrh_mask_volume_gpu", "svrh_scale_volume_gpu",
     "svrh_sr_iteration", "svrh_reconstruct_iteration", "svrh_get_state", "svrh_set_bias_correction", "svrh_set_bias_options", "svrh_bias_gpu",
     "svrh_normalise_bias_gpu", "svrh_prepare_registration_slices", "svrh_slice_to_volume_registration_gpu",
-    "svrh_get_registration_slices", "svrh_force_collectives", "svrh_set_slab_update", "svrh_set_unit_order",
+    "svrh_get_registration_slices", "svrh_force_collectives", "svrh_set_slab_update", "svrh_set_unit_order", "svrh_channel_reconstruct",
 ]
 PVR_HOST_EXPORTS = ["pvrh_create", "pvrh_destroy", "pvrh_last_error", "pvrh_initialize_em_values", "pvrh_initialize_robust_statistics",
                     "pvrh_estep", "pvrh_mstep", "pvrh_scale", "pvrh_reconstruct_iteration", "pvrh_register_patches", "pvrh_get_state",
@@ -284,6 +284,13 @@ class irtkReconstruction:
 
     def NormaliseBiasGPU(self, it):
         self._ck(self._lib.svrh_normalise_bias_gpu(self._h, int(it)))
+
+    def ChannelReconstruct(self, channel_local, unit_on_local=None, indicator=False, match=0.0):
+        """svrh_channel_reconstruct: this rank's part of a channel -> num | den in addon | cmap of the engine, summed over the ranks"""
+        c = np.ascontiguousarray(channel_local, np.float32)
+        u = None if unit_on_local is None else np.ascontiguousarray(unit_on_local, np.uint8)
+        self._ck(self._lib.svrh_channel_reconstruct(self._h, c.ctypes.data_as(C.c_void_p), None if u is None else u.ctypes.data_as(C.c_void_p),
+                                                    1 if indicator else 0, C.c_float(match)))
 
     def InitializeEMValuesGPU(self):
         self._ck(self._lib.svrh_initialize_em_values_gpu(self._h))

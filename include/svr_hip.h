@@ -350,6 +350,30 @@ int svr_slice_quality(svr_ctx *ctx, double *sums /* [ns][SVR_SLICE_QUALITY_SUMS]
 int svr_resample_to_reconstruction(svr_ctx *ctx, const uint32_t src_size[3], const float *src, const double src_from_recon[12], float padding,
                                    int flags, float scale, float *out_or_null, double stats[5]);
 
+/* A second image on the slice grid carried into the volume with the run's motion and weights (csrc/svr_channel.inc; the command line's
+ * --channelStacks, --labelStacks and the reference's --manualMask, reconstruction.cc:1240-1250).  channel: host memory, a float per slice
+ * pixel in the layout of svr_fill_slices.  Over the pixels whose primary slice pixel is not -1, whose v_PSF_sums is not 0 and whose
+ * slice has unit_on != 0 (unit_on: a byte per slice, or NULL = every slice; the channel's own value never decides),
+ *   num(v) = sum coeff(p, v) f1_p x_p,  den(v) = sum coeff(p, v) f1_p,  f1_p = weights[p] * slice_weights[s] / v_PSF_sums[p]
+ * with x_p = channel[p], or with SVR_CHANNEL_INDICATOR x_p = (channel[p] == match) ? 1 : 0, land in SVR_BUF_ADDON | SVR_BUF_CONFIDENCE_MAP
+ * through the SR iteration's scatter without atomics (the coefficient table when it is valid): the same bits on every call.  No intensity
+ * scale, stack factor or bias field is applied.  slice_weights: as svr_superresolution_backproject's, NULL keeps the device's.  The
+ * call covers THIS context's slices; a sharded run all-reduces the pair afterwards (svrh_channel_reconstruct).  Needs what an SR scatter
+ * needs -- volume, mask, slices, matrices, v_PSF_sums, EM weights -- and the cell scatter (back_mode 5): there is no fallback onto the
+ * atomic scatters.  Refused with a message, never a fault: a NULL channel, an unknown flag, a patch-based (pvr) context, missing state, a
+ * geometry the cell lists cannot hold.  The channel's device copy is freed before the call returns.
+ * svr_channel_finish: addon = den > 0 ? num / den : background, in place; out_or_null: the result, [nv] floats.
+ * svr_channel_vote: one label of an arg-max over indicator scatters.  P = num / den where den > 0; the running pair {best, label} is
+ *   replaced when `first` is set (which also allocates the two [nv] arrays) or P > best -- strictly, so a tie stays with the label voted
+ *   first: visit the labels in ascending order and ties go to the smallest.
+ * svr_channel_vote_fetch: voxels with den <= 0 get background_label and confidence 0; downloads the labels and the winning P (either
+ *   pointer may be NULL) and frees the two arrays.  Without a vote in flight: an error with a message. */
+#define SVR_CHANNEL_INDICATOR 1
+int svr_channel_scatter(svr_ctx *ctx, const float *channel, const unsigned char *unit_on, const float *slice_weights, int flags, float match);
+int svr_channel_finish(svr_ctx *ctx, float background, float *out_or_null);
+int svr_channel_vote(svr_ctx *ctx, float label, int first);
+int svr_channel_vote_fetch(svr_ctx *ctx, float background_label, float *labels_or_null, float *confidence_or_null);
+
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::
  * PrepareRegistrationSlices / SliceToVolumeRegistrationGPU (irtkReconstructionGPU.cc:2104-2290).

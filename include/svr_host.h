@@ -107,6 +107,11 @@ int svrh_set_bias_correction(svrh_recon *r, int enable, double sigma_bias);
 int svrh_set_bias_options(svrh_recon *r, int global_bias_correction, double low_intensity_cutoff);
 int svrh_bias_gpu(svrh_recon *r);
 int svrh_normalise_bias_gpu(svrh_recon *r, int iter);
+/* svr_channel_scatter (include/svr_hip.h) over this rank's slices -- channel_local / unit_on_local: the rank's own part, in its own
+ * numbering -- with the slice weights SuperresolutionGPU would scatter with; in a sharded run num | den (SVR_BUF_ADDON |
+ * SVR_BUF_CONFIDENCE_MAP) are then all-reduced like the pair of the non-slab SR update, so every rank holds the same sums.  Collective.
+ * The caller finishes (svr_channel_finish) or votes (svr_channel_vote) on the engine. */
+int svrh_channel_reconstruct(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int flags, float match);
 
 int svrh_initialize_em_values_gpu(svrh_recon *r);
 int svrh_gaussian_reconstruction_gpu(svrh_recon *r);
