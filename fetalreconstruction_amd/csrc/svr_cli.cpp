@@ -37,6 +37,9 @@
 // co-registered acquisition, a label map, a manual mask -- into the reconstructed space after the volume has been written, with the final
 // slice transformations and the EM's weights (svr_channel_scatter, csrc/svr_channel.inc): cropped with their stack, cut into slices and
 // packed like the primaries, scattered through the SR iteration's scatter, divided by the weights (channels) or voted label by label.
+// --structural (a deviation: the reference leaves a slice out by its intensity residuals or --force_exclude only) lets every outer
+// iteration end with the slices' mean windowed SSIM against their simulation (svr_slice_ssim, csrc/svr_ssim.inc) and treats a slice that
+// falls out of its stack (svr_structural_decide) like a --force_exclude slice during the next one; it lives in svrh_reconstruct_iteration.
 // Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
 #include <functional>
 #include <set>
@@ -63,6 +66,9 @@ int main(int argc, char **argv) {
   bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
   std::string reference_name;                                             // --referenceVolume (main.cc:207; takes effect here)
   std::string report_name, sim_prefix;                                   // --sliceReport, --simulatedStacks (not reference options)
+  bool structural = false;                                                // --structural (not a reference option) and its four parameters
+  int st_radius = 3, st_min_pixels = 25;
+  double st_k = 3.0, st_min_drop = 0.1;
   std::vector<std::string> channel_names, label_names;                   // --channelStacks, --labelStacks (not reference options): a file or `none` per -i stack
   std::string channel_out, label_out, label_conf, manual_name, channels_dump;   // --channelOutput, --labelOutput, --labelConfidence, --manualMask, --dumpChannels
   bool have_channel_opt = false, have_label_opt = false;
@@ -122,6 +128,11 @@ int main(int argc, char **argv) {
     else if (o == "--dryRun") dry_run = true;
     else if (o == "--sliceReport") report_name = one();                   // not reference options: the reference's main() never calls SlicesInfo / SimulateStacks
     else if (o == "--simulatedStacks") sim_prefix = one();
+    else if (o == "--structural") structural = true;                      // not reference options: the reference leaves slices out by intensity residuals only
+    else if (o == "--structuralRadius") st_radius = atoi(one().c_str());
+    else if (o == "--structuralK") st_k = atof(one().c_str());
+    else if (o == "--structuralMinDrop") st_min_drop = atof(one().c_str());
+    else if (o == "--structuralMinPixels") st_min_pixels = atoi(one().c_str());
     else if (o == "--referenceVolume") reference_name = one();            // main.cc:207, 253-258: read there and (outside the T1 experiment) never used
     else if (o == "--channelStacks") { have_channel_opt = true; multi(channel_names); }   // not reference options: a second image per stack through the run's motion and weights
     else if (o == "--channelOutput") channel_out = one();
@@ -142,6 +153,17 @@ int main(int argc, char **argv) {
              "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix] [--referenceVolume file]\n"
              "       [--channelStacks f_1 .. f_N --channelOutput file] [--labelStacks f_1 .. f_N --labelOutput file [--labelConfidence file]]\n"
              "       [--manualMask file]\n"
+             "       [--structural [--structuralRadius 3] [--structuralK 3] [--structuralMinDrop 0.1] [--structuralMinPixels 25]]\n"
+             "  --structural            deviation from the reference, which leaves a slice out by its intensity residuals (or --force_exclude)\n"
+             "                          only: after the last SR iteration of every outer iteration, the mean of a windowed structural\n"
+             "                          similarity (SSIM; box window of (2 radius + 1)^2 pixels, radius 1 .. 7) between each slice and its\n"
+             "                          simulation is taken over the pixels the M-step counts, where at least half the window holds data.  A\n"
+             "                          slice with at least --structuralMinPixels such pixels whose mean lies further below its stack's median\n"
+             "                          than max(K 1.4826 MAD, MinDrop) is treated like a --force_exclude slice during the NEXT outer iteration,\n"
+             "                          and judged again at its end: registration still moves it, so a slice that registration repairs comes\n"
+             "                          back.  Stacks with fewer than 4 judged slices exclude nothing.  One stderr line per outer iteration\n"
+             "                          lists what was found.  With --sliceReport the report gets three more columns: ssim n_ssim structural\n"
+             "                          (1 = left out during the last outer iteration).  Not with --sfolder.  Without the option nothing changes.\n"
              "  --channelStacks f_1 .. f_N --channelOutput <file>\n"
              "                          deviation from the reference, which has no such option: a second image per -i stack (another echo, a\n"
              "                          quantitative or probability map), on its stack's grid; `none` = the stack has none.  After the volume\n"
@@ -201,6 +223,13 @@ int main(int argc, char **argv) {
   if (!sim_prefix.empty() && !sfolder.empty())
     die("--simulatedStacks puts every simulated slice back into the stack it was cut from; with --sfolder the slices come from files of "
         "their own and belong to no stack: use --sliceReport, or drop --sfolder");
+  if (structural && !sfolder.empty())
+    die("--structural compares every slice with the other slices of its stack; with --sfolder the slices come from files of their own and "
+        "belong to no stack: drop one or the other");
+  if (structural && (st_radius < 1 || st_radius > SVR_SSIM_MAX_RADIUS))
+    die("--structuralRadius must be 1 .. " + std::to_string(SVR_SSIM_MAX_RADIUS) + " (the window is (2 radius + 1)^2 pixels)");
+  if (structural && (!(st_k >= 0.0) || !(st_min_drop >= 0.0) || st_min_pixels < 0))
+    die("--structuralK, --structuralMinDrop and --structuralMinPixels must not be negative");
   if (dry_run && !reference_name.empty()) die("--dryRun makes no engine context and cannot resample a volume: drop --referenceVolume");
   if (use_nmi && use_gpu_reg)
     die("--useNMI selects normalised mutual information for the IRTK registration; the reference's GPU registration (--useGPUReg) is "
@@ -594,6 +623,7 @@ int main(int argc, char **argv) {
     HOSTR(r, svrh_set_bias_options(hosts[r], global_bias ? 1 : 0, low_intensity_cutoff));
     if (nr > 1 && svrh_set_unit_order(hosts[r], order.data())) die("svrh_set_unit_order failed");
     if (!force_excluded.empty()) svrh_set_force_excluded(hosts[r], force_excluded.data(), (int)force_excluded.size());
+    if (structural) HOSTR(r, svrh_set_structural(hosts[r], 1, st_radius, st_k, st_min_drop, st_min_pixels, stack_index.data()));
     if (use_gpu_reg) HOSTR(r, svrh_prepare_registration_slices(hosts[r], grid.data() + o * mx * my, mx, my, sattr.data() + o, resolution));
   });
   if (nr > 1)
@@ -702,6 +732,22 @@ int main(int argc, char **argv) {
     svrh_get_state(host, nullptr, nullptr, nullptr, nullptr, sc);
     fprintf(stderr, "iteration %d: sigma %.4g mix %.3f\n", it, sc[0], sc[1]);
     clk.mark("reconstruction iteration");
+    if (structural) {                                                     // what this iteration's evaluation found: in force during the next one
+      std::vector<double> q(ns);
+      std::vector<unsigned char> pend(ns);
+      HOSTR(0, svrh_get_structural(host, q.data(), nullptr, nullptr, pend.data()));
+      std::vector<int> judged(n, 0), left_out(n, 0), named;
+      for (int i = 0; i < ns; ++i) {                                      // slice i of the reference's order
+        const int s = inv_order[i];
+        if (q[s] == q[s]) ++judged[stack_index[s]];
+        if (pend[s]) { ++left_out[stack_index[s]]; named.push_back(i); }
+      }
+      fprintf(stderr, "structural, iteration %d:", it);
+      for (size_t k = 0; k < n; ++k) fprintf(stderr, " stack %zu judged %d excluded %d%s", k, judged[k], left_out[k], k + 1 < n ? "," : ";");
+      fprintf(stderr, " excluded slices:");
+      for (int i : named) fprintf(stderr, " %d", i);
+      fprintf(stderr, "%s\n", named.empty() ? " none" : "");
+    }
     if (save_slice_transformations) {
       // SaveSlices + SaveTransformations after every iteration (main.cc:1213-1217; RG.cc:4884-4892, 4903-4919), into the working
       // directory like the reference: slice<i>.nii.gz (the masked slice), croppedSliceTransformation<i>.dof (the slice's transformation)
@@ -749,6 +795,8 @@ int main(int argc, char **argv) {
     std::vector<float> scale_g(ns), weight_g(ns), sim;
     std::vector<unsigned char> inside(ns);
     std::vector<double> sums((size_t)ns * SVR_SLICE_QUALITY_SUMS, 0.0);
+    const bool report_ex = structural && !report_name.empty();           // three more columns: ssim n_ssim structural
+    std::vector<double> ssim_sums(report_ex ? 2 * (size_t)ns : 0, 0.0);
     if (!sim_prefix.empty()) sim.resize((size_t)ns * mx * my);
     par([&](int r) {                                                     // (collective: the other ranks' vectors may still be on their way)
       HOSTR(r, svrh_get_state(hosts[r], r ? nullptr : scale_g.data(), r ? nullptr : weight_g.data(), nullptr, nullptr, nullptr));
@@ -761,6 +809,10 @@ int main(int argc, char **argv) {
       const auto t1 = std::chrono::steady_clock::now();
       if (!report_name.empty()) ENGR(r, svr_slice_quality(ctxs[r], sums.data() + o * SVR_SLICE_QUALITY_SUMS));
       const auto t2 = std::chrono::steady_clock::now();
+      if (report_ex && nl > 0) {                                          // the run's own window and constants (svrh_structural_evaluate)
+        const double L = (double)vmax - (double)vmin;
+        ENGR(r, svr_slice_ssim(ctxs[r], st_radius, (0.01 * L) * (0.01 * L), (0.03 * L) * (0.03 * L), ssim_sums.data() + 2 * o, nullptr));
+      }
       if (!sim_prefix.empty()) ENGR(r, svr_debug_get(ctxs[r], SVR_BUF_SIMSLICES, sim.data() + o * mx * my, nl * mx * my * sizeof(float)));
       t_sim[r] = std::chrono::duration<double>(t1 - t0).count(); t_qual[r] = std::chrono::duration<double>(t2 - t1).count();
     });
@@ -772,16 +824,21 @@ int main(int argc, char **argv) {
       std::vector<int> r_stack(ns);
       std::vector<float> r_weight(ns), r_scale(ns);
       std::vector<unsigned char> r_inside(ns);
-      std::vector<double> r_p6(6 * (size_t)ns), r_sums(sums.size());
+      std::vector<double> r_p6(6 * (size_t)ns), r_sums(sums.size()), r_ssim(ssim_sums.size());
+      std::vector<unsigned char> in_force(report_ex ? ns : 0), r_force(report_ex ? ns : 0);
+      if (report_ex) HOSTR(0, svrh_get_structural(host, nullptr, nullptr, in_force.data(), nullptr));
       for (int i = 0; i < ns; ++i) {                                     // row i = slice i of the reference's order
         const int s = inv_order[i];
         r_stack[i] = stack_index[s]; r_weight[i] = weight_g[s]; r_scale[i] = scale_g[s]; r_inside[i] = inside[s];
         svrh_irtk_rigid_parameters(&T[16 * (size_t)s], &r_p6[6 * (size_t)i], nullptr);
         std::copy(sums.begin() + (size_t)s * SVR_SLICE_QUALITY_SUMS, sums.begin() + (size_t)(s + 1) * SVR_SLICE_QUALITY_SUMS,
                   r_sums.begin() + (size_t)i * SVR_SLICE_QUALITY_SUMS);
+        if (report_ex) { r_ssim[2 * (size_t)i] = ssim_sums[2 * (size_t)s]; r_ssim[2 * (size_t)i + 1] = ssim_sums[2 * (size_t)s + 1]; r_force[i] = in_force[s]; }
       }
-      if (svr_slice_report_write(report_name.c_str(), ns, r_stack.data(), r_weight.data(), r_inside.data(), r_scale.data(), r_p6.data(),
-                                 r_sums.data(), err))
+      if (report_ex ? svr_slice_report_write_ex(report_name.c_str(), ns, r_stack.data(), r_weight.data(), r_inside.data(), r_scale.data(),
+                                                r_p6.data(), r_sums.data(), r_ssim.data(), r_force.data(), err)
+                    : svr_slice_report_write(report_name.c_str(), ns, r_stack.data(), r_weight.data(), r_inside.data(), r_scale.data(), r_p6.data(),
+                                             r_sums.data(), err))
         die(report_name + ": " + err);
       // the three lists of EvaluateGPU, then what the weights alone do not say: how well each stack's kept slices match the volume
       const char *names[3] = {"Included", "Excluded", "Outside"};

@@ -1246,6 +1246,8 @@ struct svr_ctx {
   float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
   double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
   double *d_qual_partial = nullptr, *d_qual_sums = nullptr;   // svr_slice_quality (svr_quality.inc): likewise
+  double *d_ssim_partial = nullptr, *d_ssim_sums = nullptr;   // svr_slice_ssim (svr_ssim.inc): likewise
+  float *d_ssim_map = nullptr;
   float *d_channel = nullptr;            // svr_channel_scatter (svr_channel.inc): the channel and its per-slice switches, likewise freed before the call returns
   unsigned char *d_unit_on = nullptr;
   float *d_vote_best = nullptr, *d_vote_label = nullptr;      // svr_channel_vote: the running maximum and its label, [nv] each, from the first vote to svr_channel_vote_fetch
@@ -1329,7 +1331,7 @@ void cell_free(CellState *c);
 // The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
 // of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  The buffers of
 // svr_stack_motion (svr_motion.inc) cache nothing between calls -- they are freed before the call returns -- and have no line there;
-// nor have those of svr_slice_quality (svr_quality.inc) and svr_resample_to_reconstruction (svr_seed.inc), nor the channel buffer of
+// nor have those of svr_slice_quality (svr_quality.inc), svr_slice_ssim (svr_ssim.inc) and svr_resample_to_reconstruction (svr_seed.inc), nor the channel buffer of
 // svr_channel_scatter (svr_channel.inc); the vote arrays of svr_channel_vote live from the first vote to the fetch and have one.
 enum Change : unsigned {
   CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
@@ -2298,6 +2300,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
   free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
   free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums);
+  free_dev(ctx->d_ssim_partial); free_dev(ctx->d_ssim_sums); free_dev(ctx->d_ssim_map);
   free_dev(ctx->d_channel); free_dev(ctx->d_unit_on); free_dev(ctx->d_vote_best); free_dev(ctx->d_vote_label);
   free_dev(ctx->d_seed_src); free_dev(ctx->d_seed_out); free_dev(ctx->d_seed_partial);
   free_dev(ctx->d_coeff); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff_order);
@@ -3889,6 +3892,7 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 #include "svr_nmi.inc"
 #include "svr_motion.inc"
 #include "svr_quality.inc"
+#include "svr_ssim.inc"
 #include "svr_seed.inc"
 #include "svr_channel.inc"
 #include "svr_em.inc"

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -65,7 +66,42 @@ class irtkReconstruction {
     std::vector<unsigned char> x(ns, 0);
     for (int i : _force_excluded) if (i >= 0 && i < ns) x[i] = 1;
     for (int i : _small_slices) if (i >= 0 && i < ns) x[i] = 1;
+    for (size_t i = 0; i < _st_in_force.size(); ++i) if (_st_in_force[i]) x[i] = 1;
     return x;
+  }
+
+  // ---- structural slice exclusion (--structural; not in the reference: include/svr_host.h) ---------------------
+  bool _structural = false;
+  int _st_radius = 3, _st_min_pixels = 25;
+  double _st_k_mad = 3, _st_min_drop = 0.1;
+  std::vector<int> _st_stack;                          // the stack of every slice, this object's numbering
+  std::vector<unsigned char> _st_in_force, _st_pending;
+  std::vector<double> _st_q, _st_n;                    // the last evaluation: mean SSIM (nan: not judged) and the pixels counted
+
+  int StructuralEvaluate() {
+    if (!_structural) { err = "svrh_structural_evaluate: svrh_set_structural first"; return SVR_E_STATE; }
+    if (int rc = em.flush()) return rc;                // (settle: the device's scale vector is the newest; sharded: every rank's slice_inside)
+    const double L = _max_intensity - _min_intensity, c1 = (0.01 * L) * (0.01 * L), c2 = (0.03 * L) * (0.03 * L);
+    std::vector<double> sums(2 * (size_t)ns, 0.0);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (hi > lo) ENG(svr_slice_ssim(reconstructionGPU, _st_radius, c1, c2, sums.data() + 2 * (size_t)lo, nullptr));
+    if (getenv("SVR_CLI_TIMING"))                      // (the call blocks: the host clock around it is its cost)
+      fprintf(stderr, "[timing] svr_slice_ssim, %d slices, radius %d: %.3f ms (host clock)\n", hi - lo, _st_radius,
+              1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    if (sh.on) ENG(sh.coll.allreduce_host(sh.coll.user, sums.data(), 2 * ns, 0));   // one non-zero contributor per entry: exact
+    std::vector<unsigned char> eligible(ns);
+    for (int i = 0; i < ns; ++i) eligible[i] = em.inside[i] ? 1 : 0;
+    for (int i : _force_excluded) if (i >= 0 && i < ns) eligible[i] = 0;
+    for (int i : _small_slices) if (i >= 0 && i < ns) eligible[i] = 0;
+    _st_q.assign(ns, 0.0);
+    _st_pending.assign(ns, 0);
+    for (int i = 0; i < ns; ++i) _st_n[i] = sums[2 * (size_t)i];
+    if (int rc = svr_structural_decide(ns, _st_stack.data(), sums.data(), eligible.data(), _st_min_pixels, _st_k_mad, _st_min_drop,
+                                       _st_q.data(), _st_pending.data())) {
+      err = "svr_structural_decide: bad argument";
+      return rc;
+    }
+    return 0;
   }
 
   // RG.h:605-612
@@ -118,6 +154,7 @@ class irtkReconstruction {
     for (int i = 0; i < ns; ++i)
       if (!em.inside[i]) em.weight[i] = 0;
     for (size_t i = 0; i < _force_excluded.size(); i++) em.weight[_force_excluded[i]] = 0;
+    for (size_t i = 0; i < _st_in_force.size(); ++i) if (_st_in_force[i]) em.weight[i] = 0;   // --structural: as a force-excluded slice
     em.cls.var = 0.025f;
     em.mix = 0.9f;
     em.cls.mix = 0.9f;
@@ -338,6 +375,7 @@ class irtkReconstruction {
   // reconstruction.cc:930-1140 (one outer iteration after registration)
   int reconstruct_iteration(int rec_iterations) {
     int rc;
+    if (_structural) _st_in_force = _st_pending;         // what the last outer iteration found holds for this one
     if ((rc = InitializeEMValuesGPU())) return rc;
     if ((rc = GaussianReconstructionGPU())) return rc;
     if ((rc = SimulateSlicesGPU())) return rc;
@@ -345,6 +383,7 @@ class irtkReconstruction {
     if ((rc = EStepGPU())) return rc;
     for (int i = 0; i < rec_iterations; ++i)
       if ((rc = sr_iteration(i))) return rc;
+    if (_structural && (rc = StructuralEvaluate())) return rc;   // (the slices were projected from the newest volume by the last SR iteration)
     return MaskVolumeGPU();
   }
 #undef ENG
@@ -402,6 +441,35 @@ int svrh_mask_volume_gpu(svrh_recon *r) { return r->impl.MaskVolumeGPU(); }
 int svrh_scale_volume_gpu(svrh_recon *r) { return r->impl.ScaleVolumeGPU(); }
 int svrh_sr_iteration(svrh_recon *r, int i) { return r->impl.sr_iteration(i); }
 int svrh_reconstruct_iteration(svrh_recon *r, int n) { return r->impl.reconstruct_iteration(n); }
+
+int svrh_set_structural(svrh_recon *r, int enable, int radius, double k_mad, double min_drop, int min_pixels, const int *stack_index_global) {
+  if (!r) return SVR_E_ARG;
+  svr::irtkReconstruction &o = r->impl;
+  if (enable && (!stack_index_global || radius < 1 || radius > SVR_SSIM_MAX_RADIUS || !(k_mad >= 0.0) || !(min_drop >= 0.0) || min_pixels < 0)) {
+    o.err = "svrh_set_structural: a stack index per slice, a radius of 1 .. 7 and a k, drop and pixel count that are not negative";
+    return SVR_E_ARG;
+  }
+  o._structural = enable != 0;
+  o._st_in_force.assign(o.ns, 0);
+  o._st_pending.assign(o.ns, 0);
+  o._st_q.assign(o.ns, NAN);
+  o._st_n.assign(o.ns, 0.0);
+  if (!enable) { o._st_in_force.clear(); return SVR_OK; }
+  o._st_radius = radius; o._st_k_mad = k_mad; o._st_min_drop = min_drop; o._st_min_pixels = min_pixels;
+  o._st_stack.assign(stack_index_global, stack_index_global + o.ns);
+  return SVR_OK;
+}
+int svrh_structural_evaluate(svrh_recon *r) { return r ? r->impl.StructuralEvaluate() : SVR_E_ARG; }
+int svrh_get_structural(svrh_recon *r, double *q, double *n_ssim, unsigned char *in_force, unsigned char *pending) {
+  if (!r) return SVR_E_ARG;
+  svr::irtkReconstruction &o = r->impl;
+  if (!o._structural) { o.err = "svrh_get_structural: svrh_set_structural first"; return SVR_E_STATE; }
+  if (q) std::copy(o._st_q.begin(), o._st_q.end(), q);
+  if (n_ssim) std::copy(o._st_n.begin(), o._st_n.end(), n_ssim);
+  if (in_force) std::copy(o._st_in_force.begin(), o._st_in_force.end(), in_force);
+  if (pending) std::copy(o._st_pending.begin(), o._st_pending.end(), pending);
+  return SVR_OK;
+}
 
 int svrh_prepare_registration_slices(svrh_recon *r, const float *slices, int sx, int sy, const svr_image_attr *attrs,
                                      double recon_voxel) {

@@ -425,16 +425,22 @@ void svr_slice_quality_derive(const double s[SVR_SLICE_QUALITY_SUMS], double der
 
 // The per-slice report of --sliceReport: the twelve columns of irtkReconstruction::SlicesInfo (irtkReconstructionGPU.cc:4937-4975)
 // under its names and in its order, then n_px, n and the derived values of the slice's sums.  Tab-separated, one row per slice
-// in the order of the arrays; nan is written as `nan` whatever its sign bit.
-int svr_slice_report_write(const char *path, int n_slices, const int *stack_index, const float *slice_weight, const unsigned char *slice_inside,
-                           const float *scale, const double *params6, const double *sums, char err[256]) {
+// in the order of the arrays; nan is written as `nan` whatever its sign bit.  With the sums of svr_slice_ssim and the flags of
+// --structural (svr_slice_report_write_ex) three more columns follow: ssim = S ssim / n_ssim (nan when n_ssim = 0), n_ssim, structural.
+int svr_slice_report_write_ex(const char *path, int n_slices, const int *stack_index, const float *slice_weight, const unsigned char *slice_inside,
+                              const float *scale, const double *params6, const double *sums, const double *ssim_sums_or_null,
+                              const unsigned char *structural_or_null, char err[256]) {
   if (!path || n_slices < 0 || (n_slices > 0 && (!stack_index || !slice_weight || !slice_inside || !scale || !params6 || !sums)))
     return set_err(err, "svr_slice_report_write: missing argument");
+  if ((ssim_sums_or_null != nullptr) != (structural_or_null != nullptr))
+    return set_err(err, "svr_slice_report_write_ex: the SSIM sums and the structural flags come together or not at all");
+  const bool ex = ssim_sums_or_null != nullptr;
   FILE *f = fopen(path, "w");
   if (!f) return set_err(err, std::string("cannot create ") + path);
   auto num = [&](double v) { if (v != v) fputs("\tnan", f); else fprintf(f, "\t%.9g", v); };
   fputs("stack_index\tincluded\texcluded\toutside\tweight\tscale\tTranslationX\tTranslationY\tTranslationZ\tRotationX\tRotationY\tRotationZ"
-        "\tn_px\tn\tncc\trmse\tmae\tmean_weight\n", f);
+        "\tn_px\tn\tncc\trmse\tmae\tmean_weight", f);
+  fputs(ex ? "\tssim\tn_ssim\tstructural\n" : "\n", f);
   for (int i = 0; i < n_slices; ++i) {
     const bool inside = slice_inside[i] != 0, kept = slice_weight[i] >= 0.5f;
     fprintf(f, "%d\t%d\t%d\t%d", stack_index[i], (kept && inside) ? 1 : 0, (!kept && inside) ? 1 : 0, inside ? 0 : 1);
@@ -445,10 +451,60 @@ int svr_slice_report_write(const char *path, int n_slices, const int *stack_inde
     svr_slice_quality_derive(s, d);
     fprintf(f, "\t%.0f\t%.0f", s[0], s[1]);
     for (int k = 0; k < 4; ++k) num(d[k]);
+    if (ex) {
+      const double n = ssim_sums_or_null[2 * (size_t)i], S = ssim_sums_or_null[2 * (size_t)i + 1];
+      num(n > 0 ? S / n : NAN);
+      fprintf(f, "\t%.0f\t%d", n, structural_or_null[i] ? 1 : 0);
+    }
     fputc('\n', f);
   }
   const bool ok = !ferror(f);
   return (fclose(f) == 0 && ok) ? SVR_OK : set_err(err, "write failed");
+}
+
+int svr_slice_report_write(const char *path, int n_slices, const int *stack_index, const float *slice_weight, const unsigned char *slice_inside,
+                           const float *scale, const double *params6, const double *sums, char err[256]) {
+  return svr_slice_report_write_ex(path, n_slices, stack_index, slice_weight, slice_inside, scale, params6, sums, nullptr, nullptr, err);
+}
+
+// The decision of --structural (include/svr_host.h states the rule): per stack, a slice whose mean SSIM lies further below the
+// stack's median than max(k_mad 1.4826 MAD, min_drop) is excluded.  Pure host code, in double; a stack's judged slices are sorted by
+// (q, slice index), so equal values keep their slice order and the result does not depend on the sort's algorithm.
+int svr_structural_decide(int ns, const int *stack_index, const double *sums, const unsigned char *eligible, int min_pixels, double k_mad,
+                          double min_drop, double *q_out, unsigned char *exclude_out) {
+  if (ns < 0 || (ns > 0 && (!stack_index || !sums || !eligible || !q_out || !exclude_out))) return SVR_E_ARG;
+  if (!(k_mad >= 0.0) || !(min_drop >= 0.0)) return SVR_E_ARG;
+  std::vector<int> by_stack(ns);
+  for (int i = 0; i < ns; ++i) {
+    const double n = sums[2 * (size_t)i], S = sums[2 * (size_t)i + 1];
+    const double q = (eligible[i] && n > 0 && n >= (double)min_pixels) ? S / n : NAN;
+    q_out[i] = q;                                          // (a sum that is nan: not judged either)
+    exclude_out[i] = 0;
+    by_stack[i] = i;
+  }
+  std::stable_sort(by_stack.begin(), by_stack.end(), [&](int a, int b) { return stack_index[a] < stack_index[b]; });
+  auto median = [](const std::vector<double> &v) {         // v sorted, not empty
+    const size_t n = v.size();
+    return (n & 1) ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0;
+  };
+  for (int a = 0; a < ns;) {
+    int b = a;
+    while (b < ns && stack_index[by_stack[b]] == stack_index[by_stack[a]]) ++b;
+    std::vector<int> judged;
+    for (int k = a; k < b; ++k)
+      if (q_out[by_stack[k]] == q_out[by_stack[k]]) judged.push_back(by_stack[k]);
+    a = b;
+    if (judged.size() < 4) continue;
+    std::sort(judged.begin(), judged.end(), [&](int i, int j) { return q_out[i] < q_out[j] || (q_out[i] == q_out[j] && i < j); });
+    std::vector<double> v(judged.size());
+    for (size_t k = 0; k < judged.size(); ++k) v[k] = q_out[judged[k]];
+    const double med = median(v);
+    for (double &x : v) x = fabs(x - med);
+    std::sort(v.begin(), v.end());
+    const double mad = median(v), drop = std::max((k_mad * 1.4826) * mad, min_drop), threshold = med - drop;
+    for (int i : judged) exclude_out[i] = q_out[i] < threshold ? 1 : 0;
+  }
+  return SVR_OK;
 }
 
 }  // extern "C"

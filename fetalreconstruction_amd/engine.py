@@ -43,7 +43,7 @@ EXPORTS = [
     "svr_superresolution_backproject", "svr_superresolution_update", "svr_robust_statistics_sums",
     "svr_mstep_sums", "svr_scale_volume_sums", "svr_scale_volume_apply", "svr_timer_get",
     "svr_unit_counts", "svr_fallbacks", "svr_clock_probe", "svr_slice_em_setup", "svr_slice_em_set_state", "svr_mstep_estep_device", "svr_slice_em_run", "svr_slice_em_apply_weights", "svr_slice_em_fetch", "svr_slice_em_set_patch_form", "svr_cell_stats", "svr_pair_pack", "svr_pair_unpack", "svr_timer_reset", "svr_timer_enable", "svr_timer_begin", "svr_timer_end", "svr_timer_add", "svr_counters", "svr_get_stream", "svr_device", "svr_device_count", "svr_combine_weights", "svr_update_stack_sizes", "svr_ncc_set_targets", "svr_ncc_set_source",
-    "svr_ncc_evaluate", "svr_ncc_get", "svr_ncc_alloc_targets","svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
+    "svr_ncc_evaluate", "svr_ncc_get", "svr_ncc_alloc_targets","svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_slice_ssim", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_reg_get", "svr_pvr_cc_patches", "svr_pvr_register_patches",
@@ -478,6 +478,17 @@ class Reconstruction:
         out = np.zeros((self.sgrid[0], 10), np.float64)
         self._ck(self._lib.svr_slice_quality(self._h, _p(out)))
         return out
+
+    def slice_ssim(self, radius, c1, c2, want_map=False):
+        """svr_slice_ssim -> (float64 [ns][2] = {n_ssim, sum ssim} per slice, the map float32 [ns][sy][sx] or None): the windowed
+        structural similarity of the scaled (bias-corrected) slice against the simulated one over the M-step's pixels, box window of
+        (2 radius + 1)^2 pixels; the map is NaN where a pixel is not counted (include/svr_hip.h).  SimulateSlices first."""
+        if not self.sgrid:
+            raise SvrError("slice_ssim: initStorageVolumes first")
+        out = np.zeros((self.sgrid[0], 2), np.float64)
+        m = np.zeros(self.sgrid, np.float32) if want_map else None
+        self._ck(self._lib.svr_slice_ssim(self._h, int(radius), C.c_double(c1), C.c_double(c2), _p(out), _p(m) if m is not None else None))
+        return out, m
 
     def resample_to_reconstruction(self, src, src_from_recon, padding=-1.0, install=False, scale=None, want_volume=True):
         """svr_resample_to_reconstruction: src float32 [nz][ny][nx] on any grid, src_from_recon = source world-to-image x reconstruction

@@ -24,6 +24,7 @@ HOST_EXPORTS = [
     "svrh_sr_iteration", "svrh_reconstruct_iteration", "svrh_get_state", "svrh_set_bias_correction", "svrh_set_bias_options", "svrh_bias_gpu",
     "svrh_normalise_bias_gpu", "svrh_prepare_registration_slices", "svrh_slice_to_volume_registration_gpu",
     "svrh_get_registration_slices", "svrh_force_collectives", "svrh_set_slab_update", "svrh_set_unit_order", "svrh_channel_reconstruct",
+    "svrh_set_structural", "svrh_structural_evaluate", "svrh_get_structural",
 ]
 PVR_HOST_EXPORTS = ["pvrh_create", "pvrh_destroy", "pvrh_last_error", "pvrh_initialize_em_values", "pvrh_initialize_robust_statistics",
                     "pvrh_estep", "pvrh_mstep", "pvrh_scale", "pvrh_reconstruct_iteration", "pvrh_register_patches", "pvrh_get_state",
@@ -32,7 +33,7 @@ IRTK_EXPORTS = ["svrh_stack_registrations", "svrh_slice_to_volume_registration",
                 "svrh_irtk_blur_with_padding", "svrh_irtk_rigid_parameters", "svrh_slice_to_volume_registration_ex", "svrh_package_to_volume_ex",
                 "svrh_irtk_number_of_bins", "svrh_nmi_sums", "svrh_irtk_blur_kernel", "svrh_irtk_prepare_level"]   # csrc/irtk_reg.cpp
 IO_EXPORTS = ["svr_nifti_read", "svr_nifti_write", "svr_free", "svr_dof_read", "svr_dof_write", "svr_host_threads",
-              "svr_slice_quality_derive", "svr_slice_report_write"]      # csrc/svr_io.cpp, declared in svr_host.h
+              "svr_slice_quality_derive", "svr_slice_report_write", "svr_slice_report_write_ex", "svr_structural_decide"]      # csrc/svr_io.cpp, declared in svr_host.h
 
 
 class ImageAttr(C.Structure):
@@ -344,6 +345,25 @@ class irtkReconstruction:
         t = np.ascontiguousarray(transformations, np.float64).reshape(-1, 16).copy()
         self._ck(self._lib.svrh_slice_to_volume_registration_gpu(self._h, t.ctypes.data_as(C.c_void_p)))
         return t.reshape(-1, 4, 4)
+
+    def set_structural(self, enable, stack_index=None, radius=3, k_mad=3.0, min_drop=0.1, min_pixels=25):
+        """svrh_set_structural: reconstruct_iteration then ends with structural_evaluate and starts by putting what the last one found
+        in force (include/svr_host.h); stack_index: the stack of every slice, global, in this object's numbering"""
+        si = None if stack_index is None else np.ascontiguousarray(stack_index, np.int32)
+        assert si is None or len(si) == self.ns
+        self._ck(self._lib.svrh_set_structural(self._h, int(bool(enable)), int(radius), C.c_double(k_mad), C.c_double(min_drop), int(min_pixels),
+                                               None if si is None else si.ctypes.data_as(C.c_void_p)))
+
+    def structural_evaluate(self):
+        """svrh_structural_evaluate (collective): the slices' mean SSIM as the buffers stand -> the pending set"""
+        self._ck(self._lib.svrh_structural_evaluate(self._h))
+
+    def get_structural(self):
+        """-> dict(q float64 [ns] (nan: not judged), n_ssim float64 [ns], in_force bool [ns], pending bool [ns])"""
+        q, n = np.zeros(self.ns, np.float64), np.zeros(self.ns, np.float64)
+        f, pe = np.zeros(self.ns, np.uint8), np.zeros(self.ns, np.uint8)
+        self._ck(self._lib.svrh_get_structural(self._h, *[a.ctypes.data_as(C.c_void_p) for a in (q, n, f, pe)]))
+        return dict(q=q, n_ssim=n, in_force=f.astype(bool), pending=pe.astype(bool))
 
     def sr_iteration(self, i):
         self._ck(self._lib.svrh_sr_iteration(self._h, int(i)))
@@ -724,6 +744,41 @@ def slice_quality_derive(sums):
     for i in range(len(rows)):
         lib.svr_slice_quality_derive(rows[i].ctypes.data_as(C.c_void_p), out[i].ctypes.data_as(C.c_void_p))
     return out.reshape(s.shape[:-1] + (4,))
+
+
+def structural_decide(stack_index, sums, eligible, min_pixels=25, k_mad=3.0, min_drop=0.1):
+    """svr_structural_decide: the rule of --structural on svr_slice_ssim's sums [ns][2] -> (q float64 [ns], nan = not judged;
+    excluded bool [ns]): per stack, q < median - max(k_mad 1.4826 MAD, min_drop) over the judged slices (include/svr_host.h)"""
+    lib = _engine.load_library()
+    si = np.ascontiguousarray(stack_index, np.int32)
+    n = len(si)
+    s = np.ascontiguousarray(sums, np.float64).reshape(n, 2)
+    el = np.ascontiguousarray(np.asarray(eligible) != 0, np.uint8)
+    if len(el) != n:
+        raise ValueError("structural_decide: one entry per slice expected")
+    q, ex = np.zeros(n, np.float64), np.zeros(n, np.uint8)
+    rc = lib.svr_structural_decide(n, *[a.ctypes.data_as(C.c_void_p) for a in (si, s, el)], int(min_pixels), C.c_double(k_mad), C.c_double(min_drop),
+                                   q.ctypes.data_as(C.c_void_p), ex.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise _engine.SvrError(f"svr_structural_decide: status {rc}")
+    return q, ex.astype(bool)
+
+
+def write_slice_report_ex(path, stack_index, slice_weight, slice_inside, scale, params6, sums, ssim_sums, structural):
+    """svr_slice_report_write_ex: write_slice_report's file with the three columns ssim n_ssim structural after mean_weight"""
+    lib = _engine.load_library()
+    si = np.ascontiguousarray(stack_index, np.int32)
+    n = len(si)
+    w, sc = np.ascontiguousarray(slice_weight, np.float32), np.ascontiguousarray(scale, np.float32)
+    ins = np.ascontiguousarray(np.asarray(slice_inside) != 0, np.uint8)
+    p6, s = np.ascontiguousarray(params6, np.float64).reshape(n, 6), np.ascontiguousarray(sums, np.float64).reshape(n, 10)
+    ss, st = np.ascontiguousarray(ssim_sums, np.float64).reshape(n, 2), np.ascontiguousarray(np.asarray(structural) != 0, np.uint8)
+    if not (len(w) == len(sc) == len(ins) == len(st) == n):
+        raise ValueError("write_slice_report_ex: one entry per slice expected")
+    err = C.create_string_buffer(256)
+    rc = lib.svr_slice_report_write_ex(str(path).encode(), n, *[a.ctypes.data_as(C.c_void_p) for a in (si, w, ins, sc, p6, s, ss, st)], err)
+    if rc != 0:
+        raise _engine.SvrError(f"svr_slice_report_write_ex: {err.value.decode()}")
 
 
 def write_slice_report(path, stack_index, slice_weight, slice_inside, scale, params6, sums):

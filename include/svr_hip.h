@@ -331,6 +331,23 @@ int svr_stack_motion(svr_ctx *ctx, const float *slices, int m, int n, double *si
  * slice grid alone and is readable afterwards as the option "quality_chunks".  Nothing of the call stays on the device. */
 #define SVR_SLICE_QUALITY_SUMS 10
 int svr_slice_quality(svr_ctx *ctx, double *sums /* [ns][SVR_SLICE_QUALITY_SUMS] */);
+/* A windowed structural similarity (SSIM) between every slice (or patch) and its simulation (csrc/svr_ssim.inc; no reference
+ * equivalent -- what the command line's --structural judges a slice by).  Reads the buffers as they stand, like svr_slice_quality.
+ * For slice pixel p, with svr_slice_quality's operands and pixel set V:
+ *   x = bias ? s * expf(-bias) * scale : s * scale (float32, the scale vector the M-step reads),   y = simulated slice,
+ *   p in V iff s != -1 and simweight > 0.99 (compared in double with a bias field, in float without, as the M-step does).
+ * The window is the (2 radius + 1)^2 box around p clipped to the slice grid, 1 <= radius <= SVR_SSIM_MAX_RADIUS (padding is -1 and
+ * so never in V).  Over the window's pixels in V, in double from the float operands: m (their number), Sx, Sy, Sxx, Syy, Sxy.
+ * p is counted iff p in V and m >= ((2 radius + 1)^2 + 1) / 2 (integer division: at least half the window holds data).  For a
+ * counted pixel, in double, neither contracted nor reassociated:
+ *   mx = Sx / m,  my = Sy / m,  vx = Sxx / m - mx mx,  vy = Syy / m - my my,  cxy = Sxy / m - mx my,
+ *   ssim = (((2 mx) my + c1) (2 cxy + c2)) / (((mx mx + my my) + c1) ((vx + vy) + c2)).
+ * sums[slice] = {n_ssim: the number of counted pixels, S ssim: their sum in double}.  map_or_null [ns][sy][sx]: (float)ssim, NaN
+ * where the pixel is not counted.  No atomics, a fixed order that follows from (ns, sx, sy, radius): the same bits on every call.
+ * Refused with a message: no slices, no scale vector, no forward projection, a null sums, a radius outside 1 .. 7, c1 or c2
+ * negative or not finite.  Nothing of the call stays on the device. */
+#define SVR_SSIM_MAX_RADIUS 7
+int svr_slice_ssim(svr_ctx *ctx, int radius, double c1, double c2, double *sums /* [ns][2] */, float *map_or_null);
 /* A volume on ANY grid brought onto the context's reconstruction grid (csrc/svr_seed.inc; the command line's --referenceVolume, which
  * the reference reads -- reconstruction.cc:253-258 -- and, outside its T1 experiment, never uses).  src: host memory, src_size = {nx, ny,
  * nz}, x fastest.  src_from_recon: rows 0..2 of  source world-to-image x reconstruction image-to-world,  composed by the caller in double;

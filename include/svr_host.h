@@ -181,6 +181,36 @@ int svr_host_threads(void);
 void svr_slice_quality_derive(const double sums[SVR_SLICE_QUALITY_SUMS], double derived4[4]);
 int svr_slice_report_write(const char *path, int n_slices, const int *stack_index, const float *slice_weight, const unsigned char *slice_inside,
                            const float *scale, const double *params6, const double *sums, char err[256]);
+/* svr_slice_report_write_ex: the same file; with ssim_sums [n][2] (svr_slice_ssim's {n_ssim, S ssim}) and structural [n] (both or
+ * neither) three more columns follow mean_weight:  ssim (S ssim / n_ssim, nan when n_ssim = 0)  n_ssim  structural (0 / 1).  With both
+ * NULL it writes what svr_slice_report_write writes. */
+int svr_slice_report_write_ex(const char *path, int n_slices, const int *stack_index, const float *slice_weight, const unsigned char *slice_inside,
+                              const float *scale, const double *params6, const double *sums, const double *ssim_sums_or_null,
+                              const unsigned char *structural_or_null, char err[256]);
+
+/* ---- Structural slice exclusion (the command line's --structural; a deviation from the reference) ----------------------
+ * svr_structural_decide: the rule, pure host code in double.  sums [ns][2] = svr_slice_ssim's {n_ssim, S ssim};  q = S ssim / n_ssim.
+ * A slice is judged iff eligible[i] and n_ssim >= min_pixels (and n_ssim > 0, and q is a number); otherwise q_out[i] = nan and the
+ * slice is never excluded.  Per stack (stack_index), over its judged slices: median = the middle value, or the mean of the two middle
+ * values for an even count;  MAD = the median of |q - median|;  exclude iff q < median - max((k_mad 1.4826) MAD, min_drop).  A stack
+ * with fewer than 4 judged slices excludes nothing.  Deterministic: ties in the sort are broken by slice index.  SVR_E_ARG for a
+ * missing array or a negative / nan k_mad or min_drop.
+ * svrh_set_structural: switches the evaluation inside svrh_reconstruct_iteration on (off by default: nothing below then runs).
+ *   stack_index_global [n_slices_global], in the object's numbering; copied.  radius 1 .. 7.
+ * svrh_structural_evaluate (collective): svr_slice_ssim on this rank's slices as they stand -- c1 = (0.01 L)^2, c2 = (0.03 L)^2 with
+ *   L = max - min intensity -- after settling the unit-level state; sharded, the ranks' rows are summed (every row has one non-zero
+ *   contributor, so the sum is exact); then every rank decides alike.  eligible = inside the mask, not force-excluded, not a small
+ *   slice; a slice that is structurally excluded now is judged again (the set is not sticky).  The result becomes `pending`.
+ *   svrh_reconstruct_iteration runs it after its last SR iteration, before MaskVolume: that iteration's forward projection is the
+ *   newest volume's, so none is made.  At its start `pending` becomes the set `in force`: merged into the slices the slice-level EM
+ *   leaves out and given weight 0 where the force-excluded slices are, i.e. treated as --force_exclude treats a slice, for that outer
+ *   iteration only.  Registration still moves such a slice.  In the first outer iteration nothing is in force.
+ * svrh_get_structural: q (nan = not judged) and n_ssim of the last evaluation, and the two sets; any pointer may be NULL. */
+int svr_structural_decide(int ns, const int *stack_index, const double *sums /* [ns][2] */, const unsigned char *eligible, int min_pixels,
+                          double k_mad, double min_drop, double *q_out /* [ns] */, unsigned char *exclude_out /* [ns] */);
+int svrh_set_structural(svrh_recon *r, int enable, int radius, double k_mad, double min_drop, int min_pixels, const int *stack_index_global);
+int svrh_structural_evaluate(svrh_recon *r);
+int svrh_get_structural(svrh_recon *r, double *q, double *n_ssim, unsigned char *in_force, unsigned char *pending);
 
 /* The numbering of a sharded run (round 5).  A launcher may deal the units to the ranks in any order -- e.g. the r-th part of EVERY stack
  * to rank r, so that a rank's slices are neighbours in space and it stages 1/N of the volume's work items instead of those of whole
