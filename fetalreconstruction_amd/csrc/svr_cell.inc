@@ -46,6 +46,12 @@ struct CellRun {            // the pixels of one slice in one quad
   int pad;                  // normal is the x axis lies IN the owned axis: its run is a whole column of the slice
 };
 static_assert(sizeof(CellRun) == 32, "CellRun layout");
+// The most pixels of one slice in one cell (around one band of planes) the lists take.  CellRun::n could say 65535, but a slot adds its quarter of a
+// run to a voxel in ONE chain of float adds: with the 16 k adds per slot of a 65 535-pixel run (0.01 mm pixels, regular terms) pass 2 of the Gaussian
+// reconstruction left volw 4e-5 from the oracle, twice the 2e-5 the parity tests allow, where the short chains of the slice tiles leave 7e-6
+// (tests/test_cell_limits_gpu.py).  16384 is still beyond anything the lists are laid out for: cell_auto_size stops at 16 pixels per voxel area, and the
+// largest cell whose boxes fit the LDS (26 x 26) then holds 10 816 pixels of a slice.
+constexpr uint32_t CELL_RUN_MAX = 16384u;
 
 struct CellClass {
   int x0, l0;               // first centre coordinate of cell (0, 0)
@@ -53,6 +59,7 @@ struct CellClass {
   int pfirst, plast;        // first / last absolute plane that can receive a tap (plast <= volume - 1; pfirst may be negative)
   int ng;                   // planes: plast - pfirst + 1
   int cell_base;            // global index of the class's first quad
+  int row_base, col_base;   // the class's first entry in CellArgs::rowcol: its rows of quads (ncl), its columns (ncx)
 };
 
 struct CellArgs {
@@ -76,6 +83,7 @@ struct CellArgs {
   uint32_t nents;           // much longer than the launch's fair share is cut into parts (every parts-th run that reaches the plane each)
   const int *item_of;       // [quad * ngs + plane index] -> the item's first entry | (parts - 1) << 28, or -1 (entries < 2^28)
   f2 *stage;                // [entry][DL][PL]
+  const unsigned char *rowcol; // [CellClass::row_base + row of quads] / [col_base + column]: 1 = some run lies in it (combine_class skips the rest; NULL: none skipped)
   const unsigned char *act; // COEFF == 3 (the scatter that writes the table): [sorted record] 1 = a PSF pixel -- its units are evaluated and stored whatever its
                             // factors are this time (NULL: the factors decide, as in every other launch)
   const uint32_t *pid;      // [sorted record] -> the pixel's id in the coefficient table (cell_pids; COEFF launches only): travels with the record,
@@ -94,6 +102,8 @@ struct CellState {
   size_t cap_iflag = 0, cap_ipos = 0, cap_ents = 0;
   int *d_item_of = nullptr;
   f2 *d_stage = nullptr;
+  unsigned char *d_rowcol = nullptr;
+  size_t cap_rowcol = 0;
   float *d_gf = nullptr;               // gather: 1 / v_PSF_sums per sorted pixel, 0 = not a PSF pixel
   f2 *d_part = nullptr;                // gather: the units' partial sums [unit][sorted pixel] (a run's pixels of one plane: neighbours)
   size_t cap_gf = 0, cap_part = 0;
@@ -114,7 +124,7 @@ void cell_free(CellState *c) {
   if (!c) return;
   free_dev(c->d_keys); free_dev(c->d_keys2); free_dev(c->d_head); free_dev(c->d_runid);
   free_dev(c->d_recs); free_dev(c->d_runs); free_dev(c->d_cell_first); free_dev(c->d_cell_last); free_dev(c->d_items);
-  free_dev(c->d_item_of); free_dev(c->d_ents); free_dev(c->d_item_flag); free_dev(c->d_item_pos); free_dev(c->d_stage); free_dev(c->d_gf); free_dev(c->d_part); free_dev(c->d_pid); free_dev(c->d_act); free_dev(c->d_tmp); free_dev(c->d_range);
+  free_dev(c->d_item_of); free_dev(c->d_ents); free_dev(c->d_item_flag); free_dev(c->d_item_pos); free_dev(c->d_stage); free_dev(c->d_rowcol); free_dev(c->d_gf); free_dev(c->d_part); free_dev(c->d_pid); free_dev(c->d_act); free_dev(c->d_tmp); free_dev(c->d_range);
   delete c;
 }
 
@@ -278,12 +288,25 @@ __global__ void k_cell_run_ranges(CellRun *runs, uint32_t nruns, uint32_t n, con
   }
   R.czmin = (short)mn; R.czmax = (short)mx;
   for (int q = 0; q < 4; ++q) {
-    if (cnt[q] > 65535u) atomicAdd(overflow, 1u);        // a cell holds more pixels of one slice than a run can say: the caller falls back
+    if (cnt[q] > CELL_RUN_MAX) atomicAdd(overflow, 1u);  // a cell holds more pixels of one slice than a run may: the caller falls back
     R.n[q] = (unsigned short)min(cnt[q], 65535u);
   }
   runs[r] = R;
   if (r == 0 || runs[r - 1].cell != R.cell) cell_first[R.cell] = r;
   if (r + 1 == nruns || runs[r + 1].cell != R.cell) cell_last[R.cell] = r + 1;
+}
+
+// the rows and the columns of quads that hold a run, per class.  The voxels of a low face add up every staged source coordinate <= 0 (combine_class); a slice
+// far below the volume on two axes leaves the voxels of a low edge ~10^6 of them, nearly all in rows and columns of cells nothing lies in
+__global__ void k_cell_rowcol(CellArgs ca, const CellRun *runs, uint32_t nruns, unsigned char *rowcol) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nruns) return;
+  const uint32_t cell = runs[r].cell;
+  const CellClass &C = ca.cls[cell >= (uint32_t)ca.cls[1].cell_base ? 1 : 0];
+  const int lq = (int)cell - C.cell_base;
+  const int ql = lq / C.ncx, qx = lq - ql * C.ncx;
+  rowcol[C.row_base + ql] = 1;
+  rowcol[C.col_base + qx] = 1;
 }
 
 // the work items: (cell, plane) pairs some run reaches, IN (cell, plane) ORDER -- flags, a prefix sum, then the list: the planes of
@@ -766,9 +789,20 @@ __device__ __forceinline__ f2 combine_class(const CellArgs &ca, const CellClass 
       // cells jl with l0 + jl CL - NC <= Ls <= l0 + jl CL + CL - 1 + NH
       const int jlo = max(-floordiv(-(Ls - C.l0 - NH - (ca.CL - 1)), ca.CL), 0);     // ceil
       const int jhi = min(floordiv(Ls - C.l0 + NC, ca.CL), C.ncl * ca.QL - 1);
+      // (rows and columns of cells without a run hold no item: skipping them adds the same terms in the same order)
+      if (ca.rowcol) {
+        bool any = false;
+        for (int jl = jlo; jl <= jhi && !any; ++jl) any = ca.rowcol[C.row_base + jl / ca.QL] != 0;
+        if (!any) continue;
+      }
       for (int Xs = xa; Xs <= xe; ++Xs) {
         const int ilo = max(-floordiv(-(Xs - C.x0 - NH - (ca.CX - 1)), ca.CX), 0);
         const int ihi = min(floordiv(Xs - C.x0 + NC, ca.CX), C.ncx * ca.QX - 1);
+        if (ca.rowcol) {
+          bool any = false;
+          for (int ix = ilo; ix <= ihi && !any; ++ix) any = ca.rowcol[C.col_base + ix / ca.QX] != 0;
+          if (!any) continue;
+        }
         for (int jl = jlo; jl <= jhi; ++jl)
           for (int ix = ilo; ix <= ihi; ++ix) {
             const uint32_t quad = (uint32_t)(C.cell_base + (jl / ca.QL) * C.ncx + ix / ca.QX);
@@ -1363,9 +1397,11 @@ int cell_grow(svr_ctx *ctx, T *&p, size_t &cap, size_t want) {
   return SVR_OK;
 }
 
-// (Re)build the cell structures for the current slice geometry.  On anything the layout cannot hold (centres beyond int16,
-// more than 2^20 cells / slices, a staging buffer that does not fit) the state is marked unusable and the caller takes the
-// atomic flush of back_mode 4.
+// (Re)build the cell structures for the current slice geometry.  On anything the layout cannot hold (centres beyond +-32000: the records
+// keep them as shorts; more than 1024 planes in a class, 2^18 cells or more, more than 16384 pixels of one slice in one cell around one
+// band of planes, a slice grid of more than 2^20 pixels, more than 2^17 slices: the fields of items[] and of the sort key; LDS boxes
+// beyond 64 KiB; a staging buffer that does not fit) the state is marked unusable and the caller takes the tile kernels -- the atomic
+// flush of back_mode 4, fwd_unit_kernel, the tile form of pass 1 (cells_or_fallback).
 //
 // The cell size follows the density of slice pixels in the volume, d = voxel area / pixel area in the slice plane: a run (the
 // pixels of one slice in one cell) should fill the records of the 64 (60) lanes.  Measured (scatter / gather, ms; DESIGN 5.1c):
@@ -1497,12 +1533,14 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   if ((size_t)(need_stage ? (ctx->pvr ? SlotGeom<PVR_N>::NSLOT : 4) : 1) * ca.PP * sizeof(f2) > 64 * 1024) { cs.valid = true; return SVR_OK; }
   ca.split = std::max(1, ctx->cell_split);
   uint64_t ncells = 0;
+  size_t nrowcol = 0;
   int ngs = 0;
   bool ok = true;
   for (int c = 0; c < 2; ++c) {
     CellClass &C = ca.cls[c];
     const int *q = hr + 6 * c;
     C.cell_base = (int)ncells;
+    C.row_base = C.col_base = (int)nrowcol;
     if (q[0] > q[1]) { C.ng = 0; C.ncx = C.ncl = 0; continue; }          // no pixel of this class
     const int vgz = c == 0 ? (int)ctx->vy : (int)ctx->vz;
     for (int k = 0; k < 6; ++k) ok = ok && q[k] > -32000 && q[k] < 32000;
@@ -1517,6 +1555,8 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
     while (((q[5] - q[4] + NC) >> ca.band_shift) >= 128) ++ca.band_shift;      // the band field of the sort key has 7 bits
     ngs = std::max(ngs, C.ng);
     ncells += (uint64_t)C.ncx * C.ncl;
+    C.col_base = C.row_base + C.ncl;
+    nrowcol += (size_t)C.ncl + (size_t)C.ncx;
   }
   ca.ngs = std::max(ngs, 1);
   ok = ok && ncells > 0 && ncells < (1u << 18) && ncells * (uint64_t)ca.ngs < (1ull << 28);
@@ -1580,6 +1620,13 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   hipLaunchKernelGGL(k_cell_run_ranges, dim3(nblk(nruns)), dim3(256), 0, ctx->stream, cs.d_runs, nruns, ns_, cs.d_recs, cs.d_keys2, cs.d_cell_first,
                      cs.d_cell_last, ctx->d_counter + 1);
   KCHK("k_cell_run_ranges");
+  if (need_stage) {
+    if ((r = cell_grow(ctx, cs.d_rowcol, cs.cap_rowcol, nrowcol))) return r;
+    HIPCHK(hipMemsetAsync(cs.d_rowcol, 0, nrowcol, ctx->stream));
+    hipLaunchKernelGGL(k_cell_rowcol, dim3(nblk(nruns)), dim3(256), 0, ctx->stream, ca, cs.d_runs, nruns, cs.d_rowcol);
+    KCHK("k_cell_rowcol");
+    ca.rowcol = cs.d_rowcol;
+  }
   ca.recs = cs.d_recs; ca.runs = cs.d_runs; ca.cell_first = cs.d_cell_first; ca.cell_last = cs.d_cell_last;
   ca.items = cs.d_items; ca.item_of = cs.d_item_of;
   {
@@ -1606,7 +1653,7 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   HIPCHK(hipMemcpyAsync(two, cs.d_item_pos + (tab - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const uint32_t nitems = two[0];
-  if (two[1]) { if (getenv("SVR_TUNE_DEBUG")) fprintf(stderr, "[cell] %u runs with > 65535 pixels of a slice in one cell: fallback\n", two[1]); cs.valid = true; return SVR_OK; }         // > 65535 pixels of one slice in one cell
+  if (two[1]) { if (getenv("SVR_TUNE_DEBUG")) fprintf(stderr, "[cell] %u runs with > %u pixels of a slice in one cell: fallback\n", two[1], CELL_RUN_MAX); cs.valid = true; return SVR_OK; }         // > CELL_RUN_MAX pixels of one slice in one cell
   ca.nitems = nitems;
   uint32_t nents = 0;
   {

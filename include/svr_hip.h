@@ -514,8 +514,9 @@ int svr_slice_em_fetch(svr_ctx *ctx, float *scale_global, float *slice_weight_gl
  * -1 = none, potential 0; NULL = its own) -- the reference's copy of the stacks' potentials without the stack offset (:256-276).  After setup. */
 int svr_slice_em_set_patch_form(svr_ctx *ctx, const int *source_ref_or_null);
 /* PSF launches since svr_create that were asked for on the cell path (back_mode 5 / fwd_mode 2: no float atomics, the same bits from run
- * to run) and LEFT it because the cell lists cannot hold the geometry (centre coordinates beyond int16, more than 2^18 cells or 1024
- * planes per class, slices of more than 2^20 pixels, more than 2^17 slices, a staging buffer that does not fit): out4 = {scatters that
+ * to run) and LEFT it because the cell lists cannot hold the geometry (centre coordinates beyond +-32000, 2^18 cells or more, more than 1024
+ * planes per class, more than 16384 pixels of one slice in one cell, slices of more than 2^20 pixels, more than 2^17 slices, LDS boxes beyond 64 KiB,
+ * a staging buffer that does not fit): out4 = {scatters that
  * ran as back_mode 4 (float atomics: last bits depend on the run), gathers and Gaussian pass-1 launches that ran on the tile kernels
  * (same bits, slower), tiles of tiled scatters re-run by a workgroup kernel}.  The first of each kind is also reported on stderr;
  * bench.py puts the four numbers into config.tuned.fallbacks and the tests of the bench workloads require zeros. */
