@@ -21,8 +21,15 @@
 // The arithmetic is the host object's (csrc/svr_host.cpp EStepGPU: the reference's expressions with their float / double mix), in the
 // REFERENCE's slice order, with one difference: the five sums over the slices are taken by 256 threads (thread k adds the slices k, k + 256,
 // .. in order, then a fixed tree) instead of one after the other -- double sums of a few hundred floats, so the scalars agree with the host
-// form to ~1e-15 relative before they are rounded to float (tests: slice weights within 1e-6).  Every rank runs the same kernel on the
-// same gathered vectors: the same bits on every rank, whatever the sharding.
+// form to ~1e-15 relative before they are rounded to float.  Every rank runs the same kernel on the same gathered vectors: the same bits
+// on every rank, whatever the sharding.
+//
+// What the tests pin (tests/test_unit_em_gpu.py against the numpy restatement tests/unit_em_ref.py, cases tests/unit_em_cases.py): the
+// unpacked scales / inside flags / potentials with the exclusions and mean_s, mean_s2, sigma_s, sigma_s2 BIT FOR BIT in this 256-thread
+// order (and within 1 float ulp of the reference's serial order); the slice form's weights within 1 float ulp of float64 arithmetic on the
+// returned scalars, its branch zeros and ones exactly; the patch form's within four times the float Gaussian's own gap to float64 plus an
+// ulp; mix_s bit for bit from the returned weights; every rank of a sharding the same bits; k_mstep_finish, k_potential_pack (its zero
+// padding up to maxn included) and k_mstep_scalars_dev bit for bit against the separate calls and against mstep_scalars restated.
 namespace {
 
 struct SliceEm {

@@ -707,16 +707,87 @@ class Reconstruction:
 
     def read_floats(self, ptr, n):
         """n floats at a raw device pointer of this engine (slab_rs_pack, slab_update, device_ptr), behind everything queued on its stream"""
-        out = np.empty(int(n), np.float32)
+        return self.device_read(ptr, n, np.float32)
+
+    def write_floats(self, ptr, arr):
+        """a float32 array to a raw device pointer of this engine, behind everything queued on its stream and complete on return"""
+        self.device_write(ptr, _f32(arr))
+
+    def device_read(self, ptr, n, dtype=np.float32):
+        """n items of `dtype` at a raw device pointer of this engine, behind everything queued on its stream"""
+        out = np.empty(int(n), dtype)
         self.stream_sync()
         _hip_memcpy(_p(out), ptr, out.nbytes, 2)
         return out
 
-    def write_floats(self, ptr, arr):
-        """a float32 array to a raw device pointer of this engine, behind everything queued on its stream and complete on return"""
-        a = _f32(arr).reshape(-1)
+    def device_write(self, ptr, array):
+        """an array (its own dtype) to a raw device pointer of this engine, behind everything queued on its stream and complete on return"""
+        a = np.ascontiguousarray(array).reshape(-1)
         self.stream_sync()
         _hip_memcpy(ptr, _p(a), a.nbytes, 1)
+
+    # ---- the unit-level EM on the device (csrc/svr_em.inc): what the C++ host objects drive, one call each ----------------
+    def slice_em_setup(self, n_global, world, rank, rank_lo, order=None, step=0.0001):
+        """svr_slice_em_setup: rank_lo[world + 1] = the ranks' ranges of the host numbering (this rank's must hold the context's
+        slices), order[k] = the reference index of host unit k (None: the same numbering)"""
+        lo = np.ascontiguousarray(rank_lo, np.int32)
+        if len(lo) != int(world) + 1:
+            raise ValueError("rank_lo must have world + 1 entries")
+        o = None if order is None else np.ascontiguousarray(order, np.int32)
+        if o is not None and len(o) != int(n_global):
+            raise ValueError("order must have n_global entries")
+        self._ck(self._lib.svr_slice_em_setup(self._h, int(n_global), int(world), int(rank), _p(lo), None if o is None else _p(o), C.c_double(step)))
+        self._em_n = int(n_global)                             # (set on success only: a setup refused for its ranges leaves the previous one in force, one refused later leaves none)
+
+    def slice_em_set_patch_form(self, source_ref=None):
+        """svr_slice_em_set_patch_form: source_ref[t] = the reference index of the unit whose potential reference unit t reads, -1 = none"""
+        s = None if source_ref is None else np.ascontiguousarray(source_ref, np.int32)
+        if s is not None and len(s) != getattr(self, "_em_n", -1):
+            raise ValueError("source_ref must have n_global entries")
+        self._ck(self._lib.svr_slice_em_set_patch_form(self._h, None if s is None else _p(s)))
+
+    def slice_em_set_state(self, weights, excluded, scalars5, em3):
+        w, e = _f32(weights), np.ascontiguousarray(excluded, np.uint8)
+        if len(w) != getattr(self, "_em_n", len(w)) or len(e) != len(w):
+            raise ValueError("weights and excluded must have n_global entries")
+        s5, e3 = np.ascontiguousarray(scalars5, np.float64), _f32(em3)
+        if len(s5) != 5 or len(e3) != 3:
+            raise ValueError("scalars5 / em3")
+        self._ck(self._lib.svr_slice_em_set_state(self._h, _p(w), _p(e), _p(s5), _p(e3)))
+
+    def mstep_estep_device(self, it, step=0.0001):
+        """svr_mstep_estep_device -> (send, recv, floats per rank): the device pointers of the rank's packed {potential, scale,
+        inside} and of where every rank's belong (one rank: the same buffer)"""
+        s, r, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        self._ck(self._lib.svr_mstep_estep_device(self._h, int(it), C.c_float(step), C.byref(s), C.byref(r), C.byref(n)))
+        return s.value, r.value, int(n.value)
+
+    def slice_em_run(self):
+        self._ck(self._lib.svr_slice_em_run(self._h))
+
+    def slice_em_apply_weights(self):
+        self._ck(self._lib.svr_slice_em_apply_weights(self._h))
+
+    def slice_em_fetch(self):
+        """svr_slice_em_fetch -> dict(scale, weight, potential, inside [n_global], scalars5 (float64), em3)"""
+        n = self._em_n if getattr(self, "_em_n", 0) > 0 else 1
+        sc, w, pot = (np.zeros(n, np.float32) for _ in range(3))
+        ins, s5, e3 = np.zeros(n, np.uint8), np.zeros(5, np.float64), np.zeros(3, np.float32)
+        self._ck(self._lib.svr_slice_em_fetch(self._h, _p(sc), _p(w), _p(pot), _p(ins), _p(s5), _p(e3)))
+        return dict(scale=sc, weight=w, potential=pot, inside=ins.astype(bool), scalars5=s5, em3=e3)
+
+    def mstep_partial(self, world):
+        """svr_mstep_partial -> (send, recv): this rank's M-step sums (8 doubles, five used) and where the ranks' [world][8] belong"""
+        s, r = C.c_void_p(), C.c_void_p()
+        self._ck(self._lib.svr_mstep_partial(self._h, int(world), C.byref(s), C.byref(r)))
+        return s.value, r.value
+
+    def mstep_estep_ranks(self, world, it, step, sigma, mix):
+        """svr_mstep_estep_ranks (after mstep_partial and the all-gather) -> (em3, slice potentials)"""
+        em = np.array([sigma, mix, 0.0], np.float32)
+        pot = np.zeros(self.sgrid[0], np.float32)
+        self._ck(self._lib.svr_mstep_estep_ranks(self._h, int(world), int(it), C.c_float(step), _p(em), _p(pot), None, None))
+        return em, pot
 
     def cell_stats(self):
         o = (C.c_uint64 * 8)()

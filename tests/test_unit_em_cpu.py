@@ -10,8 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.unit_em_cases import SLICE_CASES, STEP, _case   # the builders live with the device tests' cases
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STEP = 0.0001
 
 
 @pytest.fixture(scope="module")
@@ -39,45 +40,6 @@ def run_unit_em(exe, tmp_path, form, pot, w, scale, excluded, var_floor, classes
     assert r.returncode == 0, (r.returncode, r.stderr)
     out = np.frombuffer(dst.read_bytes(), np.float32)
     return out[:n].copy(), out[n:2 * n].copy(), out[2 * n:].copy()
-
-
-def _case(rng, n, p_scale_out=0.1):
-    pot = rng.uniform(0.0, 1.0, n).astype(np.float32)
-    w = rng.uniform(0.0, 1.0, n).astype(np.float32)
-    scale = rng.uniform(0.5, 2.0, n).astype(np.float32)
-    out = rng.random(n) < p_scale_out
-    scale[out] = rng.choice(np.float32([0.0, 0.1, 0.19999, 5.0001, 7.0]), int(out.sum()))
-    return pot, w, scale
-
-
-def _slice_cases():
-    rng = np.random.default_rng(20261015)
-    cases = {}
-    pot, w, scale = _case(rng, 64)
-    scale[:4] = np.float32([0.2, 5.0, 0.19999, 5.0001])             # the bounds themselves take part
-    cases["mixed, scales outside [0.2, 5], force-excluded and small slices"] = (pot, w, scale, [3, 17, 40], [8, 9], [0.3, 0.6, 0.02, 0.03, 0.8])
-    pot, w, scale = _case(rng, 20, 0.0)
-    cases["all units excluded"] = (pot, w, scale, list(range(10)), list(range(10, 20)), [0, 0, 0.02, 0.03, 0.8])
-    pot, w, scale = _case(rng, 30, 0.0)
-    cases["den2 == 0 (every weight 1)"] = (pot, np.ones(30, np.float32), scale, [2], [], [0, 0, 0.02, 0.03, 0.9])
-    pot, w, scale = _case(rng, 30, 0.0)
-    cases["weights 0: den == 0"] = (pot, np.zeros(30, np.float32), scale, [], [], [0, 0, 0.02, 0.03, 0.9])
-    pot = np.linspace(0.1, 0.9, 40).astype(np.float32)
-    w = (pot > 0.5).astype(np.float32)                               # the high potentials weigh as inliers: mean_s2 <= mean_s
-    cases["mean_s2 <= mean_s"] = (pot, w, np.ones(40, np.float32), [], [], [0, 0, 0.02, 0.03, 0.7])
-    # two tight classes and units far from both: the Gaussians underflow, likelihood == 0
-    pot = np.concatenate([np.full(200, 0.1), np.full(200000, 0.9), [0.5, 0.7, 3.0, 0.0]]).astype(np.float32)
-    w = np.concatenate([np.ones(200), np.zeros(200000), [1e-7, 0.0, 0.0, 1.0]]).astype(np.float32)
-    cases["likelihood == 0"] = (pot, w, np.ones(len(pot), np.float32), [], [], [0, 0, 0.02, 0.03, 0.5])
-    for k in range(3):
-        pot, w, scale = _case(rng, 300)
-        pot[rng.random(300) < 0.05] = -1                             # potentials the engine marked
-        fe = sorted(rng.choice(300, 6, replace=False).tolist())
-        cases[f"seeded {k}"] = (pot, w, scale, fe, [], rng.uniform(0, 1, 5).tolist())
-    return cases
-
-
-SLICE_CASES = _slice_cases()
 
 
 @pytest.mark.parametrize("name", list(SLICE_CASES))
