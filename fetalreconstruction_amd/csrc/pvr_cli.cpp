@@ -9,7 +9,7 @@
 // mask to the isotropic voxel size (nearest neighbour), match the stack intensities (:656-790, target = mean of all
 // positive voxels), min/max intensities (:792-814), CreateTemplate (:941-965), the reconstruction mask (:303-304);
 // then PatchBasedVolume::generate2DPatches per stack (patchBasedObject.cuh:176-342) and `iterations + 1` passes of
-// the loop in csrc/pvr_host.cpp (PBR.cpp:445-593).  The Python twin is fetalreconstruction_amd/pvr_cli.py.
+// the loop in csrc/pvr_host.cpp (PBR.cpp:445-593).  The Python twin is tests/twins/pvr_cli.py.
 //
 // The stack-to-stack registration (irtkStack3D3DRegistration, :280-285) runs through csrc/irtk_reg.cpp with every similarity
 // on the GPU; between the outer passes every patch is registered to the volume with the same schedule
@@ -18,12 +18,21 @@
 // --existingReconTarget starts from a given volume (and its grid); --hierarchical runs iterations + 1 levels of shrinking patches (pvrmain:359-432).
 // --dilateMask n dilates the mask n times, --packages p_1 .. p_N splits every stack into its interleaved packages (PBR.cpp:134-146).
 // --resample resamples the cropped stacks to the output voxel size with IRTK's cubic B-spline interpolator.
+//
+// Where things are.  Plain structs: Options (what the command line says; const after parse_options), Problem (the stacks, masks and
+// template of the set-up, the same for every level), Level (what one run of the loop is asked for) with its LevelPatches (what it
+// cuts and uploads), and Ranks (svr_launch.h) with one pvrh_recon* per rank.
+//   pre-processing     resample_attr, match_stack_intensities_pvr, dilate_mask, resample_bspline, split_packages
+//   patches            generate_2d_patches, append; cut_patches (square, full-slice, superpixel)
+//   options            usage, parse_options
+//   set-up             read_inputs, crop_to_mask, register_stacks, make_template
+//   one level          run_level: cut_patches, dump_problem, shard_patches, setup_engines, run_iterations (register_patches)
+// main() is the set-up, then one level or the hierarchical driver (first_level, the shrinking patch sizes), then the volume.
 #include <float.h>
 
 #include <future>
 
-#include "svr_prep.h"
-#include "svr_shard.h"
+#include "svr_launch.h"
 #include "svr_slic.h"
 
 namespace {
@@ -212,7 +221,7 @@ struct Patches {
 inline double snap(double v) { const double r = nearbyint(v); return fabs(v - r) < 1e-6 ? r : v; }
 
 // PatchBasedVolume<T>::generate2DPatches, patchBasedObject.cuh:176-342
-void append(Patches &to, const Patches &from) {
+template <class From> void append(Patches &to, const From &from) {     // From: Patches, or the superpixel cutter's SpxPatches
   to.data.insert(to.data.end(), from.data.begin(), from.data.end());
   to.i2w.insert(to.i2w.end(), from.i2w.begin(), from.i2w.end()); to.w2i.insert(to.w2i.end(), from.w2i.begin(), from.w2i.end());
   to.ri2w.insert(to.ri2w.end(), from.ri2w.begin(), from.ri2w.end()); to.mo.insert(to.mo.end(), from.mo.begin(), from.mo.end());
@@ -279,12 +288,8 @@ void generate_2d_patches(const Image &stack, double thickness, const Image &mask
   for (const Patches &p : per_slice) append(result, p);
 }
 
-#define PVRH(call) do { int rc_ = (call); if (rc_) die(std::string(#call) + ": " + pvrh_last_error(host)); } while (0)
-
-}  // namespace
-
-int main(int argc, char **argv) {
-  prog_name = "PVRreconstructionGPU";
+// ---- options (pvrmain:108-131) -----------------------------------------------------------------------
+struct Options {
   std::string output, mask_name;
   std::vector<std::string> inputs, tspecs;
   std::vector<double> thickness;
@@ -295,390 +300,419 @@ int main(int argc, char **argv) {
   int spx_size = 16, spx_extend = 50;                    // pvrmain:104-106
   std::string existing_name;                             // --existingReconTarget (pvrmain:118)
   std::string dump_name;                                 // test hooks: --dumpProblem <file> [--dryRun]
-  // ---- options (pvrmain:108-131) ---------------------------------------------------------------------
-  auto is_opt = [](const char *s) { return s[0] == '-' && !(s[1] >= '0' && s[1] <= '9') && s[1] != '.'; };
-  for (int i = 1; i < argc; ++i) {
-    const std::string o = argv[i];
-    auto multi = [&](std::vector<std::string> &dst) { while (i + 1 < argc && !is_opt(argv[i + 1])) dst.push_back(argv[++i]); };
-    auto ints = [&](std::vector<int> &dst) { std::vector<std::string> v; multi(v); for (auto &s : v) dst.push_back(atoi(s.c_str())); };
-    auto one = [&]() -> std::string { if (i + 1 >= argc) die("missing value for " + o); return argv[++i]; };
-    if (o == "-o" || o == "--output") output = one();
-    else if (o == "-m" || o == "--mask") mask_name = one();
-    else if (o == "-i" || o == "--input") multi(inputs);
-    else if (o == "-t" || o == "--transformation") multi(tspecs);
-    else if (o == "--thickness") { std::vector<std::string> v; multi(v); for (auto &s : v) thickness.push_back(atof(s.c_str())); }
-    else if (o == "--useFullSlices") full_slices = true;
-    else if (o == "--hierarchical") hierarchical = true;
-    else if (o == "--resample") resample = true;
-    else if (o == "--packages") ints(packages);
-    else if (o == "--dilateMask") dilate = atoi(one().c_str());
-    else if (o == "--existingReconTarget") existing_name = one();
-    else if (o == "--patchSize") ints(psize);
-    else if (o == "--patchStride") ints(pstride);
-    else if (o == "--resolution") resolution = atof(one().c_str());
-    else if (o == "--iterations") iterations = atoi(one().c_str());
-    else if (o == "--sr_iterations") sr_iterations = atoi(one().c_str());
-    else if (o == "--noMatchIntensities") no_matching = true;
-    else if (o == "--coeffTable") coeff_table = true;                      // not a reference option: keep the PSF taps in HBM
-    else if (o == "-d" || o == "--devices") ints(devices);
-    else if (o == "--dumpProblem") dump_name = one();
-    else if (o == "--dryRun") dry_run = true;
-    else if (o == "--no_registration") no_registration = true;
-    else if (o == "-s" || o == "--superpixel") superpixel = true;
-    else if (o == "--spxSize") spx_size = atoi(one().c_str());
-    else if (o == "--spxExtend") spx_extend = atoi(one().c_str());
-    else if (o == "-h" || o == "--help") {
-      printf("usage: PVRreconstructionGPU -o <volume> -i <stack_1> .. <stack_N> -m <mask> [-t id|<dof>|<4x4.txt> ..]\n"
-             "       [--thickness th_1 ..] [--patchSize 32 32] [--patchStride 16 16] [--resolution 0.75] [--iterations 7]\n"
-             "       [--sr_iterations 7] [--noMatchIntensities] [--no_registration] [-s [--spxSize 16] [--spxExtend 50]] [--useFullSlices] [-d device]\n");
-      return 0;
+};
+
+// the set-up's result (pvrmain:184-257, PBR.cpp:193-310): the same for every level
+struct Problem {
+  std::vector<Image> stacks;                             // the packages, where --packages splits them; cropped (and resampled)
+  std::vector<M4> ts;
+  std::vector<double> half_thickness;                    // m_thickness: dz, or the given thickness / 2 (pvrmain:209-217)
+  size_t tmpl = 0;
+  Image mask, iso_mask, recon_mask;
+  svr_image_attr tattr;
+  float vmin = 3.402823466e38f, vmax = 1.175494351e-38f;
+  std::vector<float> existing;                           // setExistingReconstructionTarget :185-191: the volume and its grid
+};
+
+// one irtkPatchBasedReconstruction<T>::run from the patch extraction on
+struct Level {
+  std::vector<int> psize, pstride;
+  int spx_size, iterations;
+  std::vector<float> existing;                           // the volume it starts from, or none
+  bool dump;                                             // --dumpProblem describes the first level
+};
+
+// what a level cuts and uploads; the per-patch arrays are in the global numbering (stack after stack) until shard_patches
+struct LevelPatches {
+  Patches P;
+  int px = 0, py = 0;
+  std::vector<char> spx_masks;
+  std::vector<int> counts;                               // patches per stack
+  std::vector<float> st, sti, dims;
+  std::vector<double> Td;                                // the registrators' m_transformations, one per patch
+  float vol_i2w[16], vol_w2i[16];                        // the volume's own matrices
+};
+
+void host_check(pvrh_recon *h, int rc, const char *what) { if (rc) die(std::string(what) + ": " + pvrh_last_error(h)); }
+#define PVRHR(r, call) host_check(hosts[r], (call), #call)
+
+void usage() {
+  printf("usage: PVRreconstructionGPU -o <volume> -i <stack_1> .. <stack_N> -m <mask> [-t id|<dof>|<4x4.txt> ..]\n"
+         "       [--thickness th_1 ..] [--patchSize 32 32] [--patchStride 16 16] [--resolution 0.75] [--iterations 7]\n"
+         "       [--sr_iterations 7] [--noMatchIntensities] [--no_registration] [-s [--spxSize 16] [--spxExtend 50]] [--useFullSlices] [-d device]\n");
+}
+
+Options parse_options(int argc, char **argv) {
+  Options p;
+  Args a{argc, argv};
+  while (a.next()) {
+    if (a.is("-o", "--output")) p.output = a.one();
+    else if (a.is("-m", "--mask")) p.mask_name = a.one();
+    else if (a.is("-i", "--input")) a.multi(p.inputs);
+    else if (a.is("-t", "--transformation")) a.multi(p.tspecs);
+    else if (a.is("--thickness")) a.doubles(p.thickness);
+    else if (a.is("--useFullSlices")) p.full_slices = true;
+    else if (a.is("--hierarchical")) p.hierarchical = true;
+    else if (a.is("--resample")) p.resample = true;
+    else if (a.is("--packages")) a.ints(p.packages);
+    else if (a.is("--dilateMask")) p.dilate = a.one_int();
+    else if (a.is("--existingReconTarget")) p.existing_name = a.one();
+    else if (a.is("--patchSize")) a.ints(p.psize);
+    else if (a.is("--patchStride")) a.ints(p.pstride);
+    else if (a.is("--resolution")) p.resolution = a.one_double();
+    else if (a.is("--iterations")) p.iterations = a.one_int();
+    else if (a.is("--sr_iterations")) p.sr_iterations = a.one_int();
+    else if (a.is("--noMatchIntensities")) p.no_matching = true;
+    else if (a.is("--coeffTable")) p.coeff_table = true;                   // not a reference option: keep the PSF taps in HBM
+    else if (a.is("-d", "--devices")) a.ints(p.devices);
+    else if (a.is("--dumpProblem")) p.dump_name = a.one();
+    else if (a.is("--dryRun")) p.dry_run = true;
+    else if (a.is("--no_registration")) p.no_registration = true;
+    else if (a.is("-s", "--superpixel")) p.superpixel = true;
+    else if (a.is("--spxSize")) p.spx_size = a.one_int();
+    else if (a.is("--spxExtend")) p.spx_extend = a.one_int();
+    else if (a.is("-h", "--help")) { usage(); exit(0); }
+    else die("option " + a.o + " is not supported by this build (see csrc/pvr_cli.cpp)");
+  }
+  if (p.output.empty() || p.inputs.empty() || p.mask_name.empty()) die("-o, -i and -m are required (try --help)");
+  if (p.psize.empty()) p.psize = {32, 32};
+  if (p.pstride.empty()) p.pstride = {16, 16};
+  if (p.psize.size() != 2 || p.pstride.size() != 2 || p.psize[0] < 1 || p.psize[1] < 1 || p.pstride[0] < 1 || p.pstride[1] < 1)
+    die("--patchSize and --patchStride take two positive integers");
+  if (p.tspecs.empty()) p.tspecs.assign(p.inputs.size(), "id");
+  if (p.tspecs.size() != p.inputs.size()) die("one transformation per stack expected");
+  return p;
+}
+
+// ---- set-up (pvrmain:184-257, PBR.cpp:193-310) --------------------------------------------------------
+// the stacks and their transformations, the thicknesses, the template's number; with --packages every package becomes a stack
+void read_inputs(const Options &opt, Problem &S) {
+  size_t n = opt.inputs.size();
+  S.stacks.resize(n);
+  parallel_for((int)n, [&](int k) { S.stacks[k] = read_image(opt.inputs[k]); });                 // gunzip is serial per file
+  for (size_t k = 0; k < n; ++k) S.ts.push_back(load_transformation(opt.tspecs[k]));
+}
+
+void split_stacks(const Options &opt, Problem &S) {
+  const size_t n = S.stacks.size();
+  if (opt.thickness.empty()) for (auto &s : S.stacks) S.half_thickness.push_back(s.a.dz);
+  else { if (opt.thickness.size() != n) die("one thickness per stack expected"); for (double t : opt.thickness) S.half_thickness.push_back(t / 2.0); }
+  for (size_t k = 0; k < n; ++k) if (opt.tspecs[k] == "id") { S.tmpl = k; break; }
+  if (opt.packages.size() != n) return;
+  std::vector<Image> ps;                                 // setImageStacks, PBR.cpp:134-146: every package becomes a stack of its own;
+  std::vector<M4> pt;                                    // m_template_num keeps indexing the new list
+  std::vector<double> ph;
+  for (size_t k = 0; k < n; ++k) {
+    if (opt.packages[k] < 1) die("--packages takes positive integers");
+    for (Image &p : split_packages(S.stacks[k], opt.packages[k])) { ps.push_back(std::move(p)); pt.push_back(S.ts[k]); ph.push_back(S.half_thickness[k]); }
+  }
+  S.stacks.swap(ps); S.ts.swap(pt); S.half_thickness.swap(ph);
+}
+
+void crop_to_mask(const Options &opt, Problem &S) {
+  S.mask = read_image(opt.mask_name);
+  for (double &v : S.mask.d) v = ((long long)v == 0) ? 0.0 : 1.0;                                // PBR.cpp:201-209
+  if (opt.dilate > 0) dilate_mask(S.mask, opt.dilate);                                           // :212-223
+  for (size_t k = 0; k < S.stacks.size(); ++k) {                                                 // :229-236
+    const Image m = transform_nn(S.mask, S.stacks[k].a, S.ts[k], 0.0);
+    S.stacks[k] = crop_image(S.stacks[k], m);
+    if (opt.resample) S.stacks[k] = resample_bspline(S.stacks[k], opt.resolution);             // :237-246
+  }
+}
+
+void register_stacks(const Options &opt, Problem &S) {   // irtkStack3D3DRegistration<T>::run, :280-285
+  svr_ctx *rctx = nullptr;
+  if (svr_create(opt.devices.empty() ? 0 : opt.devices[0], &rctx) || !rctx) die("no usable HIP device (svr_create failed)");
+  stack_registrations(rctx, S.stacks, S.ts, S.tmpl, &S.iso_mask, SVRH_STACKREG_KEEP_ORIGIN);
+  svr_destroy(rctx);
+}
+
+void make_template(const Options &opt, Problem &S) {
+  for (const Image &s : S.stacks)                                                                // computeMinMaxIntensities :792-814
+    for (double v : s.d)
+      if (v > 0) { S.vmax = std::max(S.vmax, (float)v); S.vmin = std::min(S.vmin, (float)v); }
+  S.tattr = resample_attr(S.stacks[S.tmpl].a, opt.resolution);                                   // CreateTemplate :941-965
+  if (!opt.existing_name.empty()) {
+    const Image ex = read_image(opt.existing_name);
+    S.tattr = ex.a;
+    S.existing.assign(ex.d.begin(), ex.d.end());
+  }
+  S.recon_mask = transform_nn(S.iso_mask, S.tattr, S.ts[S.tmpl], 0.0);                           // :303-304
+}
+
+// ---- one level -------------------------------------------------------------------------------------------
+// patches (PBR.cpp:385-399): square patches, every slice as one patch, or superpixels; per patch its stack's transformation and voxel size
+void cut_patches(const Options &opt, const Problem &S, const Level &lv, LevelPatches &C) {
+  Patches &P = C.P;
+  const size_t n = S.stacks.size();
+  int &px = C.px, &py = C.py;
+  px = lv.psize[0]; py = lv.psize[1];
+  if (opt.full_slices) {                                 // the patch is the slice; stacks of different sizes share a grid padded with -1
+    px = py = 0;
+    for (size_t k = 0; k < n; ++k) { px = std::max(px, S.stacks[k].a.nx); py = std::max(py, S.stacks[k].a.ny); }
+  }
+  for (size_t k = 0; k < n; ++k) {
+    const int before = P.n;
+    if (opt.superpixel) {                                // pvrmain:291-296: patch size = spxSize, stride = spxExtend
+      SpxPatches sp;
+      slic_superpixel_patches(S.stacks[k], S.half_thickness[k], S.iso_mask, lv.spx_size, lv.spx_size, opt.spx_extend, sp);
+      if (P.n > 0 && (sp.px != px || sp.py != py)) die("superpixel patches of different sizes (slices narrower than 64 pixels differ between the stacks)");
+      px = sp.px; py = sp.py;
+      append(P, sp);
+      C.spx_masks.insert(C.spx_masks.end(), sp.masks.begin(), sp.masks.end());
+    } else if (opt.full_slices) {                        // patchBasedObject.cuh:183-189: size = the slice, stride = size + 1
+      const int nx = S.stacks[k].a.nx, ny = S.stacks[k].a.ny;
+      Patches one;
+      generate_2d_patches(S.stacks[k], S.half_thickness[k], S.iso_mask, nx, ny, nx + 1, ny + 1, one);
+      std::vector<float> padded((size_t)one.n * px * py, -1.0f);
+      for (int q = 0; q < one.n; ++q)
+        for (int j = 0; j < ny; ++j) memcpy(&padded[((size_t)q * py + j) * px], &one.data[((size_t)q * ny + j) * nx], nx * sizeof(float));
+      one.data.swap(padded);
+      append(P, one);
     } else {
-      die("option " + o + " is not supported by this build (see csrc/pvr_cli.cpp)");
+      generate_2d_patches(S.stacks[k], S.half_thickness[k], S.iso_mask, px, py, lv.pstride[0], lv.pstride[1], P);
+    }
+    C.counts.push_back(P.n - before);
+    float t[16], ti[16];
+    to_f16(S.ts[k], t); to_f16(inverse_rigid_or_affine(S.ts[k]), ti);
+    for (int q = before; q < P.n; ++q) {
+      C.st.insert(C.st.end(), t, t + 16); C.sti.insert(C.sti.end(), ti, ti + 16);
+      C.Td.insert(C.Td.end(), S.ts[k].m, S.ts[k].m + 16);
+      C.dims.push_back((float)S.stacks[k].a.dx); C.dims.push_back((float)S.stacks[k].a.dy); C.dims.push_back((float)S.stacks[k].a.dz);   // getDim()
     }
   }
-  if (output.empty() || inputs.empty() || mask_name.empty()) die("-o, -i and -m are required (try --help)");
-  if (psize.empty()) psize = {32, 32};
-  if (pstride.empty()) pstride = {16, 16};
-  if (psize.size() != 2 || pstride.size() != 2 || psize[0] < 1 || psize[1] < 1 || pstride[0] < 1 || pstride[1] < 1)
-    die("--patchSize and --patchStride take two positive integers");
-  size_t n = inputs.size();
-  if (tspecs.empty()) tspecs.assign(n, "id");
-  if (tspecs.size() != n) die("one transformation per stack expected");
+}
 
+// what the engine is about to receive, for the CPU tests
+void dump_problem(const std::string &name, bool superpixel, const Problem &S, const LevelPatches &C) {
+  const Patches &P = C.P;
+  const svr_image_attr &tattr = S.tattr;
+  FILE *f = fopen(name.c_str(), "wb");
+  if (!f) die("cannot write " + name);
+  const int hdr[8] = {P.n, C.px, C.py, (int)S.stacks.size(), tattr.nx, tattr.ny, tattr.nz, 1};   // [7] = 1: the geometry block at the end
+  const float mm[2] = {S.vmin, S.vmax};
+  std::vector<float> mf(S.recon_mask.d.begin(), S.recon_mask.d.end());
+  fwrite(hdr, sizeof(int), 8, f); fwrite(C.counts.data(), sizeof(int), S.stacks.size(), f); fwrite(mm, sizeof(float), 2, f);
+  fwrite(P.data.data(), sizeof(float), P.data.size(), f); fwrite(P.i2w.data(), sizeof(float), P.i2w.size(), f);
+  fwrite(mf.data(), sizeof(float), mf.size(), f);
+  if (superpixel) fwrite(C.spx_masks.data(), 1, C.spx_masks.size(), f);
+  // everything else svr_set_slice_matrices / svr_set_slice_dims / svr_init_reconstruction_volume receive: per patch
+  // w2i, T, Tinv, dims; the volume's image-to-world / world-to-image matrices and voxel size
+  float gi2w[16], gw2i[16];
+  to_f16(image_to_world(tattr), gi2w); to_f16(world_to_image(tattr), gw2i);
+  const float gdim[3] = {(float)tattr.dx, (float)tattr.dy, (float)tattr.dz};
+  fwrite(P.w2i.data(), sizeof(float), P.w2i.size(), f); fwrite(C.st.data(), sizeof(float), C.st.size(), f);
+  fwrite(C.sti.data(), sizeof(float), C.sti.size(), f); fwrite(C.dims.data(), sizeof(float), C.dims.size(), f);
+  fwrite(gi2w, sizeof(float), 16, f); fwrite(gw2i, sizeof(float), 16, f); fwrite(gdim, sizeof(float), 3, f);
+  fclose(f);
+}
+
+// Ranks: one engine context per device of -d.  Rank r takes the r-th of nr work-balanced segments of EVERY stack's patches
+// (svr_shard.h spatial_order: a rank's patches are neighbours in space), work = the pixels that carry data, weighted by orientation.
+// From here on the per-patch arrays are in the SHARDED numbering (rank after rank); order[k] = patch k's index in the global numbering
+// (stack after stack), which the host object keeps using where the reference's arithmetic depends on it (pvrh_set_unit_order).  The
+// reference's patch-based path is single-GPU (patchBasedReconMain.cpp:78,177-179, irtkPatchBasedReconstruction.cpp:402); SURVEY 8e:
+// "identical with patches as the unit"
+void shard_patches(const Options &opt, const Problem &S, LevelPatches &C, Ranks &R) {
+  Patches &P = C.P;
+  const int ns = P.n, nr = (int)std::max<size_t>(1, opt.devices.size());
+  if (ns < nr) die("fewer patches than devices");
+  R.init(nr, ns);
+  if (nr == 1) return;
+  std::vector<double> work(ns, 0.0);
+  const size_t pp = (size_t)C.px * C.py;
+  const M4 rw = world_to_image(S.tattr);
+  parallel_for(ns, [&](int q) {
+    long c = 0;
+    for (size_t i = 0; i < pp; ++i) c += P.data[(size_t)q * pp + i] > 0.0f;
+    // a patch whose normal is the volume's x axis costs more per pixel (its runs span a band of centre planes, csrc/svr_cell.inc;
+    // measured per rank: tools/shard_probe.py, sharding.py slice_cost_weights): x (1 + 0.2 n_x^2)
+    double nv[3], len;
+    normal_in_volume_axes(&P.i2w[16 * (size_t)q], &C.st[16 * (size_t)q], rw, nv, len);
+    const double ax2 = len > 0 ? nv[0] * nv[0] / len : 0.0;
+    work[q] = (double)c * (1.0 + 0.2 * ax2);
+  });
+  std::vector<int> stack_of;
+  for (size_t k = 0; k < C.counts.size(); ++k) stack_of.insert(stack_of.end(), C.counts[k], (int)k);
+  svr::spatial_order(work, stack_of, nr, R.order, R.rlo, R.rhi);
+  for (int r = 0; r < nr; ++r) if (R.rhi[r] <= R.rlo[r]) die("a device would get no patch: fewer devices, please");
+  for (int k = 0; k < ns; ++k) R.inv_order[R.order[k]] = k;
+  svr::permute_rows(P.data, pp, R.order);
+  svr::permute_rows(P.i2w, 16, R.order); svr::permute_rows(P.w2i, 16, R.order); svr::permute_rows(P.attr, 1, R.order);
+  if (opt.superpixel) svr::permute_rows(C.spx_masks, 4096, R.order);
+  svr::permute_rows(C.st, 16, R.order); svr::permute_rows(C.sti, 16, R.order); svr::permute_rows(C.dims, 3, R.order); svr::permute_rows(C.Td, 16, R.order);
+}
+
+// upload (the engine in PVR mode; m_quality_factor = 1, PBR.cpp:415), per rank, and every rank's host object
+void setup_engines(const Options &opt, const Problem &S, const Level &lv, LevelPatches &C, const Ranks &R, std::vector<pvrh_recon *> &hosts) {
+  const Patches &P = C.P;
+  const svr_image_attr &tattr = S.tattr;
+  const int px = C.px, py = C.py;
+  const uint32_t vsize[3] = {(uint32_t)tattr.nx, (uint32_t)tattr.ny, (uint32_t)tattr.nz};
+  const float vdim[3] = {(float)tattr.dx, (float)tattr.dy, (float)tattr.dz};
+  const std::vector<float> maskf(S.recon_mask.d.begin(), S.recon_mask.d.end());
+  to_f16(image_to_world(tattr), C.vol_i2w); to_f16(world_to_image(tattr), C.vol_w2i);
+  if (!lv.existing.empty() && lv.existing.size() != (size_t)tattr.nx * tattr.ny * tattr.nz) die("existing reconstruction target of the wrong size");
+  float pi2w[16], pw2i[16];
+  psf_volume_matrices(tattr, pi2w, pw2i);
+  hosts.assign(R.nr, nullptr);
+  R.par([&](int r) {
+    svr_ctx *c = R.ctxs[r];
+    const int nl = R.rhi[r] - R.rlo[r];
+    const size_t o = (size_t)R.rlo[r];
+    ENGR(R, r, svr_set_option(c, "pvr", 1));
+    if (opt.coeff_table) ENGR(R, r, svr_set_option(c, "coeff_table", 1));
+    ENGR(R, r, svr_init_reconstruction_volume(c, vsize, vdim, lv.existing.empty() ? nullptr : lv.existing.data(), 12.0f));   // copyFromHost :310-314
+    ENGR(R, r, svr_set_mask(c, vsize, vdim, maskf.data(), 12.0f));
+    const uint32_t ssize[3] = {(uint32_t)px, (uint32_t)py, (uint32_t)nl};
+    std::vector<int> sizes_x(nl, px), sizes_y(nl, py);
+    ENGR(R, r, svr_init_storage_volumes(c, ssize, &C.dims[3 * o]));
+    ENGR(R, r, svr_fill_slices(c, P.data.data() + o * px * py, sizes_x.data(), sizes_y.data()));
+    if (opt.superpixel) ENGR(R, r, svr_set_spx_masks(c, C.spx_masks.data() + o * 4096));
+    ENGR(R, r, svr_set_slice_dims(c, C.dims.data() + 3 * o, 1.0f));
+    const uint32_t psz[3] = {128, 128, 128};
+    ENGR(R, r, svr_generate_psf_volume(c, nullptr, psz, &C.dims[3 * o], vdim, pi2w, pw2i, 1.0f));
+    R.set_matrices(r, C.st, C.sti, P.i2w, P.w2i, C.vol_i2w, C.vol_w2i);
+    hosts[r] = pvrh_create_sharded(c, C.counts.data(), (int)C.counts.size(), S.vmin, S.vmax, R.rlo[r], R.rhi[r], R.group ? svr_group_join(R.group, r, c) : nullptr);
+    if (!hosts[r]) die("pvrh_create_sharded failed" + std::string(R.group ? " (the rank group could not be joined)" : ""));
+    if (R.nr > 1 && pvrh_set_unit_order(hosts[r], R.order.data())) die("pvrh_set_unit_order failed");
+  });
+  std::string per_rank = ", patches per rank";
+  for (int r = 0; r < R.nr; ++r) per_rank += " " + std::to_string(R.rhi[r] - R.rlo[r]);
+  R.describe(opt.devices, per_rank);
+}
+
+// PBR.cpp:452-489: runHybrid, the IRTK schedule on every patch; every rank registers its own patches against the shared volume
+void register_patches(const Problem &S, LevelPatches &C, const Ranks &R) {
+  const Patches &P = C.P;
+  const int px = C.px, py = C.py;
+  std::vector<float> vol((size_t)S.tattr.nx * S.tattr.ny * S.tattr.nz);
+  ENGR(R, 0, svr_sync_cpu(R.ctxs[0], vol.data()));       // m_GPURecon.copyToHost (every rank holds the same volume)
+  std::vector<long> evals(R.nr, 0);
+  R.par([&](int r) {
+    char e[256] = {0};
+    const size_t o = (size_t)R.rlo[r];
+    if (svrh_slice_to_volume_registration(R.ctxs[r], nullptr, R.rhi[r] - R.rlo[r], P.data.data() + o * px * py, px, py, P.attr.data() + o,
+                                          C.Td.data() + 16 * o, &S.tattr, vol.data(), SVRH_S2V_NO_RESAMPLE, &evals[r], e))
+      die(std::string("patch-to-volume registration: ") + e);
+  });
+  R.update_matrices(C.Td, C.st, C.sti, P.i2w, P.w2i, C.vol_i2w, C.vol_w2i);   // updateTransformationMatrices (patchBasedObject.cuh:151-169)
+  long total = 0;
+  for (long v : evals) total += v;
+  fprintf(stderr, "patch-to-volume registration: %ld similarity evaluations\n", total);
+}
+
+// the loop (PBR.cpp:445-593)
+void run_iterations(const Options &opt, const Problem &S, const Level &lv, LevelPatches &C, const Ranks &R, const std::vector<pvrh_recon *> &hosts,
+                    StageClock &clk) {
+  for (int it = 0; it < lv.iterations + 1; ++it) {
+    const bool have_volume = it > 0 || !lv.existing.empty();                                   // PBR.cpp:456
+    if (have_volume && !opt.no_registration && opt.superpixel) {
+      // runHybrid registers the square CPU patches of generatePatchesCPU and updateTransformationMatrices then reads one
+      // transformation per GPU patch from that shorter list: undefined in the reference for superpixel patches, not done
+      fprintf(stderr, "superpixel mode: the patch-to-volume registration is skipped\n");
+    } else if (have_volume && !opt.no_registration) {
+      register_patches(S, C, R);
+    }
+    if (have_volume && !opt.no_registration) clk.mark("registration of the patches");
+    R.par([&](int r) { PVRHR(r, pvrh_reconstruct_iteration(hosts[r], opt.sr_iterations)); });
+    clk.mark("reconstruction iteration");
+    double sc[8];
+    pvrh_get_state(hosts[0], nullptr, nullptr, nullptr, sc);
+    fprintf(stderr, "iteration %d: sigma %.4g mix %.3f\n", it, sc[0], sc[1]);
+  }
+}
+
+// one level from the patch extraction on (the set-up gives the same result every time); false: --dryRun stopped it
+bool run_level(const Options &opt, const Problem &S, const Level &lv, StageClock &clk, std::vector<float> &vol_out) {
+  const svr_image_attr &tattr = S.tattr;
+  LevelPatches C;
+  cut_patches(opt, S, lv, C);
+  clk.mark("patch generation");
+  if (C.P.n == 0) die("no patch overlaps the mask");
+  fprintf(stderr, "%zu stacks, %d patches of %dx%d, volume %dx%dx%d at %g mm\n", S.stacks.size(), C.P.n, C.px, C.py, tattr.nx, tattr.ny, tattr.nz, opt.resolution);
+  if (!opt.dump_name.empty() && lv.dump) dump_problem(opt.dump_name, opt.superpixel, S, C);
+  if (opt.dry_run) return false;
+
+  Ranks R;
+  std::vector<pvrh_recon *> hosts;
+  shard_patches(opt, S, C, R);
+  for (int r = 0; r < R.nr; ++r) R.create_context(r, opt.devices.empty() ? 0 : opt.devices[r]);
+  R.create_group(opt.devices);
+  setup_engines(opt, S, lv, C, R, hosts);
+  clk.mark("engine set-up and upload");
+  run_iterations(opt, S, lv, C, R, hosts, clk);
+  vol_out.resize((size_t)tattr.nx * tattr.ny * tattr.nz);
+  ENGR(R, 0, svr_sync_cpu(R.ctxs[0], vol_out.data()));
+  if (clk.on) {
+    int o[6] = {0, 0, 0, 0, 0, 0};
+    const char *names[6] = {"tile_w", "tile_h", "wave_cap", "fwd_tile_w", "fwd_tile_h", "fwd_unit_cap"};
+    for (int k = 0; k < 6; ++k) (void)svr_get_option(R.ctxs[0], names[k], &o[k]);
+    fprintf(stderr, "[timing] tuned: scatter tiles %dx%d box %d, gather tiles %dx%d box %d\n", o[0], o[1], o[2], o[3], o[4], o[5]);
+  }
+  clk.mark("volume download");
+  for (pvrh_recon *h : hosts) pvrh_destroy(h);
+  R.destroy();
+  return true;
+}
+
+// pvrmain:359-432: iterations + 1 levels of one registration-reconstruction iteration each; a level starts from the volume of
+// the level before (its "reconimage1_<size>_<stride>.nii.gz") and cuts patches 4 pixels smaller (stride 2 smaller, not for superpixels)
+bool run_hierarchical(const Options &opt, const Problem &S, StageClock &clk, std::vector<float> &vol) {
+  Level lv{opt.psize, opt.pstride, opt.spx_size, 1, S.existing, true};
+  std::vector<int> &ps = lv.psize, &pt = lv.pstride;
+  for (int level = 0; level <= opt.iterations; ++level) {
+    if (opt.superpixel ? lv.spx_size < 1 : (ps[0] < 1 || ps[1] < 1 || pt[0] < 1 || pt[1] < 1))
+      die("hierarchical mode: the patch size reached zero at level " + std::to_string(level) + " (--patchSize - 4 * --iterations must stay positive)");
+    fprintf(stderr, "hierarchical level %d: patch size %d stride %d\n", level, opt.superpixel ? lv.spx_size : ps[0], opt.superpixel ? opt.spx_extend : pt[0]);
+    if (!run_level(opt, S, lv, clk, vol)) return false;
+    lv.existing = vol;
+    lv.dump = false;
+    if (opt.superpixel) lv.spx_size -= 4;
+    else { ps[0] -= 4; ps[1] -= 4; pt[0] -= 2; pt[1] -= 2; }
+  }
+  return true;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  prog_name = "PVRreconstructionGPU";
+  const Options opt = parse_options(argc, argv);
   StageClock clk;
   // the HIP runtime comes up on a second thread while the stacks are read: a first context (the stack-to-stack registration
   // makes one, the reconstruction another) then costs milliseconds instead of 75
   std::future<void> runtime_up = std::async(std::launch::async, [&] {
     svr_ctx *warm = nullptr;
-    if (!dry_run && svr_create(devices.empty() ? 0 : devices[0], &warm) == 0 && warm) svr_destroy(warm);
+    if (!opt.dry_run && svr_create(opt.devices.empty() ? 0 : opt.devices[0], &warm) == 0 && warm) svr_destroy(warm);
   });
   before_exit = [&] { if (runtime_up.valid()) runtime_up.wait(); };
-  // ---- set-up (pvrmain:184-257, PBR.cpp:193-310) --------------------------------------------------------
-  std::vector<Image> stacks;
-  std::vector<M4> ts;
-  stacks.resize(n);
-  parallel_for((int)n, [&](int k) { stacks[k] = read_image(inputs[k]); });                        // gunzip is serial per file
-  for (size_t k = 0; k < n; ++k) ts.push_back(load_transformation(tspecs[k]));
+  Problem S;
+  read_inputs(opt, S);
   clk.mark("read stacks");
-  std::vector<double> half_thickness;                    // m_thickness: dz, or the given thickness / 2 (pvrmain:209-217)
-  if (thickness.empty()) for (auto &s : stacks) half_thickness.push_back(s.a.dz);
-  else { if (thickness.size() != n) die("one thickness per stack expected"); for (double t : thickness) half_thickness.push_back(t / 2.0); }
-  size_t tmpl = 0;
-  for (size_t k = 0; k < n; ++k) if (tspecs[k] == "id") { tmpl = k; break; }
-  if (packages.size() == n) {                            // setImageStacks, PBR.cpp:134-146: every package becomes a stack of its own;
-    std::vector<Image> ps;                               // m_template_num keeps indexing the new list
-    std::vector<M4> pt;
-    std::vector<double> ph;
-    for (size_t k = 0; k < n; ++k) {
-      if (packages[k] < 1) die("--packages takes positive integers");
-      for (Image &p : split_packages(stacks[k], packages[k])) { ps.push_back(std::move(p)); pt.push_back(ts[k]); ph.push_back(half_thickness[k]); }
-    }
-    stacks.swap(ps); ts.swap(pt); half_thickness.swap(ph);
-    n = stacks.size();
-  }
-  Image mask = read_image(mask_name);
-  for (double &v : mask.d) v = ((long long)v == 0) ? 0.0 : 1.0;                               // PBR.cpp:201-209
-  if (dilate > 0) dilate_mask(mask, dilate);                                                     // :212-223
-  for (size_t k = 0; k < n; ++k) {                                                               // :229-236
-    const Image m = transform_nn(mask, stacks[k].a, ts[k], 0.0);
-    stacks[k] = crop_image(stacks[k], m);
-    if (resample) stacks[k] = resample_bspline(stacks[k], resolution);                          // :237-246
-  }
+  split_stacks(opt, S);
+  crop_to_mask(opt, S);
   clk.mark("mask, crop (resample)");
-  const Image iso_mask = transform_nn(mask, resample_attr(mask.a, resolution), ident(), 0.0);    // :258-266
+  S.iso_mask = transform_nn(S.mask, resample_attr(S.mask.a, opt.resolution), ident(), 0.0);      // :258-266
   clk.mark("isotropic mask");
   if (runtime_up.valid()) runtime_up.wait();
-  if (!no_registration && n > 1) {                       // irtkStack3D3DRegistration<T>::run, :280-285
-    svr_ctx *rctx = nullptr;
-    if (svr_create(devices.empty() ? 0 : devices[0], &rctx) || !rctx) die("no usable HIP device (svr_create failed)");
-    std::vector<svr_image_attr> at(n);
-    std::vector<const double *> ptr(n);
-    std::vector<double> tm(16 * n);
-    for (size_t k = 0; k < n; ++k) { at[k] = stacks[k].a; ptr[k] = stacks[k].d.data(); for (int q = 0; q < 16; ++q) tm[16 * k + q] = ts[k].m[q]; }
-    long evals = 0;
-    char e[256] = {0};
-    if (svrh_stack_registrations(rctx, nullptr, (int)n, at.data(), ptr.data(), tm.data(), (int)tmpl, &iso_mask.a, iso_mask.d.data(),
-                                 SVRH_STACKREG_KEEP_ORIGIN, &evals, e))
-      die(std::string("stack registration: ") + e);
-    for (size_t k = 0; k < n; ++k) for (int q = 0; q < 16; ++q) ts[k].m[q] = tm[16 * k + q];
-    fprintf(stderr, "stack-to-stack registration: %ld similarity evaluations\n", evals);
-    svr_destroy(rctx);
-  }
+  if (!opt.no_registration && S.stacks.size() > 1) register_stacks(opt, S);
   clk.mark("registration of the stacks");
-  if (!no_matching) match_stack_intensities_pvr(stacks, ts, iso_mask);                           // :288-294
+  if (!opt.no_matching) match_stack_intensities_pvr(S.stacks, S.ts, S.iso_mask);                 // :288-294
   clk.mark("match stack intensities");
-  float vmin = 3.402823466e38f, vmax = 1.175494351e-38f;                                         // computeMinMaxIntensities :792-814
-  for (const Image &s : stacks)
-    for (double v : s.d)
-      if (v > 0) { vmax = std::max(vmax, (float)v); vmin = std::min(vmin, (float)v); }
-  svr_image_attr tattr = resample_attr(stacks[tmpl].a, resolution);                              // CreateTemplate :941-965
-  std::vector<float> existing;                           // setExistingReconstructionTarget :185-191: the volume and its grid
-  if (!existing_name.empty()) {
-    const Image ex = read_image(existing_name);
-    tattr = ex.a;
-    existing.assign(ex.d.begin(), ex.d.end());
-  }
-  const Image recon_mask = transform_nn(iso_mask, tattr, ts[tmpl], 0.0);                         // :303-304
+  make_template(opt, S);
   clk.mark("template, reconstruction mask");
-  if (superpixel && full_slices) die("--superpixel with --useFullSlices is not supported by this build");
-  if (hierarchical && full_slices) hierarchical = false;                                         // pvrmain:282-285 "SVR ON"
-  bool first_level = true;
-
-  // one irtkPatchBasedReconstruction<T>::run from the patch extraction on (the set-up above gives the same result every time)
-  auto run_level = [&](const std::vector<int> &psize, const std::vector<int> &pstride, int iterations, const std::vector<float> &existing,
-                       std::vector<float> &vol_out) -> bool {
-  // ---- patches (PBR.cpp:385-399) -----------------------------------------------------------------------
-  int px = psize[0], py = psize[1];
-  if (full_slices) {                                     // the patch is the slice; stacks of different sizes share a grid padded with -1
-    px = py = 0;
-    for (size_t k = 0; k < n; ++k) { px = std::max(px, stacks[k].a.nx); py = std::max(py, stacks[k].a.ny); }
-  }
-  Patches P;
-  std::vector<char> spx_masks;
-  std::vector<int> counts;
-  std::vector<float> st, sti, dims;
-  std::vector<double> Td;                                // the registrators' m_transformations, one per patch
-  for (size_t k = 0; k < n; ++k) {
-    const int before = P.n;
-    if (superpixel) {                                    // pvrmain:291-296: patch size = spxSize, stride = spxExtend
-      SpxPatches sp;
-      slic_superpixel_patches(stacks[k], half_thickness[k], iso_mask, spx_size, spx_size, spx_extend, sp);
-      if (P.n > 0 && (sp.px != px || sp.py != py)) die("superpixel patches of different sizes (slices narrower than 64 pixels differ between the stacks)");
-      px = sp.px; py = sp.py;
-      P.data.insert(P.data.end(), sp.data.begin(), sp.data.end());
-      P.i2w.insert(P.i2w.end(), sp.i2w.begin(), sp.i2w.end()); P.w2i.insert(P.w2i.end(), sp.w2i.begin(), sp.w2i.end());
-      P.ri2w.insert(P.ri2w.end(), sp.ri2w.begin(), sp.ri2w.end()); P.mo.insert(P.mo.end(), sp.mo.begin(), sp.mo.end());
-      P.invmo.insert(P.invmo.end(), sp.invmo.begin(), sp.invmo.end());
-      P.attr.insert(P.attr.end(), sp.attr.begin(), sp.attr.end());
-      spx_masks.insert(spx_masks.end(), sp.masks.begin(), sp.masks.end());
-      P.n += sp.n;
-    } else if (full_slices) {                            // patchBasedObject.cuh:183-189: size = the slice, stride = size + 1
-      const int nx = stacks[k].a.nx, ny = stacks[k].a.ny;
-      Patches one;
-      generate_2d_patches(stacks[k], half_thickness[k], iso_mask, nx, ny, nx + 1, ny + 1, one);
-      for (int q = 0; q < one.n; ++q) {
-        std::vector<float> padded((size_t)px * py, -1.0f);
-        for (int j = 0; j < ny; ++j) memcpy(&padded[(size_t)j * px], &one.data[((size_t)q * ny + j) * nx], nx * sizeof(float));
-        P.data.insert(P.data.end(), padded.begin(), padded.end());
-      }
-      P.i2w.insert(P.i2w.end(), one.i2w.begin(), one.i2w.end()); P.w2i.insert(P.w2i.end(), one.w2i.begin(), one.w2i.end());
-      P.ri2w.insert(P.ri2w.end(), one.ri2w.begin(), one.ri2w.end()); P.mo.insert(P.mo.end(), one.mo.begin(), one.mo.end());
-      P.invmo.insert(P.invmo.end(), one.invmo.begin(), one.invmo.end());
-      P.attr.insert(P.attr.end(), one.attr.begin(), one.attr.end());
-      P.n += one.n;
-    } else {
-      generate_2d_patches(stacks[k], half_thickness[k], iso_mask, px, py, pstride[0], pstride[1], P);
-    }
-    counts.push_back(P.n - before);
-    float t[16], ti[16];
-    to_f16(ts[k], t); to_f16(inverse_rigid_or_affine(ts[k]), ti);
-    for (int q = before; q < P.n; ++q) {
-      st.insert(st.end(), t, t + 16); sti.insert(sti.end(), ti, ti + 16);
-      Td.insert(Td.end(), ts[k].m, ts[k].m + 16);
-      dims.push_back((float)stacks[k].a.dx); dims.push_back((float)stacks[k].a.dy); dims.push_back((float)stacks[k].a.dz);   // getDim()
-    }
-  }
-  clk.mark("patch generation");
-  const int ns = P.n;
-  if (ns == 0) die("no patch overlaps the mask");
-  fprintf(stderr, "%zu stacks, %d patches of %dx%d, volume %dx%dx%d at %g mm\n", n, ns, px, py, tattr.nx, tattr.ny, tattr.nz, resolution);
-
-  if (!dump_name.empty() && first_level) {               // what the engine is about to receive, for the CPU tests
-    FILE *f = fopen(dump_name.c_str(), "wb");
-    if (!f) die("cannot write " + dump_name);
-    const int hdr[8] = {ns, px, py, (int)n, tattr.nx, tattr.ny, tattr.nz, 1};   // [7] = 1: the geometry block at the end
-    const float mm[2] = {vmin, vmax};
-    std::vector<float> mf(recon_mask.d.begin(), recon_mask.d.end());
-    fwrite(hdr, sizeof(int), 8, f); fwrite(counts.data(), sizeof(int), n, f); fwrite(mm, sizeof(float), 2, f);
-    fwrite(P.data.data(), sizeof(float), P.data.size(), f); fwrite(P.i2w.data(), sizeof(float), P.i2w.size(), f);
-    fwrite(mf.data(), sizeof(float), mf.size(), f);
-    if (superpixel) fwrite(spx_masks.data(), 1, spx_masks.size(), f);
-    {
-      // everything else svr_set_slice_matrices / svr_set_slice_dims / svr_init_reconstruction_volume receive: per patch
-      // w2i, T, Tinv, dims; the volume's image-to-world / world-to-image matrices and voxel size
-      float gi2w[16], gw2i[16];
-      to_f16(image_to_world(tattr), gi2w); to_f16(world_to_image(tattr), gw2i);
-      const float gdim[3] = {(float)tattr.dx, (float)tattr.dy, (float)tattr.dz};
-      fwrite(P.w2i.data(), sizeof(float), P.w2i.size(), f); fwrite(st.data(), sizeof(float), st.size(), f);
-      fwrite(sti.data(), sizeof(float), sti.size(), f); fwrite(dims.data(), sizeof(float), dims.size(), f);
-      fwrite(gi2w, sizeof(float), 16, f); fwrite(gw2i, sizeof(float), 16, f); fwrite(gdim, sizeof(float), 3, f);
-    }
-    fclose(f);
-  }
-  if (dry_run) return false;
-  first_level = false;
-
-  // ---- ranks: one engine context per device of -d.  Rank r takes the r-th of nr work-balanced segments of EVERY stack's patches
-  // (svr_shard.h spatial_order: a rank's patches are neighbours in space), work = the pixels that carry data, weighted by orientation.
-  // From here on the per-patch arrays are in the SHARDED numbering (rank after rank); order[k] = patch k's index in the global numbering
-  // (stack after stack), which the host object keeps using where the reference's arithmetic depends on it (pvrh_set_unit_order).  The
-  // reference's patch-based path is single-GPU (patchBasedReconMain.cpp:78,177-179, irtkPatchBasedReconstruction.cpp:402); SURVEY 8e:
-  // "identical with patches as the unit"
-  const int nr = (int)std::max<size_t>(1, devices.size());
-  if (ns < nr) die("fewer patches than devices");
-  std::vector<int> rlo(nr, 0), rhi(nr, ns), order;
-  if (nr > 1) {
-    std::vector<double> work(ns, 0.0);
-    const size_t pp = (size_t)px * py;
-    parallel_for(ns, [&](int q) {
-      long c = 0;
-      for (size_t i = 0; i < pp; ++i) c += P.data[(size_t)q * pp + i] > 0.0f;
-      // a patch whose normal is the volume's x axis costs more per pixel (its runs span a band of centre planes, csrc/svr_cell.inc;
-      // measured per rank: tools/shard_probe.py, sharding.py slice_cost_weights): x (1 + 0.2 n_x^2)
-      const M4 rw = world_to_image(tattr);
-      double nw[3], nt[3], nv[3], len = 0;
-      for (int k = 0; k < 3; ++k) nw[k] = P.i2w[16 * (size_t)q + 4 * k + 2];
-      for (int k = 0; k < 3; ++k) nt[k] = st[16 * (size_t)q + 4 * k] * nw[0] + st[16 * (size_t)q + 4 * k + 1] * nw[1] + st[16 * (size_t)q + 4 * k + 2] * nw[2];
-      for (int k = 0; k < 3; ++k) { nv[k] = rw.m[4 * k] * nt[0] + rw.m[4 * k + 1] * nt[1] + rw.m[4 * k + 2] * nt[2]; len += nv[k] * nv[k]; }
-      const double ax2 = len > 0 ? nv[0] * nv[0] / len : 0.0;
-      work[q] = (double)c * (1.0 + 0.2 * ax2);
-    });
-    std::vector<int> stack_of;
-    for (size_t k = 0; k < counts.size(); ++k) stack_of.insert(stack_of.end(), counts[k], (int)k);
-    svr::spatial_order(work, stack_of, nr, order, rlo, rhi);
-    for (int r = 0; r < nr; ++r) if (rhi[r] <= rlo[r]) die("a device would get no patch: fewer devices, please");
-    svr::permute_rows(P.data, pp, order);
-    svr::permute_rows(P.i2w, 16, order); svr::permute_rows(P.w2i, 16, order); svr::permute_rows(P.attr, 1, order);
-    if (superpixel) svr::permute_rows(spx_masks, 4096, order);
-    svr::permute_rows(st, 16, order); svr::permute_rows(sti, 16, order); svr::permute_rows(dims, 3, order); svr::permute_rows(Td, 16, order);
-  }
-  std::vector<svr_ctx *> ctxs(nr, nullptr);
-  std::vector<pvrh_recon *> hosts(nr, nullptr);
-  for (int r = 0; r < nr; ++r)
-    if (svr_create(devices.empty() ? 0 : devices[r], &ctxs[r]) || !ctxs[r])
-      die("no usable HIP device " + std::to_string(devices.empty() ? 0 : devices[r]) + " (svr_create failed)");
-  svr_ctx *ctx = ctxs[0];
-  svr_group *group = nr > 1 ? svr_group_create(nr, devices.data()) : nullptr;
-  if (nr > 1 && !group) die("cannot set up the rank group (librccl not found?)");
-  auto par = [&](const std::function<void(int)> &fn) {   // every rank in its own thread (the collectives block until all have arrived)
-    if (nr == 1) { fn(0); return; }
-    std::vector<std::thread> th;
-    for (int r = 0; r < nr; ++r) th.emplace_back(fn, r);
-    for (auto &t : th) t.join();
-  };
-#define ENGR(r, call) do { int rc_ = (call); if (rc_) die(std::string(#call) + ": " + svr_last_error(ctxs[r])); } while (0)
-#define PVRHR(r, call) do { int rc_ = (call); if (rc_) die(std::string(#call) + ": " + pvrh_last_error(hosts[r])); } while (0)
-
-  // ---- upload (the engine in PVR mode; m_quality_factor = 1, PBR.cpp:415), per rank --------------------------------
-  const uint32_t vsize[3] = {(uint32_t)tattr.nx, (uint32_t)tattr.ny, (uint32_t)tattr.nz};
-  const float vdim[3] = {(float)tattr.dx, (float)tattr.dy, (float)tattr.dz};
-  std::vector<float> maskf(recon_mask.d.begin(), recon_mask.d.end());
-  float ri2w[16], rw2i[16];
-  to_f16(image_to_world(tattr), ri2w); to_f16(world_to_image(tattr), rw2i);
-  if (!existing.empty() && existing.size() != (size_t)tattr.nx * tattr.ny * tattr.nz) die("existing reconstruction target of the wrong size");
-  float pi2w[16], pw2i[16];
-  {
-    svr_image_attr pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.nx = pa.ny = pa.nz = 128; pa.dx = tattr.dx; pa.dy = tattr.dy; pa.dz = tattr.dz;
-    pa.xaxis[0] = pa.yaxis[1] = pa.zaxis[2] = 1.0;
-    to_f16(image_to_world(pa), pi2w); to_f16(world_to_image(pa), pw2i);
-  }
-  auto set_matrices = [&](int r) {
-    const size_t o = 16 * (size_t)rlo[r];
-    ENGR(r, svr_set_slice_matrices(ctxs[r], st.data() + o, sti.data() + o, P.i2w.data() + o, P.w2i.data() + o, P.i2w.data() + o, P.w2i.data() + o, ri2w, rw2i));
-  };
-  par([&](int r) {
-    const int nl = rhi[r] - rlo[r];
-    const size_t o = (size_t)rlo[r];
-    ENGR(r, svr_set_option(ctxs[r], "pvr", 1));
-    if (coeff_table) ENGR(r, svr_set_option(ctxs[r], "coeff_table", 1));
-    ENGR(r, svr_init_reconstruction_volume(ctxs[r], vsize, vdim, existing.empty() ? nullptr : existing.data(), 12.0f));   // copyFromHost :310-314
-    ENGR(r, svr_set_mask(ctxs[r], vsize, vdim, maskf.data(), 12.0f));
-    const uint32_t ssize[3] = {(uint32_t)px, (uint32_t)py, (uint32_t)nl};
-    std::vector<int> sizes_x(nl, px), sizes_y(nl, py);
-    ENGR(r, svr_init_storage_volumes(ctxs[r], ssize, &dims[3 * o]));
-    ENGR(r, svr_fill_slices(ctxs[r], P.data.data() + o * px * py, sizes_x.data(), sizes_y.data()));
-    if (superpixel) ENGR(r, svr_set_spx_masks(ctxs[r], spx_masks.data() + o * 4096));
-    ENGR(r, svr_set_slice_dims(ctxs[r], dims.data() + 3 * o, 1.0f));
-    const uint32_t psz[3] = {128, 128, 128};
-    ENGR(r, svr_generate_psf_volume(ctxs[r], nullptr, psz, &dims[3 * o], vdim, pi2w, pw2i, 1.0f));
-    set_matrices(r);
-    hosts[r] = pvrh_create_sharded(ctxs[r], counts.data(), (int)counts.size(), vmin, vmax, rlo[r], rhi[r],
-                                   group ? svr_group_join(group, r, ctxs[r]) : nullptr);
-    if (!hosts[r]) die("pvrh_create_sharded failed" + std::string(group ? " (the rank group could not be joined)" : ""));
-    if (nr > 1 && pvrh_set_unit_order(hosts[r], order.data())) die("pvrh_set_unit_order failed");
-  });
-  if (nr > 1)
-    fprintf(stderr, "%d ranks on devices%s, patches per rank%s, collectives: %s\n", nr,
-            [&] { std::string t; for (int d : devices) t += " " + std::to_string(d); return t; }().c_str(),
-            [&] { std::string t; for (int r = 0; r < nr; ++r) t += " " + std::to_string(rhi[r] - rlo[r]); return t; }().c_str(),
-            svr_group_uses_rccl(group) ? "RCCL" : "host memory (a device is named more than once: test mode)");
-
-  clk.mark("engine set-up and upload");
-  // ---- the loop (PBR.cpp:445-593) ----------------------------------------------------------------------------
-  pvrh_recon *host = hosts[0];
-  for (int it = 0; it < iterations + 1; ++it) {
-    const bool have_volume = it > 0 || !existing.empty();                                      // PBR.cpp:456
-    if (have_volume && !no_registration && superpixel) {
-      // runHybrid registers the square CPU patches of generatePatchesCPU and updateTransformationMatrices then reads one
-      // transformation per GPU patch from that shorter list: undefined in the reference for superpixel patches, not done
-      fprintf(stderr, "superpixel mode: the patch-to-volume registration is skipped\n");
-    } else if (have_volume && !no_registration) {        // PBR.cpp:452-489: runHybrid, the IRTK schedule on every patch
-      std::vector<float> vol((size_t)tattr.nx * tattr.ny * tattr.nz);
-      ENG(svr_sync_cpu(ctx, vol.data()));                // m_GPURecon.copyToHost (every rank holds the same volume)
-      std::vector<long> evals(nr, 0);
-      par([&](int r) {                                   // every rank registers its own patches against the shared volume
-        char e[256] = {0};
-        const size_t o = (size_t)rlo[r];
-        if (svrh_slice_to_volume_registration(ctxs[r], nullptr, rhi[r] - rlo[r], P.data.data() + o * px * py, px, py, P.attr.data() + o,
-                                              Td.data() + 16 * o, &tattr, vol.data(), SVRH_S2V_NO_RESAMPLE, &evals[r], e))
-          die(std::string("patch-to-volume registration: ") + e);
-      });
-      for (int q = 0; q < ns; ++q) {                     // updateTransformationMatrices (patchBasedObject.cuh:151-169)
-        M4 t;
-        for (int k = 0; k < 16; ++k) t.m[k] = Td[16 * (size_t)q + k];
-        to_f16(t, &st[16 * (size_t)q]); to_f16(inverse_rigid_or_affine(t), &sti[16 * (size_t)q]);
-      }
-      for (int r = 0; r < nr; ++r) set_matrices(r);
-      long total = 0;
-      for (long v : evals) total += v;
-      fprintf(stderr, "patch-to-volume registration: %ld similarity evaluations\n", total);
-    }
-    if (have_volume && !no_registration) clk.mark("registration of the patches");
-    par([&](int r) { PVRHR(r, pvrh_reconstruct_iteration(hosts[r], sr_iterations)); });
-    clk.mark("reconstruction iteration");
-    double sc[8];
-    pvrh_get_state(host, nullptr, nullptr, nullptr, sc);
-    fprintf(stderr, "iteration %d: sigma %.4g mix %.3f\n", it, sc[0], sc[1]);
-  }
-  vol_out.resize((size_t)tattr.nx * tattr.ny * tattr.nz);
-  ENG(svr_sync_cpu(ctx, vol_out.data()));
-  if (clk.on) {
-    int o[6] = {0, 0, 0, 0, 0, 0};
-    const char *names[6] = {"tile_w", "tile_h", "wave_cap", "fwd_tile_w", "fwd_tile_h", "fwd_unit_cap"};
-    for (int k = 0; k < 6; ++k) (void)svr_get_option(ctx, names[k], &o[k]);
-    fprintf(stderr, "[timing] tuned: scatter tiles %dx%d box %d, gather tiles %dx%d box %d\n", o[0], o[1], o[2], o[3], o[4], o[5]);
-  }
-  clk.mark("volume download");
-  for (int r = 0; r < nr; ++r) pvrh_destroy(hosts[r]);
-  svr_group_destroy(group);
-  for (int r = 0; r < nr; ++r) svr_destroy(ctxs[r]);
-  return true;
-  };
-
+  if (opt.superpixel && opt.full_slices) die("--superpixel with --useFullSlices is not supported by this build");
   std::vector<float> vol;
-  if (!hierarchical) {
-    if (!run_level(psize, pstride, iterations, existing, vol)) return 0;
+  if (opt.hierarchical && !opt.full_slices) {            // (with --useFullSlices: pvrmain:282-285 "SVR ON", one level)
+    if (!run_hierarchical(opt, S, clk, vol)) return 0;
   } else {
-    // pvrmain:359-432: iterations + 1 levels of one registration-reconstruction iteration each; a level starts from the volume of
-    // the level before (its "reconimage1_<size>_<stride>.nii.gz") and cuts patches 4 pixels smaller (stride 2 smaller, not for superpixels)
-    std::vector<int> ps = psize, pt = pstride;
-    for (int level = 0; level <= iterations; ++level) {
-      if (superpixel ? spx_size < 1 : (ps[0] < 1 || ps[1] < 1 || pt[0] < 1 || pt[1] < 1))
-        die("hierarchical mode: the patch size reached zero at level " + std::to_string(level) + " (--patchSize - 4 * --iterations must stay positive)");
-      fprintf(stderr, "hierarchical level %d: patch size %d stride %d\n", level, superpixel ? spx_size : ps[0], superpixel ? spx_extend : pt[0]);
-      std::vector<float> next;
-      if (!run_level(ps, pt, 1, existing, next)) return 0;
-      existing = next;
-      vol.swap(next);
-      if (superpixel) spx_size -= 4;
-      else { ps[0] -= 4; ps[1] -= 4; pt[0] -= 2; pt[1] -= 2; }
-    }
+    if (!run_level(opt, S, Level{opt.psize, opt.pstride, opt.spx_size, opt.iterations, S.existing, true}, clk, vol)) return 0;
   }
   clk.mark("engine teardown");
   char err[256] = {0};
-  if (svr_nifti_write(output.c_str(), &tattr, vol.data(), err)) die(output + ": " + err);
+  if (svr_nifti_write(opt.output.c_str(), &S.tattr, vol.data(), err)) die(opt.output + ": " + err);
   clk.mark("write the volume");
   return 0;
 }
+

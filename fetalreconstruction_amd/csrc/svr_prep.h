@@ -328,9 +328,6 @@ M4 load_transformation(const std::string &spec) {
 
 void to_f16(const M4 &m, float *out) { for (int i = 0; i < 16; ++i) out[i] = (float)m.m[i]; }
 
-#define ENG(call) do { int rc_ = (call); if (rc_) die(std::string(#call) + ": " + svr_last_error(ctx)); } while (0)
-#define HOST(call) do { int rc_ = (call); if (rc_) die(std::string(#call) + ": " + svrh_last_error(host)); } while (0)
-
 }  // namespace
 
 #endif  // SVR_PREP_H
