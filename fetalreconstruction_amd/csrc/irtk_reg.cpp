@@ -18,7 +18,9 @@
 // engine's svr_ncc_evaluate: exact integer moments, so the accept / reject decisions of the optimiser do not depend on
 // where the cost is evaluated.  With SVRH_SIM_NMI (the reference's --useNMI) it is irtkNormalisedMutualInformationSimilarity-
 // Metric: the levels are binned (irtkCalculateNumberOfBins) and svr_nmi_evaluate returns integer joint histograms' entropy
-// sums added in the reference's order, equal to nmi_sums below bit for bit -- the same guarantee.  All targets that share a source are optimised in lock step: one optimiser step of every
+// sums added in the reference's order, equal to nmi_sums below bit for bit -- the same guarantee.  With SVRH_SIM_LNCC (a
+// deviation: the reference has no local metric) it is the windowed cross correlation of svr_lncc_evaluate, per plane the
+// integers {N, S} added over the planes of an evaluation -- again independent of where it is evaluated.  All targets that share a source are optimised in lock step: one optimiser step of every
 // target (its similarity, its 12 finite differences, or one line-search probe) is ONE batched evaluate call.  A 3-D target
 // (a stack) is handed to the engine as its z-planes, each with the start position the reference's iterator reaches by
 // repeated addition (irtkHomogeneousTransformationIterator.h:96-199), and the six moments are added up.
@@ -385,6 +387,11 @@ struct Backend {                                           // the engine, or wha
   int evaluate(int n, const int *idx, const double *m, int64_t *sums) const {
     return be ? be->evaluate(be->user, n, idx, m, sums, nullptr) : svr_ncc_evaluate(ctx, n, idx, m, sums, nullptr);
   }
+  // {N, S} per plane at sums[stride * plane]: the engine's (stride 2), or the first two entries of the caller's six
+  int lncc_stride() const { return be ? 6 : 2; }
+  int evaluate_lncc(int n, const int *idx, const double *m, int radius, int64_t *sums) const {
+    return be ? be->evaluate(be->user, n, idx, m, sums, nullptr) : svr_lncc_evaluate(ctx, n, idx, m, radius, sums, nullptr);
+  }
   // {n, S_xy, S_x, S_y} per evaluation: the engine's, or nmi_sums of the caller's histograms
   int evaluate_nmi(int n, const int *ppe, const int *idx, const double *m, const int *width, const int *nbins, int source_nbins, double *out4,
                    std::vector<uint32_t> &hist) const {
@@ -464,11 +471,23 @@ struct GridKey {
 };
 struct GridGroup { std::vector<int> members; size_t offset = 0; };
 
-// irtkImageRegistration::Run for every target against one source, in lock step; nmi: the similarity is NMI instead of CC
-// (GuessParameterSliceToVolume(useNMI), IRRWP.cc:319-321: the schedule, the optimiser and epsilon are the same)
+// SVRH_SIM_* and the LNCC radius of the `similarity` of the _ex entry points (radius 0 = 3); false = refused
+bool parse_similarity(int similarity, int &sim, int &radius) {
+  sim = similarity & 0xff;
+  radius = (similarity >> 8) & 0xffffff;
+  if (similarity < 0 || (sim != SVRH_SIM_CC && sim != SVRH_SIM_NMI && sim != SVRH_SIM_LNCC)) return false;
+  if (sim != SVRH_SIM_LNCC) return radius == 0;
+  if (radius == 0) radius = 3;
+  return radius >= 1 && radius <= 7;
+}
+
+// irtkImageRegistration::Run for every target against one source, in lock step; sim: the similarity is NMI instead of CC
+// (GuessParameterSliceToVolume(useNMI), IRRWP.cc:319-321: the schedule, the optimiser and epsilon are the same), or the
+// windowed cross correlation of radius lncc_radius (neither image binned)
 int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol<short> &source, int slice_to_volume, short target_padding,
-                      int nmi, long *n_eval, std::string &err) {
+                      int sim, int lncc_radius, long *n_eval, std::string &err) {
   if (targets.empty()) return 0;
+  const int nmi = sim == SVRH_SIM_NMI, lncc = sim == SVRH_SIM_LNCC;
   const short source_padding = guess_padding(source);
   const bool timing = getenv("SVR_REG_TIMING") != nullptr;        // dev: where a registration pass spends its wall time
   double t_src = 0, t_tgt = 0, t_pack = 0, t_opt = 0, t_eval = 0;
@@ -617,7 +636,7 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
       if (live.empty()) break;
       idx.resize(n_planes); mats.resize(16 * (size_t)n_planes); value.resize(n_req);
       if (nmi) { req_planes.resize(n_req); req_width.resize(n_req); req_nbins.resize(n_req); out4.resize(4 * (size_t)n_req); }
-      else sums.resize(6 * (size_t)n_planes);
+      else sums.resize((lncc ? be.lncc_stride() : 6) * (size_t)n_planes);
       over_live(3000, [&](int l0, int l1) {
         for (int l = l0; l < l1; ++l) {
           const Target &t = targets[live[l]];
@@ -653,6 +672,11 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
           err = be.external() ? "svr_nmi_evaluate failed" : std::string("svr_nmi_evaluate: ") + svr_last_error(be.ctx);
           return 2;
         }
+      } else if (lncc) {
+        if (be.evaluate_lncc(n_planes, idx.data(), mats.data(), lncc_radius, sums.data())) {
+          err = be.external() ? "svr_lncc_evaluate failed" : std::string("svr_lncc_evaluate: ") + svr_last_error(be.ctx);
+          return 2;
+        }
       } else if (be.evaluate(n_planes, idx.data(), mats.data(), sums.data())) { err = "svr_ncc_evaluate failed"; return 2; }
       t_eval += now() - te; ++rounds;
       if (n_eval) *n_eval += (long)n_req;
@@ -664,6 +688,12 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
             if (nmi) { value[req_off[l] + q] = nmi_from_sums(&out4[4 * ((size_t)req_off[l] + q)]); continue; }
             int64_t sacc[6] = {0, 0, 0, 0, 0, 0};
             const size_t at = (size_t)plane_off[l] + (size_t)q * nz;
+            if (lncc) {                                        // (sum S / sum N) / 2^24 over the planes of the evaluation
+              const int st = be.lncc_stride();
+              for (int c = 0; c < nz; ++c) { sacc[0] += sums[st * (at + c)]; sacc[1] += sums[st * (at + c) + 1]; }
+              value[req_off[l] + q] = sacc[0] > 0 ? ((double)sacc[1] / (double)sacc[0]) / 16777216.0 : 0.0;
+              continue;
+            }
             for (int c = 0; c < nz; ++c) for (int k = 0; k < 6; ++k) sacc[k] += sums[6 * (at + c) + k];
             value[req_off[l] + q] = ncc_from_sums(sacc);
           }
@@ -716,7 +746,7 @@ int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol
   }
   if (timing)
     fprintf(stderr, "[svr reg timing] %s: source pyramid %.1f ms, target pyramids %.1f ms, pack + upload %.1f ms, optimiser %.1f ms (%ld rounds, %.1f ms in the batched evaluations)\n",
-            nmi ? "NMI" : "CC", 1e3 * t_src, 1e3 * t_tgt, 1e3 * t_pack, 1e3 * t_opt, rounds, 1e3 * t_eval);
+            nmi ? "NMI" : lncc ? "LNCC" : "CC", 1e3 * t_src, 1e3 * t_tgt, 1e3 * t_pack, 1e3 * t_opt, rounds, 1e3 * t_eval);
   return 0;
 }
 
@@ -790,7 +820,7 @@ int svrh_stack_registrations(svr_ctx *ctx, const svr_ncc_backend *backend, int n
     one[0].matrix = mul(T[s], mo);                                        // include the offset: PutMatrix(m * mo)
     matrix_to_params(one[0].matrix, one[0].p);
     std::string e;
-    const int rc = run_registrations(be, one, source, 0, (short)0, 0, n_evaluations_or_null, e);   // ThickSlices, SetTargetPadding(0)
+    const int rc = run_registrations(be, one, source, 0, (short)0, SVRH_SIM_CC, 0, n_evaluations_or_null, e);   // ThickSlices, SetTargetPadding(0)
     if (rc) { set_err(err, e); return rc; }
     T[s] = mul(params_to_matrix(one[0].p), mo_inv);                       // undo the offset
   }
@@ -812,8 +842,10 @@ int svrh_slice_to_volume_registration_ex(svr_ctx *ctx, const svr_ncc_backend *ba
                                          int n_slices, const float *slices, int sx, int sy, const svr_image_attr *attrs, double *transformations,
                                          const svr_image_attr *recon_attr, const float *reconstructed, int flags, long *n_evaluations_or_null,
                                          char err[256]) {
-  const int nmi = similarity == SVRH_SIM_NMI;
-  if ((similarity != SVRH_SIM_CC && !nmi) || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_slices < 1 || !slices ||
+  int sim = 0, radius = 0;
+  const bool known = parse_similarity(similarity, sim, radius);
+  const int nmi = sim == SVRH_SIM_NMI;
+  if (!known || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_slices < 1 || !slices ||
       !attrs || !transformations || !recon_attr || !reconstructed) {
     set_err(err, "svrh_slice_to_volume_registration: bad arguments");
     return 1;
@@ -863,7 +895,7 @@ int svrh_slice_to_volume_registration_ex(svr_ctx *ctx, const svr_ncc_backend *ba
     which.push_back(s);
   }
   std::string e;
-  const int rc = run_registrations(be, targets, source, 1, (short)-1, nmi, n_evaluations_or_null, e);   // SliceToVolume, SetTargetPadding(-1)
+  const int rc = run_registrations(be, targets, source, 1, (short)-1, sim, radius, n_evaluations_or_null, e);   // SliceToVolume, SetTargetPadding(-1)
   if (rc) { set_err(err, e); return rc; }
   for (size_t k = 0; k < targets.size(); ++k) {
     const M4 m = mul(params_to_matrix(targets[k].p), mo_inv[which[k]]);
@@ -931,8 +963,10 @@ int svrh_package_to_volume_ex(svr_ctx *ctx, const svr_ncc_backend *backend, cons
                               const svr_image_attr *attrs, const double *const *stacks, const int *pack_num, int evenodd, int half, int half_iter,
                               double *transformations, const svr_image_attr *recon_attr, const float *reconstructed, long *n_evaluations_or_null,
                               char err[256]) {
-  const int nmi = similarity == SVRH_SIM_NMI;
-  if ((similarity != SVRH_SIM_CC && !nmi) || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_stacks < 1 || !attrs ||
+  int sim = 0, radius = 0;
+  const bool known = parse_similarity(similarity, sim, radius);
+  const int nmi = sim == SVRH_SIM_NMI;
+  if (!known || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_stacks < 1 || !attrs ||
       !stacks || !pack_num || !transformations || !recon_attr || !reconstructed) {
     set_err(err, "svrh_package_to_volume: bad arguments");
     return 1;
@@ -987,7 +1021,7 @@ int svrh_package_to_volume_ex(svr_ctx *ctx, const svr_ncc_backend *backend, cons
     matrix_to_params(tg.matrix, tg.p);
   }
   std::string e;
-  const int rc = run_registrations(be, targets, source, 1, (short)0, nmi, n_evaluations_or_null, e);
+  const int rc = run_registrations(be, targets, source, 1, (short)0, sim, radius, n_evaluations_or_null, e);
   if (rc) { set_err(err, e); return rc; }
   for (size_t k = 0; k < packs.size(); ++k) {
     const M4 m = mul(params_to_matrix(targets[k].p), packs[k].mo_inv);      // PutMatrix: the first slice keeps this matrix

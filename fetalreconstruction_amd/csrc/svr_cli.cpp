@@ -16,7 +16,8 @@
 // stack-to-stack registration (StackRegistrations, before and after the other stacks are cropped, main.cc:661,711).
 // Slice-to-volume registration is the reference's default IRTK schedule (csrc/irtk_reg.cpp, every similarity evaluation
 // on the GPU) or, with --useGPUReg, the reference's GPU registration.  --no_registration (not a reference option) skips
-// both.  --useNMI makes the IRTK schedule's slice-to-volume and package-to-volume registrations use normalised mutual
+// both.  --useLNCC [--lnccRadius 3] makes the same two registrations use a windowed cross correlation (csrc/svr_lncc.inc), which
+// tolerates the bias field that is only estimated after the slices are registered; the reference has no such metric.  --useNMI makes the IRTK schedule's slice-to-volume and package-to-volume registrations use normalised mutual
 // information (csrc/svr_nmi.inc), as GuessParameterSliceToVolume(true) would; the reference parses it and never passes it
 // on (main.cc:210), so this is a deviation; the GPU registration stays CC-only and refuses it.  --enableBiasCorrection (not a reference option either: the reference hard-wires its bias correction off) runs
 // BiasGPU / NormaliseBiasGPU in every SR iteration with --sigma, --global_bias_correction and --low_intensity_cutoff as the
@@ -74,7 +75,8 @@ struct Options {
   std::vector<int> force_excluded, devices, packages;
   int iterations = 4, levels = 3, rec_first = 4, rec_last = 13, num_stacks_tuner = 0;
   double resolution = 0.75, average = 700, delta = 150, lambda = 0.02, last_lambda = 0.01, smooth_mask = 4;
-  bool no_matching = false, use_gpu_reg = false, no_registration = false, use_nmi = false;
+  bool no_matching = false, use_gpu_reg = false, no_registration = false, use_nmi = false, use_lncc = false;
+  int lncc_radius = 3;
   bool auto_template = false, auto_central = false;                      // --useAutoTemplate (main.cc:199), --autoTemplateCentral (not a reference option)
   double sigma = 12.0, low_intensity_cutoff = 0.01;                      // main.cc:172, 181
   bool enable_bias = false, global_bias = false;                         // --enableBiasCorrection (not a reference option), --global_bias_correction
@@ -135,6 +137,7 @@ void usage() {
          "       [--rec_iterations_first 4] [--rec_iterations_last 13] [--packages p_1 ..] [--useGPUReg] [--no_registration] [--tfolder dir] [--sfolder dir]\n"
          "       [--saveSliceTransformations] [--coeffTable | --noCoeffTable] [-d device_1 .. device_N]\n"
          "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
+         "       [--useLNCC] [--lnccRadius 3]\n"
          "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix] [--referenceVolume file]\n"
          "       [--channelStacks f_1 .. f_N --channelOutput file] [--labelStacks f_1 .. f_N --labelOutput file [--labelConfidence file]]\n"
          "       [--manualMask file]\n"
@@ -194,6 +197,13 @@ void usage() {
          "  --useNMI                deviation from the reference, whose --useNMI is parsed and never takes effect: slice-to-volume and\n"
          "                          package-to-volume registration use normalised mutual information (64 bins, IRTK's histogram metric)\n"
          "                          instead of cross correlation -- for stacks whose contrast differs.  Not with --useGPUReg (CC only).\n"
+         "  --useLNCC               deviation from the reference, which has no local metric: slice-to-volume and package-to-volume\n"
+         "                          registration use a windowed normalised cross correlation -- the signed squared correlation of every\n"
+         "                          (2 radius + 1)^2 window, averaged -- instead of the global one.  It ignores any intensity change that is\n"
+         "                          linear inside a window, so slices register under a bias field (coil falloff, differing receive fields)\n"
+         "                          that --enableBiasCorrection only estimates afterwards.  Stack-to-stack registration stays CC.\n"
+         "                          Not with --useNMI, not with --useGPUReg (CC only).\n"
+         "  --lnccRadius            radius of that window in pixels of the registration level, 1 .. 7 [3].\n"
          "  --enableBiasCorrection  deviation from the reference, whose bias correction cannot be switched on: run BiasGPU and\n"
          "                          NormaliseBiasGPU in every SR iteration (bias field stdev --sigma mm; sigma <= 0: no bias step).\n"
          "                          Without it bias correction is off, as in the reference; --disableBiasCorrection is accepted and changes nothing.\n");
@@ -406,6 +416,8 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
     else if (a.is("--rec_iterations_last")) p.rec_last = a.one_int();
     else if (a.is("--useGPUReg")) p.use_gpu_reg = true;
     else if (a.is("--useNMI")) p.use_nmi = true;                          // main.cc:210 parses it and never calls setUseNMI(): here it takes effect
+    else if (a.is("--useLNCC")) p.use_lncc = true;                        // not reference options: a local metric for the IRTK registration
+    else if (a.is("--lnccRadius")) p.lncc_radius = a.one_int();
     else if (a.is("--useAutoTemplate")) p.auto_template = true;           // main.cc:199, 565-591 (there: HAVE_CULA builds only)
     else if (a.is("--autoTemplateCentral")) p.auto_template = p.auto_central = true;   // the middle third of the slices instead of the first
     else if (a.is("-p", "--packages")) a.ints(p.packages);
@@ -455,6 +467,11 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
   if (p.use_nmi && p.use_gpu_reg)
     die("--useNMI selects normalised mutual information for the IRTK registration; the reference's GPU registration (--useGPUReg) is "
         "cross-correlation only: use one or the other");
+  if (p.use_lncc && p.use_nmi) die("--useLNCC and --useNMI each select the similarity of the IRTK registration: use one or the other");
+  if (p.use_lncc && p.use_gpu_reg)
+    die("--useLNCC selects the windowed cross correlation for the IRTK registration; the reference's GPU registration (--useGPUReg) is "
+        "cross-correlation only: use one or the other");
+  if (p.use_lncc && (p.lncc_radius < 1 || p.lncc_radius > 7)) die("--lnccRadius must be 1 .. 7 (the window is (2 radius + 1)^2 pixels)");
   if (p.num_stacks_tuner > 0 && (size_t)p.num_stacks_tuner < p.inputs.size()) {      // main.cc:406-419: only the first stacks are used
     p.inputs.resize(p.num_stacks_tuner);
     if (p.tspecs.size() > (size_t)p.num_stacks_tuner) p.tspecs.resize(p.num_stacks_tuner);
@@ -757,6 +774,10 @@ void seed_reference_volume(const Options &opt, const Problem &P, const Ranks &R)
   fprintf(stderr, "reference volume: n=%.0f mean=%.9g min=%.9g max=%.9g scale=%.9g\n", rs[0], rmean, rs[3], rs[4], rscale);
 }
 
+// the similarity of the IRTK schedule's slice- and package-to-volume registrations, and what the registration lines call it
+int reg_similarity(const Options &opt) { return opt.use_nmi ? SVRH_SIM_NMI : opt.use_lncc ? SVRH_SIM_LNCC | (opt.lncc_radius << 8) : SVRH_SIM_CC; }
+std::string reg_metric(const Options &opt) { return opt.use_lncc ? " (LNCC, radius " + std::to_string(opt.lncc_radius) + ")" : ""; }
+
 // ---- registration-reconstruction loop (main.cc:816-1237) ---------------------------------------------
 // packages first (main.cc:832-864): plain, even/odd, even/odd halves; from iteration 4 on also the slices
 void register_packages(const Options &opt, Problem &P, const Ranks &R, int it) {
@@ -769,11 +790,11 @@ void register_packages(const Options &opt, Problem &P, const Ranks &R, int it) {
   long evals = 0;
   char e[256] = {0};
   svr::unpermute_rows(P.T, 16, R.order);                                 // (packages are sub-stacks: one transformation per slice, stack after stack)
-  if (svrh_package_to_volume_ex(R.ctxs[0], nullptr, nullptr, opt.use_nmi ? SVRH_SIM_NMI : SVRH_SIM_CC, (int)n, at.data(), ptr.data(), opt.packages.data(),
+  if (svrh_package_to_volume_ex(R.ctxs[0], nullptr, nullptr, reg_similarity(opt), (int)n, at.data(), ptr.data(), opt.packages.data(),
                                 it >= 2, it >= 3, it >= 4 ? it - 2 : 1, P.T.data(), &P.tattr, vol.data(), &evals, e))
     die(std::string("package-to-volume registration: ") + e);
   svr::permute_rows(P.T, 16, R.order);
-  fprintf(stderr, "package-to-volume registration: %ld similarity evaluations\n", evals);
+  fprintf(stderr, "package-to-volume registration%s: %ld similarity evaluations\n", reg_metric(opt).c_str(), evals);
 }
 
 void register_slices(const Options &opt, Problem &P, const Ranks &R, const std::vector<svrh_recon *> &hosts) {   // main.cc:829-880
@@ -784,10 +805,10 @@ void register_slices(const Options &opt, Problem &P, const Ranks &R, const std::
     ENGR(R, 0, svr_sync_cpu(R.ctxs[0], vol.data()));                      // _reconstructed after SyncCPU, main.cc:1189
     long evals = 0;
     char e[256] = {0};
-    if (svrh_slice_to_volume_registration_ex(R.ctxs[0], nullptr, nullptr, opt.use_nmi ? SVRH_SIM_NMI : SVRH_SIM_CC, P.ns, P.grid.data(), P.mx, P.my,
+    if (svrh_slice_to_volume_registration_ex(R.ctxs[0], nullptr, nullptr, reg_similarity(opt), P.ns, P.grid.data(), P.mx, P.my,
                                              P.sattr.data(), P.T.data(), &P.tattr, vol.data(), 0, &evals, e))
       die(std::string("slice-to-volume registration: ") + e);
-    fprintf(stderr, "slice-to-volume registration: %ld similarity evaluations\n", evals);
+    fprintf(stderr, "slice-to-volume registration%s: %ld similarity evaluations\n", reg_metric(opt).c_str(), evals);
   }
   update_matrices_from_T(P, R);
 }

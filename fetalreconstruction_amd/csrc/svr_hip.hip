@@ -1243,6 +1243,8 @@ struct svr_ctx {
   size_t nmi_terms_n = 0;
   unsigned *d_nmi_merge = nullptr;       // merge slots of split evaluations + their counters, all zero between calls
   size_t nmi_slots = 0;
+  unsigned char *d_lncc_io = nullptr;    // grow-only scratch of svr_lncc_evaluate (svr_lncc.inc): requests in, {N, S} and the k maps out
+  size_t lncc_cap = 0;
   float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
   double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
   double *d_qual_partial = nullptr, *d_qual_sums = nullptr;   // svr_slice_quality (svr_quality.inc): likewise
@@ -2298,6 +2300,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_pyr_full[0]); free_dev(ctx->d_pyr_full[1]); free_dev(ctx->d_pyr_a); free_dev(ctx->d_pyr_b); free_dev(ctx->d_pyr_meta);
   free_dev(ctx->d_ncc_idx); free_dev(ctx->d_ncc_m); free_dev(ctx->d_ncc_s);
   free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
+  free_dev(ctx->d_lncc_io);
   free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
   free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums);
   free_dev(ctx->d_ssim_partial); free_dev(ctx->d_ssim_sums); free_dev(ctx->d_ssim_map);
@@ -3890,6 +3893,7 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 #include "svr_reg.inc"
 #include "svr_pyr.inc"
 #include "svr_nmi.inc"
+#include "svr_lncc.inc"
 #include "svr_motion.inc"
 #include "svr_quality.inc"
 #include "svr_ssim.inc"

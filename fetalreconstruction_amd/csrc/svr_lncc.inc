@@ -1,0 +1,185 @@
+// svr_lncc.inc -- local (windowed) normalised cross correlation of the default (IRTK) registration on the device; included by
+// svr_hip.hip.  A deviation from the reference, which has no local metric (--useLNCC, DESIGN 9).
+//
+// The sampling is k_ncc's (svr_small.inc), operation for operation: the source position from the evaluation's 4 x 4 in double, the
+// strict inside test, double trilinear in EvaluateInside's order, value >= 0, IRTK round().  V = the target pixels (tv >= 0) that
+// pass all of it; both operands are then integers in 0..32767.  With radius R the window of pixel p is the (2R+1)^2 box around
+// it, clipped to the plane and restricted to V.  Over the window, in exact integers,
+//   m, St, Ss, Stt, Sss, Sts,   A = m Sts - St Ss,   B = m Stt - St^2,   C = m Sss - Ss^2      (all below 2^53)
+// p is counted iff p in V, m >= ((2R+1)^2 + 1) / 2 and B > 0 (the target window has structure).  A counted pixel scores q = 0 if
+// C == 0, else q = (A / B) * (A / C) negated when A < 0 -- the signed squared local correlation, two IEEE double divisions and one
+// multiplication -- and k = (int64) floor(q 2^24 + 0.5).  A plane's result is {N, S} = {counted pixels, sum of k}: everything
+// added is an integer, so no order of summation matters and the result equals a serial restatement's bit for bit.
+//
+// One 256-thread workgroup per (plane, candidate), as k_ncc.  The plane is walked in bands of 32 rows (and, beyond 256 columns,
+// in strips of 256 columns); every pixel of a band is sampled ONCE into LDS as one 32-bit word t | valid << 15 | s << 16 (0 = not in
+// V, and 0 too for the halo outside the plane, so the window loops do not clip).  The rows live in a ring of 32 + 2R slots: a band
+// samples only the rows the band before it did not, its R-row halo stays where it is.  The window sums are separable: a thread owns
+// one column of a run of rows, forms the 2R+1-wide row sums of a row from LDS (consecutive lanes read consecutive words) and slides
+// them down its column -- add the row entering the window, subtract the row leaving it, exact in integers -- so a pixel costs two
+// row sums instead of (2R+1)^2 taps and nothing but the samples is ever stored.  m, St, Ss are 32-bit (at most 225 x 32767), the
+// three product sums 64-bit (a product of two shorts fits 32 bits, 225 of them do not).  {N, S} are reduced with wave_sum_i64.
+// LDS: (32 + 2R) x (columns + 2R) words, sized per launch: 15 KB for a 100-pixel-wide slice at R = 3, 49 KB at most (R = 7, 256
+// columns) -- within the 64 KB a workgroup may declare statically.
+
+namespace {
+
+constexpr int LNCC_BH = 32;                   // output rows of a band
+constexpr int LNCC_RMAX = 7;
+
+struct LnccRow { unsigned m, st, ss; unsigned long long tt, sss, ts; };
+
+// the 2R+1-wide sums of one ring row, window starting at word `w` (the halo columns hold 0)
+__device__ __forceinline__ LnccRow lncc_row(const unsigned *w, int R) {
+  LnccRow r = {0u, 0u, 0u, 0ull, 0ull, 0ull};
+  for (int d = 0; d <= 2 * R; ++d) {
+    const unsigned pk = w[d], t = pk & 0x7fffu, s = pk >> 16;
+    r.m += (pk >> 15) & 1u; r.st += t; r.ss += s;
+    r.tt += t * t; r.sss += s * s; r.ts += t * s;              // 32767^2 < 2^32
+  }
+  return r;
+}
+
+__global__ __launch_bounds__(256) void k_lncc(const short *targets, int tx, int ty, const int *target_index, const double *mats,
+                                              const short *source, int vx, int vy, int vz, int R, int cw_log2, long long *sums2,
+                                              int *kmap) {
+  extern __shared__ unsigned lncc_pk[];                        // [LNCC_BH + 2R][CW + 2R], row r of the plane in slot (r + R) % NR
+  __shared__ long long red[4][2];
+  const int e = blockIdx.x;
+  const short *tgt = targets + (size_t)target_index[e] * tx * ty;
+  const double *M = mats + 16 * (size_t)e;
+  const double m00 = M[0], m01 = M[1], m03 = M[3], m10 = M[4], m11 = M[5], m13 = M[7], m20 = M[8], m21 = M[9], m23 = M[11];
+  const double sx2 = vx - 1, sy2 = vy - 1, sz2 = vz - 1;
+  const size_t o3 = vx, o5 = (size_t)vx * vy;
+  const int CW = 1 << cw_log2, WIN = CW + 2 * R, NR = LNCC_BH + 2 * R, SEG = (LNCC_BH * CW) >> 8;   // rows a thread walks per band
+  const int c = threadIdx.x & (CW - 1), g = threadIdx.x >> cw_log2;
+  const int need = ((2 * R + 1) * (2 * R + 1) + 1) / 2;
+  int *km = kmap ? kmap + (size_t)e * tx * ty : nullptr;
+  long long acc_n = 0, acc_s = 0;
+  for (int x0 = 0; x0 < tx; x0 += CW) {                        // strips: one for every plane up to 256 columns
+    for (int y0 = 0; y0 < ty; y0 += LNCC_BH) {
+      // ---- sample the rows this band adds to the ring: [-R, BH + R) for the first band, [y0 + R, y0 + BH + R) after it ----
+      const int r_lo = y0 == 0 ? -R : y0 + R, n_new = y0 + LNCC_BH + R - r_lo;
+      for (int p = threadIdx.x; p < n_new * WIN; p += 256) {
+        const int rr = p / WIN, cc = p - rr * WIN, j = r_lo + rr, i = x0 - R + cc;
+        unsigned pk = 0;
+        if (j >= 0 && j < ty && i >= 0 && i < tx) {
+          const int tv = tgt[(size_t)j * tx + i];
+          if (tv >= 0) {
+            const double X = m00 * i + m01 * j + m03, Y = m10 * i + m11 * j + m13, Z = m20 * i + m21 * j + m23;
+            if ((X > 0) && (X < sx2) && (Y > 0) && (Y < sy2) && (Z > 0) && (Z < sz2)) {
+              const int a = (int)X, b = (int)Y, cz = (int)Z;
+              const double t1 = X - a, u1 = Y - b, v1 = Z - cz, t2 = 1 - t1, u2 = 1 - u1, v2 = 1 - v1;
+              const short *q = source + a + (size_t)b * o3 + (size_t)cz * o5;
+              const double value = (t1 * (u2 * (v2 * q[1] + v1 * q[o5 + 1]) + u1 * (v2 * q[o3 + 1] + v1 * q[o5 + o3 + 1])) +
+                                    t2 * (u2 * (v2 * q[0] + v1 * q[o5]) + u1 * (v2 * q[o3] + v1 * q[o5 + o3])));
+              if (value >= 0) {
+                const int sv = value > 0 ? (int)(value + 0.5) : (int)(value - 0.5);   // irtkCommon.h:85-88
+                pk = (unsigned)tv | 0x8000u | ((unsigned)sv << 16);
+              }
+            }
+          }
+        }
+        lncc_pk[((j + R) % NR) * WIN + cc] = pk;
+      }
+      __syncthreads();
+      // ---- the windows of rows [ya, ya + SEG) of column x0 + c: row sums slid down the column -----------------------------
+      const int ya = y0 + g * SEG, x = x0 + c;
+      if (x < tx && ya < ty) {
+        unsigned m = 0, st = 0, ss = 0;
+        unsigned long long tt = 0, sss = 0, ts = 0;
+        for (int j = ya - R; j < ya + R; ++j) {                // rows ya - R .. ya + R - 1; row ya + R enters below
+          const LnccRow r = lncc_row(&lncc_pk[((j + R) % NR) * WIN + c], R);
+          m += r.m; st += r.st; ss += r.ss; tt += r.tt; sss += r.sss; ts += r.ts;
+        }
+        const int yb = min(ya + SEG, ty);
+        for (int y = ya; y < yb; ++y) {
+          {
+            const LnccRow r = lncc_row(&lncc_pk[((y + 2 * R) % NR) * WIN + c], R);     // row y + R
+            m += r.m; st += r.st; ss += r.ss; tt += r.tt; sss += r.sss; ts += r.ts;
+          }
+          const unsigned own = lncc_pk[((y + R) % NR) * WIN + c + R];
+          int k = INT_MIN;
+          if ((own & 0x8000u) && (int)m >= need) {
+            const long long B = (long long)m * (long long)tt - (long long)st * (long long)st;
+            if (B > 0) {
+              const long long A = (long long)m * (long long)ts - (long long)st * (long long)ss;
+              const long long C = (long long)m * (long long)sss - (long long)ss * (long long)ss;
+              double q = 0;
+              if (C != 0) {
+                q = ((double)A / (double)B) * ((double)A / (double)C);
+                if (A < 0) q = -q;
+              }
+              k = (int)(long long)floor(q * 16777216.0 + 0.5);
+              acc_n += 1; acc_s += k;
+            }
+          }
+          if (km) km[(size_t)y * tx + x] = k;
+          {
+            const LnccRow r = lncc_row(&lncc_pk[(y % NR) * WIN + c], R);               // row y - R leaves
+            m -= r.m; st -= r.st; ss -= r.ss; tt -= r.tt; sss -= r.sss; ts -= r.ts;
+          }
+        }
+      }
+      __syncthreads();                                         // the next band overwrites rows this one has read
+    }
+  }
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  acc_n = wave_sum_i64(acc_n);
+  acc_s = wave_sum_i64(acc_s);
+  if (lane == 0) { red[w][0] = acc_n; red[w][1] = acc_s; }
+  __syncthreads();
+  if (threadIdx.x < 2) sums2[2 * (size_t)e + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+}  // namespace
+
+extern "C" {
+
+int svr_lncc_evaluate(svr_ctx *ctx, int n_eval, const int *target_index, const double *matrices, int radius, int64_t *sums2,
+                      int32_t *k_or_null) {
+  SVR_ENTER(ctx);
+  if (!ctx || n_eval <= 0 || !target_index || !matrices || !sums2) return SVR_E_ARG;
+  NEED(ctx->d_reg_targets && ctx->d_reg_source, "svr_ncc_set_targets / svr_ncc_set_source first");
+  if (radius < 1 || radius > LNCC_RMAX) return fail(ctx, SVR_E_ARG, "svr_lncc_evaluate: radius out of range (1..7)");
+  for (int i = 0; i < n_eval; ++i)
+    if (target_index[i] < 0 || target_index[i] >= ctx->reg_n) return fail(ctx, SVR_E_ARG, "target index out of range");
+  const int tx = ctx->reg_tx, ty = ctx->reg_ty;
+  const size_t npix = (size_t)tx * ty;
+  // grow-only scratch of the context: matrices | sums | target indices | the k maps (tests only)
+  const size_t b_mats = (size_t)n_eval * 16 * sizeof(double), b_sums = (size_t)n_eval * 2 * sizeof(long long), b_idx = (size_t)n_eval * sizeof(int),
+               o_map = (b_mats + b_sums + b_idx + 7) / 8 * 8, b_map = k_or_null ? (size_t)n_eval * npix * sizeof(int) : 0, need = o_map + b_map;
+  if (need > ctx->lncc_cap) {
+    free_dev(ctx->d_lncc_io);
+    ctx->lncc_cap = 0;
+    const size_t cap = need * 3 / 2 + 4096;
+    HIPCHK(hipMalloc(&ctx->d_lncc_io, cap));
+    ctx->lncc_cap = cap;
+  }
+  unsigned char *d = ctx->d_lncc_io;
+  double *d_m = reinterpret_cast<double *>(d);
+  long long *d_s = reinterpret_cast<long long *>(d + b_mats);
+  int *d_idx = reinterpret_cast<int *>(d + b_mats + b_sums);
+  int *d_map = k_or_null ? reinterpret_cast<int *>(d + o_map) : nullptr;
+  // columns a workgroup takes at once: the plane's width rounded up to a power of two, 32..256 (wider planes go in strips)
+  int cw_log2 = 5;
+  while (cw_log2 < 8 && (1 << cw_log2) < tx) ++cw_log2;
+  const size_t lds = (size_t)(LNCC_BH + 2 * radius) * ((1 << cw_log2) + 2 * radius) * sizeof(unsigned);
+  static_assert((LNCC_BH + 2 * LNCC_RMAX) * (256 + 2 * LNCC_RMAX) * sizeof(unsigned) + 64 <= 65536, "k_lncc: LDS beyond a static allocation");
+  std::vector<long long> h((size_t)n_eval * 2);
+  hipError_t e = hipMemcpyAsync(d_idx, target_index, b_idx, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_m, matrices, b_mats, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_lncc, dim3(n_eval), dim3(256), lds, ctx->stream, ctx->d_reg_targets, tx, ty, d_idx, d_m, ctx->d_reg_source,
+                       (int)ctx->reg_vx, (int)ctx->reg_vy, (int)ctx->reg_vz, radius, cw_log2, d_s, d_map);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_s, b_sums, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && k_or_null) e = hipMemcpyAsync(k_or_null, d_map, b_map, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return fail(ctx, (int)e, "svr_lncc_evaluate");
+  for (size_t i = 0; i < h.size(); ++i) sums2[i] = h[i];
+  return SVR_OK;
+}
+
+}  // extern "C"

@@ -43,7 +43,7 @@ EXPORTS = [
     "svr_superresolution_backproject", "svr_superresolution_update", "svr_robust_statistics_sums",
     "svr_mstep_sums", "svr_scale_volume_sums", "svr_scale_volume_apply", "svr_timer_get",
     "svr_unit_counts", "svr_fallbacks", "svr_clock_probe", "svr_slice_em_setup", "svr_slice_em_set_state", "svr_mstep_estep_device", "svr_slice_em_run", "svr_slice_em_apply_weights", "svr_slice_em_fetch", "svr_slice_em_set_patch_form", "svr_cell_stats", "svr_pair_pack", "svr_pair_unpack", "svr_timer_reset", "svr_timer_enable", "svr_timer_begin", "svr_timer_end", "svr_timer_add", "svr_counters", "svr_get_stream", "svr_device", "svr_device_count", "svr_combine_weights", "svr_update_stack_sizes", "svr_ncc_set_targets", "svr_ncc_set_source",
-    "svr_ncc_evaluate", "svr_ncc_get", "svr_ncc_alloc_targets","svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_slice_ssim", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
+    "svr_ncc_evaluate", "svr_ncc_get", "svr_ncc_alloc_targets","svr_pyr_upload", "svr_pyr_level", "svr_nmi_bin_source", "svr_nmi_evaluate", "svr_lncc_evaluate", "svr_stack_motion", "svr_slice_quality", "svr_slice_ssim", "svr_resample_to_reconstruction", "svr_correct_bias", "svr_normalise_bias", "svr_normalise_bias_local",
     "svr_normalise_bias_finish", "svr_init_reg_storage_volumes", "svr_fill_reg_slices",
     "svr_update_resampled_slices_i2w", "svr_prepare_slice_to_volume_reg", "svr_register_slices_to_volume",
     "svr_reg_set_schedule", "svr_reg_evaluate_costs", "svr_reg_counters", "svr_reg_get", "svr_pvr_cc_patches", "svr_pvr_register_patches",
@@ -457,6 +457,20 @@ class Reconstruction:
         self._ck(self._lib.svr_nmi_evaluate(self._h, len(ppe), _p(ppe), _p(idx), _p(m), _p(w), _p(nb), int(source_nbins), _p(out),
                                             _p(h) if h is not None else None))
         return out, h
+
+    def lncc_evaluate(self, target_index, matrices, radius=3, maps=False):
+        """svr_lncc_evaluate -> ({N, S} int64 [n_eval][2], the k maps int32 [n_eval][ty][tx] (INT32_MIN = not counted) or None): the
+        windowed cross correlation of one candidate matrix per target plane, (S / N) / 2^24."""
+        idx = np.ascontiguousarray(target_index, np.int32)
+        m = np.ascontiguousarray(matrices, np.float64).reshape(len(idx), 16)
+        out = np.zeros((len(idx), 2), np.int64)
+        k = None
+        if maps:
+            dims = (C.c_int * 3)()
+            self._ck(self._lib.svr_ncc_get(self._h, 1, dims, None, C.c_size_t(0)))
+            k = np.zeros((len(idx), dims[1], dims[0]), np.int32)
+        self._ck(self._lib.svr_lncc_evaluate(self._h, len(idx), _p(idx), _p(m), int(radius), _p(out), _p(k) if k is not None else None))
+        return out, k
 
     def stack_motion(self, slices):
         """svr_stack_motion on float32 slices [n][...] (already normalised; a slice is flattened to its pixels) ->

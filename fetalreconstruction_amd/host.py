@@ -493,7 +493,8 @@ class _NccBackend(C.Structure):
 class NccBackend:
     """struct svr_ncc_backend over a Python evaluator `fn(target int16 [ty][tx], M float64 [4][4], source int16 [z][y][x]) ->
     six integer moments`: how the CPU tests put the oracle's restatement of irtkImageRigidRegistrationWithPadding::Evaluate
-    behind the C++ schedule.  The product path passes no backend (the engine evaluates)."""
+    behind the C++ schedule.  The product path passes no backend (the engine evaluates).  For similarity="lncc" `fn` returns the
+    plane's {N, S} (svr_lncc_evaluate's, include/svr_hip.h) -- two integers; whatever follows them is ignored."""
 
     def __init__(self, fn):
         self.fn, self.targets, self.source, self.calls = fn, None, None, 0
@@ -512,7 +513,9 @@ class NccBackend:
                 m = np.ctypeslib.as_array(mats, shape=(n, 4, 4))
                 out = np.ctypeslib.as_array(sums, shape=(n, 6))
                 for e in range(n):
-                    out[e] = np.asarray(self.fn(self.targets[i[e]], m[e], self.source), np.int64)
+                    r = np.asarray(self.fn(self.targets[i[e]], m[e], self.source), np.int64).reshape(-1)[:6]
+                    out[e, :r.size] = r
+                    out[e, r.size:] = 0
                 self.calls += 1
                 return 0
             except Exception as ex:      # never let an exception cross the C boundary
@@ -573,7 +576,7 @@ class NmiBackend:
         self.struct = _NmiBackend(None, *self._cbs)
 
 
-SIMILARITY = {"cc": 0, "nmi": 1}          # SVRH_SIM_CC, SVRH_SIM_NMI (include/svr_host.h)
+SIMILARITY = {"cc": 0, "nmi": 1, "lncc": 2}          # SVRH_SIM_CC, SVRH_SIM_NMI, SVRH_SIM_LNCC (include/svr_host.h)
 
 
 def _reg_lib():
@@ -583,13 +586,20 @@ def _reg_lib():
     return lib
 
 
-def _backends(similarity, backend):
-    """(svr_ncc_backend*, svr_nmi_backend*, SVRH_SIM_*) for the _ex entry points"""
+def _backends(similarity, backend, radius=None):
+    """(svr_ncc_backend*, svr_nmi_backend*, SVRH_SIM_* with the LNCC radius above bit 8) for the _ex entry points"""
     sim = SIMILARITY.get(str(similarity).lower())
     if sim is None:
         raise ValueError(f"similarity must be one of {sorted(SIMILARITY)}, not {similarity!r}")
     if backend is not None and isinstance(backend, NmiBackend) != (sim == 1):
-        raise ValueError("similarity='nmi' takes an NmiBackend, 'cc' an NccBackend")
+        raise ValueError("similarity='nmi' takes an NmiBackend, 'cc' and 'lncc' an NccBackend")
+    if sim == 2:
+        r = 3 if radius is None else int(radius)
+        if r != radius and radius is not None or not 1 <= r <= 7:
+            raise ValueError(f"the radius of similarity='lncc' is an integer in 1..7, not {radius!r}")
+        sim |= r << 8
+    elif radius is not None:
+        raise ValueError("radius= belongs to similarity='lncc'")
     ptr = C.byref(backend.struct) if backend is not None else None
     return (None, ptr, sim) if sim == 1 else (ptr, None, sim)
 
@@ -616,13 +626,15 @@ def StackRegistrations(rec, stacks, attrs, transformations, template_number, mas
 
 
 def SliceToVolumeRegistration(rec, slices, slice_attrs, transformations, recon_attr, reconstructed, backend=None, no_resample=False,
-                              similarity="cc"):
+                              similarity="cc", radius=None):
     """irtkReconstruction::SliceToVolumeRegistration (RG.cc:1991-2059, 2291-2303), the reference's default registration
     -> (new transformations [n][4][4], number of evaluations).  slices: the padded float32 grid [n][sy][sx].
     no_resample: the patch-to-volume registration of the patch-based command line (patchBased2D3DRegistration.cpp:88-225).
-    similarity: "cc" (the reference's) or "nmi" (GuessParameterSliceToVolume(true); `backend` then an NmiBackend)."""
+    similarity: "cc" (the reference's), "nmi" (GuessParameterSliceToVolume(true); `backend` then an NmiBackend) or "lncc" (the
+    windowed cross correlation of csrc/svr_lncc.inc, window radius `radius` = 1..7, default 3; `backend` an NccBackend whose
+    evaluator returns {N, S})."""
     lib = _reg_lib()
-    ncc_be, nmi_be, sim = _backends(similarity, backend)
+    ncc_be, nmi_be, sim = _backends(similarity, backend, radius)
     g = np.ascontiguousarray(slices, np.float32)
     n, sy, sx = g.shape
     at = (ImageAttr * n)(*[ImageAttr.of(a) for a in slice_attrs])
@@ -639,11 +651,11 @@ def SliceToVolumeRegistration(rec, slices, slice_attrs, transformations, recon_a
 
 
 def PackageToVolume(rec, stacks, attrs, pack_num, transformations, recon_attr, reconstructed, evenodd=False, half=False, half_iter=1,
-                    backend=None, similarity="cc"):
+                    backend=None, similarity="cc", radius=None):
     """irtkReconstruction::PackageToVolume (RG.cc:5096-5192) -> (new per-slice transformations [n][4][4], evaluations).
-    similarity: "cc" or "nmi", as for SliceToVolumeRegistration."""
+    similarity: "cc", "nmi" or "lncc" (with `radius`), as for SliceToVolumeRegistration."""
     lib = _reg_lib()
-    ncc_be, nmi_be, sim = _backends(similarity, backend)
+    ncc_be, nmi_be, sim = _backends(similarity, backend, radius)
     n = len(stacks)
     data = [np.ascontiguousarray(s, np.float64) for s in stacks]
     ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in data])

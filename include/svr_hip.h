@@ -310,6 +310,16 @@ int svr_ncc_get(svr_ctx *ctx, int which, int dims[3], int16_t *out_or_null, size
 int svr_nmi_bin_source(svr_ctx *ctx, int width);
 int svr_nmi_evaluate(svr_ctx *ctx, int n_eval, const int *planes_per_eval, const int *target_index, const double *matrices,
                      const int *target_width, const int *target_nbins, int source_nbins, double *out4, uint32_t *hist_or_null);
+/* Local (windowed) normalised cross correlation of the same registration (csrc/svr_lncc.inc; --useLNCC, a deviation: the reference
+ * has no local metric).  Evaluation e is one candidate matrix on one target plane, sampled exactly as svr_ncc_evaluate samples it;
+ * V = the target pixels that contribute there.  With radius R (1..7) the window of a pixel is the (2R+1)^2 box around it, clipped to
+ * the plane and restricted to V; over it, in exact integers, m, St, Ss, Stt, Sss, Sts and A = m Sts - St Ss, B = m Stt - St^2,
+ * C = m Sss - Ss^2.  A pixel is counted iff it is in V, m >= ((2R+1)^2 + 1) / 2 and B > 0; it scores q = 0 if C == 0, else
+ * (A / B) * (A / C) in double, negated when A < 0, and k = floor(q 2^24 + 0.5).  sums2[e] = {N, S}: the counted pixels and the sum of
+ * their k; the similarity of an evaluation is (sum S / sum N) / 2^24 over its planes (0 when sum N = 0).  Integers throughout: the
+ * result does not depend on the schedule.  k_or_null: int32 [n_eval][ty][tx], INT32_MIN where a pixel is not counted. */
+int svr_lncc_evaluate(svr_ctx *ctx, int n_eval, const int *target_index, const double *matrices, int radius, int64_t *sums2,
+                      int32_t *k_or_null);
 /* The motion score of a stack (csrc/svr_motion.inc; the reference's --useAutoTemplate, stackMotionEstimator.cpp:67-164, there on
  * CULA's SVD).  slices: host memory, [n][m] -- n slices of m pixels, already normalised to [0, 1] with the stack's min / max.  The
  * singular values of the m x n matrix whose columns are the slices come from its n x n Gram matrix (accumulated in double on the

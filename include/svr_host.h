@@ -282,6 +282,15 @@ int svrh_package_to_volume(svr_ctx *ctx, const svr_ncc_backend *backend, int n_s
  * of irtkHistogram_2D (svrh_nmi_sums) -- the engine's sums equal them bit for bit. */
 #define SVRH_SIM_CC 0
 #define SVRH_SIM_NMI 1
+/* Local (windowed) cross correlation (csrc/svr_lncc.inc; --useLNCC, a deviation: the reference has no local metric): invariant to
+ * any intensity change that is linear inside a window, so a slice registers under a bias field the volume does not have.  The
+ * radius R of the (2R+1)^2 window travels in the same int: similarity = SVRH_SIM_LNCC | (R << 8), R = 1..7, 0 meaning 3.  The
+ * schedule, the optimiser, epsilon and the pyramids are those of CC and neither image is binned.  `backend` NULL = the engine
+ * (svr_lncc_evaluate, include/svr_hip.h, where the metric is defined); an external evaluator is a svr_ncc_backend whose `evaluate`
+ * fills sums6[0..1] = {N, S} of every plane -- the counted pixels and the sum of their k = floor(q 2^24 + 0.5) -- and whose other
+ * four entries are ignored.  Requests are per plane, as for CC; the schedule adds the planes of an evaluation and takes
+ * (sum S / sum N) / 2^24, 0 when sum N = 0.  `nmi_backend` is not used. */
+#define SVRH_SIM_LNCC 2
 typedef struct svr_nmi_backend {
   void *user;
   int (*set_targets)(void *user, int n, int tx, int ty, const int16_t *targets);
