@@ -373,7 +373,7 @@ void matrix_to_params(const M4 &m, double p[6]) {
   p[3] *= 180.0 / M_PI; p[4] *= 180.0 / M_PI; p[5] *= 180.0 / M_PI;
 }
 
-struct Backend {                                           // the engine, or whatever the caller supplies
+struct Backend {                                           // where the images go: the engine, or whatever the caller supplies
   svr_ctx *ctx;
   const svr_ncc_backend *be;
   const svr_nmi_backend *nbe = nullptr;                    // NMI: the caller's joint histograms instead of the engine's sums
@@ -383,23 +383,6 @@ struct Backend {                                           // the engine, or wha
   }
   int set_source(const uint32_t size[3], const int16_t *s) const {
     return nbe ? nbe->set_source(nbe->user, size, s) : be ? be->set_source(be->user, size, s) : svr_ncc_set_source(ctx, size, s);
-  }
-  int evaluate(int n, const int *idx, const double *m, int64_t *sums) const {
-    return be ? be->evaluate(be->user, n, idx, m, sums, nullptr) : svr_ncc_evaluate(ctx, n, idx, m, sums, nullptr);
-  }
-  // {N, S} per plane at sums[stride * plane]: the engine's (stride 2), or the first two entries of the caller's six
-  int lncc_stride() const { return be ? 6 : 2; }
-  int evaluate_lncc(int n, const int *idx, const double *m, int radius, int64_t *sums) const {
-    return be ? be->evaluate(be->user, n, idx, m, sums, nullptr) : svr_lncc_evaluate(ctx, n, idx, m, radius, sums, nullptr);
-  }
-  // {n, S_xy, S_x, S_y} per evaluation: the engine's, or nmi_sums of the caller's histograms
-  int evaluate_nmi(int n, const int *ppe, const int *idx, const double *m, const int *width, const int *nbins, int source_nbins, double *out4,
-                   std::vector<uint32_t> &hist) const {
-    if (!nbe) return svr_nmi_evaluate(ctx, n, ppe, idx, m, width, nbins, source_nbins, out4, nullptr);
-    hist.assign((size_t)n * 4096, 0);
-    if (int rc = nbe->evaluate(nbe->user, n, ppe, idx, m, width, nbins, source_nbins, hist.data())) return rc;
-    for (int e = 0; e < n; ++e) nmi_sums(&hist[(size_t)e * 4096], nbins[e], source_nbins, out4 + 4 * (size_t)e);
-    return 0;
   }
 };
 
@@ -426,6 +409,69 @@ double ncc_from_sums(const int64_t s[6]) {                 // irtkCrossCorrelati
   if (n > 0) return (xy - (x * y) / n) / (sqrt(x2 - x * x / n) * sqrt(y2 - y * y / n));
   return 0;
 }
+
+// The similarity of a pass: everything between the optimiser's requests and the values it gets back that depends on which of
+// the three metrics runs, and on whether the engine or a caller's backend evaluates it.  The schedule and the optimiser see
+// requests and value(): CC is the six moments added over the planes of a request; NMI (the levels binned, irtkCalculateNumber-
+// OfBins) one {n, S_xy, S_x, S_y} per request, the engine's or nmi_sums of the caller's histograms; LNCC (neither image binned)
+// the integers {N, S} per plane -- the engine's pairs, or the first two of a caller's six -- added over the planes.
+struct Metric {
+  const Backend &be;
+  int kind, radius;                                        // SVRH_SIM_*; the LNCC window
+  int src_nbins = 1;                                       // NMI: bins of this level's source
+  std::vector<int> req_planes, req_width, req_nbins;       // NMI: what a request records
+  std::vector<double> out4;
+  std::vector<int64_t> sums;
+  std::vector<uint32_t> hist;
+  bool nmi() const { return kind == SVRH_SIM_NMI; }
+  bool lncc() const { return kind == SVRH_SIM_LNCC; }
+  const char *name() const { return nmi() ? "NMI" : lncc() ? "LNCC" : "CC"; }
+  int stride() const { return lncc() && !be.be ? 2 : 6; }  // entries per plane in `sums`
+  // the level's source: binned before it is interpolated (IRWP.cc:243-244), [mn, mx] its range before the shift
+  int prepare_source(Vol<short> &src, int mn, int mx, bool dev, std::string &err) {
+    if (!nmi()) return 0;
+    int width = 1;
+    src_nbins = nmi_number_of_bins(mn, mx, width);
+    if (!dev) nmi_bin(src.d.data(), src.d.size(), width);
+    else if (svr_nmi_bin_source(be.ctx, width)) { err = std::string("svr_nmi_bin_source: ") + svr_last_error(be.ctx); return 2; }
+    return 0;
+  }
+  void prepare_target(Target &t, int mn, int mx) const { t.nbins = nmi_number_of_bins(mn, mx, t.bin_width); }   // binned on the fly
+  void size_round(int n_req, int n_planes) {
+    if (nmi()) { req_planes.resize(n_req); req_width.resize(n_req); req_nbins.resize(n_req); out4.resize(4 * (size_t)n_req); }
+    else sums.resize(stride() * (size_t)n_planes);
+  }
+  void record(int rq, const Target &t) {
+    if (nmi()) { req_planes[rq] = t.lvl.a.nz; req_width[rq] = t.bin_width; req_nbins[rq] = t.nbins; }
+  }
+  int call(int n_req, int n_planes, const int *idx, const double *m) {
+    if (nmi()) {
+      const int *ppe = req_planes.data(), *width = req_width.data(), *nbins = req_nbins.data();
+      if (!be.nbe) return svr_nmi_evaluate(be.ctx, n_req, ppe, idx, m, width, nbins, src_nbins, out4.data(), nullptr);
+      hist.assign((size_t)n_req * 4096, 0);
+      if (int rc = be.nbe->evaluate(be.nbe->user, n_req, ppe, idx, m, width, nbins, src_nbins, hist.data())) return rc;
+      for (int e = 0; e < n_req; ++e) nmi_sums(&hist[(size_t)e * 4096], nbins[e], src_nbins, &out4[4 * (size_t)e]);
+      return 0;
+    }
+    if (be.be) return be.be->evaluate(be.be->user, n_planes, idx, m, sums.data(), nullptr);
+    return lncc() ? svr_lncc_evaluate(be.ctx, n_planes, idx, m, radius, sums.data(), nullptr) : svr_ncc_evaluate(be.ctx, n_planes, idx, m, sums.data(), nullptr);
+  }
+  int evaluate(int n_req, int n_planes, const int *idx, const double *m, std::string &err) {
+    if (!call(n_req, n_planes, idx, m)) return 0;
+    const std::string fn = nmi() ? "svr_nmi_evaluate" : lncc() ? "svr_lncc_evaluate" : "svr_ncc_evaluate";
+    err = (kind == SVRH_SIM_CC || be.external()) ? fn + " failed" : fn + ": " + svr_last_error(be.ctx);
+    return 2;
+  }
+  // request rq, whose nz planes start at plane `at` of the round
+  double value(size_t rq, size_t at, int nz) const {
+    if (nmi()) return nmi_from_sums(&out4[4 * rq]);
+    int64_t s[6] = {0, 0, 0, 0, 0, 0};
+    const int st = stride(), n = lncc() ? 2 : 6;
+    for (int c = 0; c < nz; ++c) for (int k = 0; k < n; ++k) s[k] += sums[st * (at + c) + k];
+    if (lncc()) return s[0] > 0 ? ((double)s[1] / (double)s[0]) / 16777216.0 : 0.0;   // (sum S / sum N) / 2^24
+    return ncc_from_sums(s);
+  }
+};
 
 // One level of prepare_level on the device (csrc/svr_pyr.inc) for `n` images of one grid whose unprocessed voxels sit at
 // `offset` of the upload slot: the attributes of the level come back in out[i], the voxels stay on the device as the NCC
@@ -481,276 +527,305 @@ bool parse_similarity(int similarity, int &sim, int &radius) {
   return radius >= 1 && radius <= 7;
 }
 
-// irtkImageRegistration::Run for every target against one source, in lock step; sim: the similarity is NMI instead of CC
-// (GuessParameterSliceToVolume(useNMI), IRRWP.cc:319-321: the schedule, the optimiser and epsilon are the same), or the
-// windowed cross correlation of radius lncc_radius (neither image binned)
-int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol<short> &source, int slice_to_volume, short target_padding,
-                      int sim, int lncc_radius, long *n_eval, std::string &err) {
-  if (targets.empty()) return 0;
-  const int nmi = sim == SVRH_SIM_NMI, lncc = sim == SVRH_SIM_LNCC;
-  const short source_padding = guess_padding(source);
-  const bool timing = getenv("SVR_REG_TIMING") != nullptr;        // dev: where a registration pass spends its wall time
-  double t_src = 0, t_tgt = 0, t_pack = 0, t_opt = 0, t_eval = 0;
-  long rounds = 0;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+// ---- a pass = irtkImageRegistration::Run for every target against one source, in lock step, stage by stage ------------------------
+struct Pass {                                              // what the stages share
+  const Backend &be;
+  std::vector<Target> &targets;
+  const Vol<short> &source;
+  int slice_to_volume;
+  short target_padding, source_padding;
   // The engine makes the pyramids itself (csrc/svr_pyr.inc: the same arithmetic, no host pass over the voxels, no upload
-  // per level); another backend (the oracle evaluator of the tests), or SVR_HOST_PYRAMID=1, takes the host code below.
-  const bool dev = !be.external() && be.ctx && !getenv("SVR_HOST_PYRAMID");
-  std::map<GridKey, GridGroup> groups;                    // targets of one grid go through the kernels together
-  if (dev) {
-    if (svr_pyr_upload(be.ctx, 0, source.d.data(), source.n())) { err = std::string("svr_pyr_upload: ") + svr_last_error(be.ctx); return 2; }
-    size_t total = 0;
-    for (size_t r = 0; r < targets.size(); ++r) {
-      const svr_image_attr &a = targets[r].full->a;
-      groups[GridKey{a.nx, a.ny, a.nz, a.dx, a.dy, a.dz}].members.push_back((int)r);
-      total += targets[r].full->n();
-    }
-    std::vector<int16_t> all(total);
-    size_t at = 0;
-    for (auto &g : groups) {
-      g.second.offset = at;
-      for (int r : g.second.members) { memcpy(&all[at], targets[r].full->d.data(), sizeof(int16_t) * targets[r].full->n()); at += targets[r].full->n(); }
-    }
-    if (svr_pyr_upload(be.ctx, 1, all.data(), total)) { err = std::string("svr_pyr_upload: ") + svr_last_error(be.ctx); return 2; }
+  // per level); another backend (the oracle evaluator of the tests), or SVR_HOST_PYRAMID=1, takes the host code.
+  bool dev;
+  std::map<GridKey, GridGroup> groups;                     // dev: targets of one grid go through the kernels together
+  Schedule schedule(const Target &t) const { return guess_parameters(t.full->a, source.a, slice_to_volume); }
+  short padding_of(const Target &t) const { return t.own_padding ? t.padding : target_padding; }
+};
+struct Level {
+  int level;
+  Schedule ps;                                             // of the first target: the optimiser's iterations, steps and epsilon
+  Vol<short> src;                                          // the source of the level (dev: its attributes only)
+  int tx = 0, ty = 0, planes = 0;                          // the backend's target planes
+};
+struct Round {                                             // one batched evaluation: the requests of every target still running
+  std::vector<int> live, req_off, plane_off, idx;
+  std::vector<double> mats, value;
+  int n_req = 0, n_planes = 0;
+};
+struct Times { double src = 0, tgt = 0, pack = 0, opt = 0, eval = 0; long rounds = 0; };   // SVR_REG_TIMING
+double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// a target enters a level: its optimiser starts over, its planes follow those of the targets before it
+void enter_level(Target &t, const Schedule &p, Level &lv) {
+  t.phase = PH_START; t.step_i = 0; t.iter_j = 0; t.done = false;
+  t.step = p.length[lv.level]; t.delta = p.delta[lv.level];
+}
+void place_planes(Target &t, Level &lv) {
+  lv.tx = std::max(lv.tx, t.lvl.a.nx); lv.ty = std::max(lv.ty, t.lvl.a.ny);
+  t.first_plane = lv.planes;
+  lv.planes += t.lvl.a.nz;
+}
+
+// dev: the unprocessed source (slot 0) and targets (slot 1, grid by grid) go up once per pass
+int upload_pyramid_inputs(Pass &ps, std::string &err) {
+  if (svr_pyr_upload(ps.be.ctx, 0, ps.source.d.data(), ps.source.n())) { err = std::string("svr_pyr_upload: ") + svr_last_error(ps.be.ctx); return 2; }
+  size_t total = 0;
+  for (size_t r = 0; r < ps.targets.size(); ++r) {
+    const svr_image_attr &a = ps.targets[r].full->a;
+    ps.groups[GridKey{a.nx, a.ny, a.nz, a.dx, a.dy, a.dz}].members.push_back((int)r);
+    total += ps.targets[r].full->n();
   }
-  for (int level = 2; level >= 0; --level) {
-    double t0 = now();
-    // ---- Initialize(level): every target and the source -------------------------------------------------------------
-    Vol<short> src;
-    const Schedule ps = guess_parameters(targets[0].full->a, source.a, slice_to_volume);
-    int smn = 0, smx = -1, src_width = 1, src_nbins = 1;
-    if (dev) {
-      const svr_image_attr *in = &source.a;
-      if (int rc = device_level(be.ctx, 0, 0, 1, &in, &source_padding, ps.s_blur[level], ps.s_res[level], ps.s_res[0], level, 0, &src.a, err, &smn,
-                                &smx))
-        return rc;
-    } else if (prepare_level(source, ps.s_blur[level], ps.s_res[level], ps.s_res[0], level, source_padding, src, err, &smn, &smx)) return 1;
-    if (nmi) {                                                 // the source is binned before it is interpolated (IRWP.cc:243-244)
-      src_nbins = nmi_number_of_bins(smn, smx, src_width);
-      if (!dev) nmi_bin(src.d.data(), src.d.size(), src_width);
-      else if (svr_nmi_bin_source(be.ctx, src_width)) { err = std::string("svr_nmi_bin_source: ") + svr_last_error(be.ctx); return 2; }
-    }
-    t_src += now() - t0; t0 = now();
-    int tx = 0, ty = 0, planes = 0;
-    std::vector<int> bad(targets.size(), 0);
-    std::vector<std::string> errs(targets.size());
-    size_t pixels = 0;
-    for (const Target &t : targets) pixels += t.full->n();
-    if (dev) {
-      // the grids of the level first (the planes must be allocated before the kernels write them), group by group
-      for (auto &g : groups)
-        for (int r : g.second.members) {
-          Target &t = targets[r];
-          const Schedule p = guess_parameters(t.full->a, source.a, slice_to_volume);
-          const double temp = fabs(p.t_res[0][0] - t.full->a.dx) + fabs(p.t_res[0][1] - t.full->a.dy) + fabs(p.t_res[0][2] - t.full->a.dz);
-          t.lvl.a = (level > 0 || temp > 0.000001) ? resampled_attr(t.full->a, p.t_res[level][0], p.t_res[level][1], p.t_res[level][2]) : t.full->a;
-          t.lvl.d.clear();
-          t.phase = PH_START; t.step_i = 0; t.iter_j = 0; t.done = false;
-          t.step = p.length[level]; t.delta = p.delta[level];
-          tx = std::max(tx, t.lvl.a.nx); ty = std::max(ty, t.lvl.a.ny);
-          t.first_plane = planes;
-          planes += t.lvl.a.nz;
-        }
-      if (svr_ncc_alloc_targets(be.ctx, planes, tx, ty)) { err = std::string("svr_ncc_alloc_targets: ") + svr_last_error(be.ctx); return 2; }
-      for (auto &g : groups) {
-        const std::vector<int> &mem = g.second.members;
-        const Schedule p = guess_parameters(targets[mem[0]].full->a, source.a, slice_to_volume);
-        const size_t nvox = targets[mem[0]].full->n();
-        for (size_t c0 = 0; c0 < mem.size(); c0 += 32768) {                        // the grid's y dimension holds 65535 images
-          const int n = (int)std::min<size_t>(32768, mem.size() - c0);
-          std::vector<const svr_image_attr *> in(n);
-          std::vector<short> pads(n);
-          std::vector<svr_image_attr> outa(n);
-          for (int i = 0; i < n; ++i) {
-            const Target &t = targets[mem[c0 + i]];
-            in[i] = &t.full->a;
-            pads[i] = t.own_padding ? t.padding : target_padding;
-          }
-          std::vector<int> tmn(n), tmx(n);
-          if (int rc = device_level(be.ctx, 1, g.second.offset + c0 * nvox, n, in.data(), pads.data(), p.t_blur[level], p.t_res[level], p.t_res[0], level,
-                                    targets[mem[c0]].first_plane, outa.data(), err, tmn.data(), tmx.data()))
-            return rc;
-          for (int i = 0; i < n; ++i) {                                              // the targets are binned on the fly
-            Target &t = targets[mem[c0 + i]];
-            t.nbins = nmi_number_of_bins(tmn[i], tmx[i], t.bin_width);
-          }
-        }
-      }
-    } else
-    parallel_rows((int)targets.size(), pixels / targets.size() * 60, [&](int r0, int r1) {
-      for (int r = r0; r < r1; ++r) {
-        Target &t = targets[r];
-        const Schedule p = guess_parameters(t.full->a, source.a, slice_to_volume);
-        int mn = 0, mx = -1;
-        bad[r] = prepare_level(*t.full, p.t_blur[level], p.t_res[level], p.t_res[0], level, t.own_padding ? t.padding : target_padding, t.lvl,
-                               errs[r], &mn, &mx);
-        t.nbins = nmi_number_of_bins(mn, mx, t.bin_width);
-        t.phase = PH_START; t.step_i = 0; t.iter_j = 0; t.done = false;
-        t.step = p.length[level]; t.delta = p.delta[level];
-      }
-    });
-    t_tgt += now() - t0; t0 = now();
-    if (!dev) {
-      for (size_t r = 0; r < targets.size(); ++r) {
-        if (bad[r]) { err = errs[r]; return 1; }
-        Target &t = targets[r];
-        tx = std::max(tx, t.lvl.a.nx); ty = std::max(ty, t.lvl.a.ny);
-        t.first_plane = planes;
-        planes += t.lvl.a.nz;
-      }
-      std::vector<int16_t> packed((size_t)planes * tx * ty, (int16_t)-1);
-      for (const Target &t : targets)
-        for (int k = 0; k < t.lvl.a.nz; ++k)
-          for (int y = 0; y < t.lvl.a.ny; ++y)
-            memcpy(&packed[((size_t)(t.first_plane + k) * ty + y) * tx], &t.lvl.d[((size_t)k * t.lvl.a.ny + y) * t.lvl.a.nx],
-                   sizeof(int16_t) * t.lvl.a.nx);
-      if (be.set_targets(planes, tx, ty, packed.data())) { err = "svr_ncc_set_targets failed"; return 2; }
-      const uint32_t ssz[3] = {(uint32_t)src.a.nx, (uint32_t)src.a.ny, (uint32_t)src.a.nz};
-      if (be.set_source(ssz, src.d.data())) { err = "svr_ncc_set_source failed"; return 2; }
-    }
-    const M4 s_w2i = world_to_image(src.a);
-    const Schedule p0 = ps;
-    t_pack += now() - t0; t0 = now();
-    // ---- the optimiser, one round = one batched evaluation --------------------------------------------------------------
-    // A round costs the host a few double trigonometric calls per target; with tens of thousands of targets (the patches
-    // of the patch-based path) that was 1.6 s of a 2.8 s pass, so the requests are laid out by a prefix sum and written,
-    // and the answers consumed, by the host threads -- every target touches only its own state and its own slots.
-    std::vector<int> live, req_off, plane_off, idx, req_planes, req_width, req_nbins;
-    std::vector<double> mats, value, out4;
-    std::vector<int64_t> sums;
-    std::vector<uint32_t> hist;
-    auto over_live = [&](size_t work, const std::function<void(int, int)> &fn) {
-      if (live.size() >= 2048) parallel_rows((int)live.size(), work, fn);
-      else fn(0, (int)live.size());
-    };
-    for (;;) {
-      live.clear(); req_off.clear(); plane_off.clear();
-      int n_req = 0, n_planes = 0;
-      for (size_t ti = 0; ti < targets.size(); ++ti) {
-        const Target &t = targets[ti];
-        if (t.done) continue;
-        const int nr = t.phase == PH_GRAD ? 12 : 1;         // START: old_similarity = Evaluate(), GDO.cc:31; GRAD: IR.cc:530-568; LINE: one probe
-        live.push_back((int)ti); req_off.push_back(n_req); plane_off.push_back(n_planes);
-        n_req += nr; n_planes += nr * t.lvl.a.nz;
-      }
-      if (live.empty()) break;
-      idx.resize(n_planes); mats.resize(16 * (size_t)n_planes); value.resize(n_req);
-      if (nmi) { req_planes.resize(n_req); req_width.resize(n_req); req_nbins.resize(n_req); out4.resize(4 * (size_t)n_req); }
-      else sums.resize((lncc ? be.lncc_stride() : 6) * (size_t)n_planes);
-      over_live(3000, [&](int l0, int l1) {
-        for (int l = l0; l < l1; ++l) {
-          const Target &t = targets[live[l]];
-          int at = plane_off[l], rq = req_off[l];
-          auto request = [&](const M4 &tm) {                 // the per-plane matrices of one evaluation (push_request)
-            if (nmi) { req_planes[rq] = t.lvl.a.nz; req_width[rq] = t.bin_width; req_nbins[rq] = t.nbins; }
-            ++rq;
-            const M4 m = mul(mul(s_w2i, tm), image_to_world(t.lvl.a));
-            double zx = m.m[3], zy = m.m[7], zz = m.m[11];
-            for (int k = 0; k < t.lvl.a.nz; ++k, ++at) {
-              idx[at] = t.first_plane + k;
-              M4 q = m;
-              q.m[3] = zx; q.m[7] = zy; q.m[11] = zz;
-              memcpy(&mats[16 * (size_t)at], q.m, sizeof(q.m));
-              zx += m.m[2]; zy += m.m[6]; zz += m.m[10];     // NextZ()
-            }
-          };
-          if (t.phase == PH_GRAD) {
-            for (int i = 0; i < 6; ++i) {
-              double q[6];
-              for (int k = 0; k < 6; ++k) q[k] = t.p[k];
-              q[i] = t.p[i] + t.step; request(params_to_matrix(q));
-              q[i] = t.p[i] - t.step; request(params_to_matrix(q));
-            }
-          } else {
-            request(t.matrix);
-          }
-        }
-      });
-      const double te = now();
-      if (nmi) {
-        if (be.evaluate_nmi(n_req, req_planes.data(), idx.data(), mats.data(), req_width.data(), req_nbins.data(), src_nbins, out4.data(), hist)) {
-          err = be.external() ? "svr_nmi_evaluate failed" : std::string("svr_nmi_evaluate: ") + svr_last_error(be.ctx);
-          return 2;
-        }
-      } else if (lncc) {
-        if (be.evaluate_lncc(n_planes, idx.data(), mats.data(), lncc_radius, sums.data())) {
-          err = be.external() ? "svr_lncc_evaluate failed" : std::string("svr_lncc_evaluate: ") + svr_last_error(be.ctx);
-          return 2;
-        }
-      } else if (be.evaluate(n_planes, idx.data(), mats.data(), sums.data())) { err = "svr_ncc_evaluate failed"; return 2; }
-      t_eval += now() - te; ++rounds;
-      if (n_eval) *n_eval += (long)n_req;
-      over_live(600, [&](int l0, int l1) {
-        for (int l = l0; l < l1; ++l) {
-          Target &t = targets[live[l]];
-          const int nz = t.lvl.a.nz, nr = t.phase == PH_GRAD ? 12 : 1;
-          for (int q = 0; q < nr; ++q) {
-            if (nmi) { value[req_off[l] + q] = nmi_from_sums(&out4[4 * ((size_t)req_off[l] + q)]); continue; }
-            int64_t sacc[6] = {0, 0, 0, 0, 0, 0};
-            const size_t at = (size_t)plane_off[l] + (size_t)q * nz;
-            if (lncc) {                                        // (sum S / sum N) / 2^24 over the planes of the evaluation
-              const int st = be.lncc_stride();
-              for (int c = 0; c < nz; ++c) { sacc[0] += sums[st * (at + c)]; sacc[1] += sums[st * (at + c) + 1]; }
-              value[req_off[l] + q] = sacc[0] > 0 ? ((double)sacc[1] / (double)sacc[0]) / 16777216.0 : 0.0;
-              continue;
-            }
-            for (int c = 0; c < nz; ++c) for (int k = 0; k < 6; ++k) sacc[k] += sums[6 * (at + c) + k];
-            value[req_off[l] + q] = ncc_from_sums(sacc);
-          }
-          size_t r = req_off[l];
-          auto take_step = [&](double sign) {                // Put(i, Get(i) +- StepSize * dx[i]) for every i
-            for (int i = 0; i < 6; ++i) t.p[i] = t.p[i] + sign * (t.step * t.dx[i]);
-            t.matrix = params_to_matrix(t.p);
-          };
-          if (t.phase == PH_START) {
-            t.old_sim = t.new_sim = t.sim = value[r++];
-            for (int i = 0; i < 6; ++i) t.start[i] = t.p[i];   // irtkOptimizer::Run stores the parameters, O.cc:113-116
-            t.phase = PH_GRAD;
-          } else if (t.phase == PH_GRAD) {
-            double norm = 0;
-            for (int i = 0; i < 6; ++i) { const double s1 = value[r++], s2 = value[r++]; t.dx[i] = (float)(s1 - s2); }
-            t.matrix = params_to_matrix(t.p);                  // Put(i, parameterValue) rebuilt the matrix from the parameters
-            for (int i = 0; i < 6; ++i) norm += t.dx[i] * t.dx[i];
-            norm = sqrt(norm);
-            for (int i = 0; i < 6; ++i) t.dx[i] = norm > 0 ? (float)(t.dx[i] / norm) : 0.0f;
-            t.new_sim = t.sim;                                 // first pass of the do-while, GDO.cc:47-54
-            take_step(+1);
-            t.phase = PH_LINE;
-          } else {
-            t.sim = value[r++];
-            if (t.sim > t.new_sim + p0.epsilon) {              // keep stepping
-              t.new_sim = t.sim;
-              take_step(+1);
-            } else {
-              take_step(-1);                                   // last step was no improvement: back track, GDO.cc:58-61
-              const double eps = t.new_sim > t.old_sim ? t.new_sim - t.old_sim : 0;
-              double max_change = 0;
-              for (int i = 0; i < 6; ++i) max_change = std::max(max_change, fabs(t.p[i] - t.start[i]));
-              bool next_step = true;                           // IR.cc:482-506
-              if (eps > p0.epsilon && max_change > t.delta) {
-                if (++t.iter_j < p0.iterations[level]) next_step = false;
-              }
-              if (next_step) {
-                t.iter_j = 0;
-                t.step = t.step / 2;
-                t.delta = t.delta / 2.0;
-                if (++t.step_i >= p0.steps[level]) t.done = true;
-              }
-              t.phase = PH_START;
-            }
-          }
-        }
-      });
-    }
-    t_opt += now() - t0;
+  std::vector<int16_t> all(total);
+  size_t at = 0;
+  for (auto &g : ps.groups) {
+    g.second.offset = at;
+    for (int r : g.second.members) { memcpy(&all[at], ps.targets[r].full->d.data(), sizeof(int16_t) * ps.targets[r].full->n()); at += ps.targets[r].full->n(); }
   }
-  if (timing)
-    fprintf(stderr, "[svr reg timing] %s: source pyramid %.1f ms, target pyramids %.1f ms, pack + upload %.1f ms, optimiser %.1f ms (%ld rounds, %.1f ms in the batched evaluations)\n",
-            nmi ? "NMI" : lncc ? "LNCC" : "CC", 1e3 * t_src, 1e3 * t_tgt, 1e3 * t_pack, 1e3 * t_opt, rounds, 1e3 * t_eval);
+  if (svr_pyr_upload(ps.be.ctx, 1, all.data(), total)) { err = std::string("svr_pyr_upload: ") + svr_last_error(ps.be.ctx); return 2; }
   return 0;
 }
 
-Vol<short> to_grey(const svr_image_attr &a, const double *d) {           // irtkGreyImage = irtkRealImage: static_cast per voxel
+// Initialize(level) of the source, on the device or on the host
+int level_source(Pass &ps, Metric &metric, Level &lv, std::string &err) {
+  const int level = lv.level;
+  int smn = 0, smx = -1;
+  if (ps.dev) {
+    const svr_image_attr *in = &ps.source.a;
+    if (int rc = device_level(ps.be.ctx, 0, 0, 1, &in, &ps.source_padding, lv.ps.s_blur[level], lv.ps.s_res[level], lv.ps.s_res[0], level, 0, &lv.src.a,
+                              err, &smn, &smx))
+      return rc;
+  } else if (prepare_level(ps.source, lv.ps.s_blur[level], lv.ps.s_res[level], lv.ps.s_res[0], level, ps.source_padding, lv.src, err, &smn, &smx)) return 1;
+  return metric.prepare_source(lv.src, smn, smx, ps.dev, err);
+}
+
+// Initialize(level) of every target on the device: the grids of the level first (the planes must be allocated before the kernels
+// write them), then the kernels group by group
+int level_targets_device(Pass &ps, const Metric &metric, Level &lv, std::string &err) {
+  const int level = lv.level;
+  for (auto &g : ps.groups)
+    for (int r : g.second.members) {
+      Target &t = ps.targets[r];
+      const Schedule p = ps.schedule(t);
+      const double temp = fabs(p.t_res[0][0] - t.full->a.dx) + fabs(p.t_res[0][1] - t.full->a.dy) + fabs(p.t_res[0][2] - t.full->a.dz);
+      t.lvl.a = (level > 0 || temp > 0.000001) ? resampled_attr(t.full->a, p.t_res[level][0], p.t_res[level][1], p.t_res[level][2]) : t.full->a;
+      t.lvl.d.clear();
+      enter_level(t, p, lv);
+      place_planes(t, lv);
+    }
+  if (svr_ncc_alloc_targets(ps.be.ctx, lv.planes, lv.tx, lv.ty)) { err = std::string("svr_ncc_alloc_targets: ") + svr_last_error(ps.be.ctx); return 2; }
+  for (auto &g : ps.groups) {
+    const std::vector<int> &mem = g.second.members;
+    const Schedule p = ps.schedule(ps.targets[mem[0]]);
+    const size_t nvox = ps.targets[mem[0]].full->n();
+    for (size_t c0 = 0; c0 < mem.size(); c0 += 32768) {                        // the grid's y dimension holds 65535 images
+      const int n = (int)std::min<size_t>(32768, mem.size() - c0);
+      std::vector<const svr_image_attr *> in(n);
+      std::vector<short> pads(n);
+      std::vector<svr_image_attr> outa(n);
+      for (int i = 0; i < n; ++i) {
+        const Target &t = ps.targets[mem[c0 + i]];
+        in[i] = &t.full->a;
+        pads[i] = ps.padding_of(t);
+      }
+      std::vector<int> tmn(n), tmx(n);
+      if (int rc = device_level(ps.be.ctx, 1, g.second.offset + c0 * nvox, n, in.data(), pads.data(), p.t_blur[level], p.t_res[level], p.t_res[0], level,
+                                ps.targets[mem[c0]].first_plane, outa.data(), err, tmn.data(), tmx.data()))
+        return rc;
+      for (int i = 0; i < n; ++i) metric.prepare_target(ps.targets[mem[c0 + i]], tmn[i], tmx[i]);
+    }
+  }
+  return 0;
+}
+
+// ... and on the host, by the host threads
+int level_targets_host(Pass &ps, const Metric &metric, Level &lv, std::string &err) {
+  std::vector<Target> &targets = ps.targets;
+  std::vector<int> bad(targets.size(), 0);
+  std::vector<std::string> errs(targets.size());
+  size_t pixels = 0;
+  for (const Target &t : targets) pixels += t.full->n();
+  parallel_rows((int)targets.size(), pixels / targets.size() * 60, [&](int r0, int r1) {
+    for (int r = r0; r < r1; ++r) {
+      Target &t = targets[r];
+      const Schedule p = ps.schedule(t);
+      int mn = 0, mx = -1;
+      bad[r] = prepare_level(*t.full, p.t_blur[lv.level], p.t_res[lv.level], p.t_res[0], lv.level, ps.padding_of(t), t.lvl, errs[r], &mn, &mx);
+      metric.prepare_target(t, mn, mx);
+      enter_level(t, p, lv);
+    }
+  });
+  for (size_t r = 0; r < targets.size(); ++r)
+    if (bad[r]) { err = errs[r]; return 1; }
+  return 0;
+}
+
+// host: the level's planes packed into one array and handed, with the source, to the backend
+int pack_level_host(Pass &ps, Level &lv, std::string &err) {
+  for (Target &t : ps.targets) place_planes(t, lv);
+  const int tx = lv.tx, ty = lv.ty;
+  std::vector<int16_t> packed((size_t)lv.planes * tx * ty, (int16_t)-1);
+  for (const Target &t : ps.targets)
+    for (int k = 0; k < t.lvl.a.nz; ++k)
+      for (int y = 0; y < t.lvl.a.ny; ++y)
+        memcpy(&packed[((size_t)(t.first_plane + k) * ty + y) * tx], &t.lvl.d[((size_t)k * t.lvl.a.ny + y) * t.lvl.a.nx], sizeof(int16_t) * t.lvl.a.nx);
+  if (ps.be.set_targets(lv.planes, tx, ty, packed.data())) { err = "svr_ncc_set_targets failed"; return 2; }
+  const uint32_t ssz[3] = {(uint32_t)lv.src.a.nx, (uint32_t)lv.src.a.ny, (uint32_t)lv.src.a.nz};
+  if (ps.be.set_source(ssz, lv.src.d.data())) { err = "svr_ncc_set_source failed"; return 2; }
+  return 0;
+}
+
+// the requests of a round by a prefix sum over the targets still running; false = none is
+bool lay_out_round(const std::vector<Target> &targets, Round &rd) {
+  rd.live.clear(); rd.req_off.clear(); rd.plane_off.clear();
+  rd.n_req = rd.n_planes = 0;
+  for (size_t ti = 0; ti < targets.size(); ++ti) {
+    const Target &t = targets[ti];
+    if (t.done) continue;
+    const int nr = t.phase == PH_GRAD ? 12 : 1;             // START: old_similarity = Evaluate(), GDO.cc:31; GRAD: IR.cc:530-568; LINE: one probe
+    rd.live.push_back((int)ti); rd.req_off.push_back(rd.n_req); rd.plane_off.push_back(rd.n_planes);
+    rd.n_req += nr; rd.n_planes += nr * t.lvl.a.nz;
+  }
+  rd.idx.resize(rd.n_planes); rd.mats.resize(16 * (size_t)rd.n_planes); rd.value.resize(rd.n_req);
+  return !rd.live.empty();
+}
+
+// the requests of live target l: its similarity or probe at t.matrix, or its 12 finite differences
+void write_requests(const Target &t, const M4 &s_w2i, int l, Metric &metric, Round &rd) {
+  int at = rd.plane_off[l], rq = rd.req_off[l];
+  auto request = [&](const M4 &tm) {                         // the per-plane matrices of one evaluation (push_request)
+    metric.record(rq++, t);
+    const M4 m = mul(mul(s_w2i, tm), image_to_world(t.lvl.a));
+    double zx = m.m[3], zy = m.m[7], zz = m.m[11];
+    for (int k = 0; k < t.lvl.a.nz; ++k, ++at) {
+      rd.idx[at] = t.first_plane + k;
+      M4 q = m;
+      q.m[3] = zx; q.m[7] = zy; q.m[11] = zz;
+      memcpy(&rd.mats[16 * (size_t)at], q.m, sizeof(q.m));
+      zx += m.m[2]; zy += m.m[6]; zz += m.m[10];             // NextZ()
+    }
+  };
+  if (t.phase != PH_GRAD) { request(t.matrix); return; }
+  for (int i = 0; i < 6; ++i) {
+    double q[6];
+    for (int k = 0; k < 6; ++k) q[k] = t.p[k];
+    q[i] = t.p[i] + t.step; request(params_to_matrix(q));
+    q[i] = t.p[i] - t.step; request(params_to_matrix(q));
+  }
+}
+
+// One step of irtkImageRegistration::Run + irtkGradientDescentOptimizer::Run for a target whose requests came back as value[]:
+// START took the similarity, GRAD the 12 finite differences, LINE one probe of the line search.
+void advance(Target &t, const double *value, const Schedule &p0, int level) {
+  auto take_step = [&](double sign) {                        // Put(i, Get(i) +- StepSize * dx[i]) for every i
+    for (int i = 0; i < 6; ++i) t.p[i] = t.p[i] + sign * (t.step * t.dx[i]);
+    t.matrix = params_to_matrix(t.p);
+  };
+  if (t.phase == PH_START) {
+    t.old_sim = t.new_sim = t.sim = value[0];
+    for (int i = 0; i < 6; ++i) t.start[i] = t.p[i];         // irtkOptimizer::Run stores the parameters, O.cc:113-116
+    t.phase = PH_GRAD;
+    return;
+  }
+  if (t.phase == PH_GRAD) {
+    double norm = 0;
+    for (int i = 0; i < 6; ++i) { const double s1 = value[2 * i], s2 = value[2 * i + 1]; t.dx[i] = (float)(s1 - s2); }
+    t.matrix = params_to_matrix(t.p);                        // Put(i, parameterValue) rebuilt the matrix from the parameters
+    for (int i = 0; i < 6; ++i) norm += t.dx[i] * t.dx[i];
+    norm = sqrt(norm);
+    for (int i = 0; i < 6; ++i) t.dx[i] = norm > 0 ? (float)(t.dx[i] / norm) : 0.0f;
+    t.new_sim = t.sim;                                       // first pass of the do-while, GDO.cc:47-54
+    take_step(+1);
+    t.phase = PH_LINE;
+    return;
+  }
+  t.sim = value[0];
+  if (t.sim > t.new_sim + p0.epsilon) {                      // keep stepping
+    t.new_sim = t.sim;
+    take_step(+1);
+    return;
+  }
+  take_step(-1);                                             // last step was no improvement: back track, GDO.cc:58-61
+  const double eps = t.new_sim > t.old_sim ? t.new_sim - t.old_sim : 0;
+  double max_change = 0;
+  for (int i = 0; i < 6; ++i) max_change = std::max(max_change, fabs(t.p[i] - t.start[i]));
+  bool next_step = true;                                     // IR.cc:482-506
+  if (eps > p0.epsilon && max_change > t.delta) {
+    if (++t.iter_j < p0.iterations[level]) next_step = false;
+  }
+  if (next_step) {
+    t.iter_j = 0;
+    t.step = t.step / 2;
+    t.delta = t.delta / 2.0;
+    if (++t.step_i >= p0.steps[level]) t.done = true;
+  }
+  t.phase = PH_START;
+}
+
+// The optimiser of a level, one round = one batched evaluation.  A round costs the host a few double trigonometric calls per
+// target; with tens of thousands of targets (the patches of the patch-based path) that was 1.6 s of a 2.8 s pass, so the requests
+// are laid out by a prefix sum and written, and the answers consumed, by the host threads -- every target touches only its own
+// state and its own slots.
+int optimise_level(Pass &ps, Metric &metric, const Level &lv, Times &tm, long *n_eval, std::string &err) {
+  const M4 s_w2i = world_to_image(lv.src.a);
+  Round rd;
+  auto over_live = [&](size_t work, const std::function<void(int, int)> &fn) {
+    if (rd.live.size() >= 2048) parallel_rows((int)rd.live.size(), work, fn);
+    else fn(0, (int)rd.live.size());
+  };
+  while (lay_out_round(ps.targets, rd)) {
+    metric.size_round(rd.n_req, rd.n_planes);
+    over_live(3000, [&](int l0, int l1) {
+      for (int l = l0; l < l1; ++l) write_requests(ps.targets[rd.live[l]], s_w2i, l, metric, rd);
+    });
+    const double te = now();
+    if (int rc = metric.evaluate(rd.n_req, rd.n_planes, rd.idx.data(), rd.mats.data(), err)) return rc;
+    tm.eval += now() - te; ++tm.rounds;
+    if (n_eval) *n_eval += (long)rd.n_req;
+    over_live(600, [&](int l0, int l1) {
+      for (int l = l0; l < l1; ++l) {
+        Target &t = ps.targets[rd.live[l]];
+        const int nz = t.lvl.a.nz, nr = t.phase == PH_GRAD ? 12 : 1;
+        double *v = &rd.value[rd.req_off[l]];
+        for (int q = 0; q < nr; ++q) v[q] = metric.value((size_t)rd.req_off[l] + q, (size_t)rd.plane_off[l] + (size_t)q * nz, nz);
+        advance(t, v, lv.ps, lv.level);
+      }
+    });
+  }
+  return 0;
+}
+
+// sim: the similarity is NMI instead of CC (GuessParameterSliceToVolume(useNMI), IRRWP.cc:319-321: the schedule, the optimiser
+// and epsilon are the same), or the windowed cross correlation of radius lncc_radius
+int run_registrations(const Backend &be, std::vector<Target> &targets, const Vol<short> &source, int slice_to_volume, short target_padding,
+                      int sim, int lncc_radius, long *n_eval, std::string &err) {
+  if (targets.empty()) return 0;
+  Pass ps{be, targets, source, slice_to_volume, target_padding, guess_padding(source), !be.external() && be.ctx && !getenv("SVR_HOST_PYRAMID"), {}};
+  Metric metric{be, sim, lncc_radius};
+  Times tm;                                                 // dev: where a registration pass spends its wall time
+  if (ps.dev)
+    if (int rc = upload_pyramid_inputs(ps, err)) return rc;
+  for (int level = 2; level >= 0; --level) {
+    Level lv;
+    lv.level = level;
+    lv.ps = ps.schedule(targets[0]);
+    double t0 = now();
+    if (int rc = level_source(ps, metric, lv, err)) return rc;
+    tm.src += now() - t0; t0 = now();
+    if (int rc = ps.dev ? level_targets_device(ps, metric, lv, err) : level_targets_host(ps, metric, lv, err)) return rc;
+    tm.tgt += now() - t0; t0 = now();
+    if (!ps.dev)
+      if (int rc = pack_level_host(ps, lv, err)) return rc;
+    tm.pack += now() - t0; t0 = now();
+    if (int rc = optimise_level(ps, metric, lv, tm, n_eval, err)) return rc;
+    tm.opt += now() - t0;
+  }
+  if (getenv("SVR_REG_TIMING"))
+    fprintf(stderr, "[svr reg timing] %s: source pyramid %.1f ms, target pyramids %.1f ms, pack + upload %.1f ms, optimiser %.1f ms (%ld rounds, %.1f ms in the batched evaluations)\n",
+            metric.name(), 1e3 * tm.src, 1e3 * tm.tgt, 1e3 * tm.pack, 1e3 * tm.opt, tm.rounds, 1e3 * tm.eval);
+  return 0;
+}
+
+template <class T> Vol<short> to_grey(const svr_image_attr &a, const T *d) {   // irtkGreyImage = irtkRealImage: static_cast per voxel
   Vol<short> v;
   v.a = a;
   v.d.resize(v.n());
@@ -765,6 +840,18 @@ void reset_origin(svr_image_attr &a, M4 &offset) {                       // Rese
 }
 
 void set_err(char err[256], const std::string &m) { if (err) { strncpy(err, m.c_str(), 255); err[255] = 0; } }
+
+// The opening of the two _ex entry points: the similarity taken apart, a place to evaluate it (the engine, or the caller's backend
+// of that similarity's kind) and the entry point's own arguments (`args_ok`) required, the evaluation count zeroed; false = refused
+bool open_registration(svr_ctx *ctx, const svr_ncc_backend *backend, const svr_nmi_backend *nmi_backend, int similarity, bool args_ok,
+                       long *n_evaluations_or_null, Backend &be, int &sim, int &radius) {
+  if (!parse_similarity(similarity, sim, radius)) return false;
+  const bool nmi = sim == SVRH_SIM_NMI;
+  be = Backend{ctx, nmi ? nullptr : backend, nmi ? nmi_backend : nullptr};
+  if ((!ctx && !be.external()) || !args_ok) return false;
+  if (n_evaluations_or_null) *n_evaluations_or_null = 0;
+  return true;
+}
 
 }  // namespace
 
@@ -842,20 +929,14 @@ int svrh_slice_to_volume_registration_ex(svr_ctx *ctx, const svr_ncc_backend *ba
                                          int n_slices, const float *slices, int sx, int sy, const svr_image_attr *attrs, double *transformations,
                                          const svr_image_attr *recon_attr, const float *reconstructed, int flags, long *n_evaluations_or_null,
                                          char err[256]) {
+  Backend be{nullptr, nullptr};
   int sim = 0, radius = 0;
-  const bool known = parse_similarity(similarity, sim, radius);
-  const int nmi = sim == SVRH_SIM_NMI;
-  if (!known || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_slices < 1 || !slices ||
-      !attrs || !transformations || !recon_attr || !reconstructed) {
+  if (!open_registration(ctx, backend, nmi_backend, similarity, n_slices >= 1 && slices && attrs && transformations && recon_attr && reconstructed,
+                         n_evaluations_or_null, be, sim, radius)) {
     set_err(err, "svrh_slice_to_volume_registration: bad arguments");
     return 1;
   }
-  if (n_evaluations_or_null) *n_evaluations_or_null = 0;
-  const Backend be{ctx, nmi ? nullptr : backend, nmi ? nmi_backend : nullptr};
-  Vol<short> source;                                                      // irtkGreyImage source = _reconstructed, RG.cc:2031
-  source.a = *recon_attr;
-  source.d.resize(source.n());
-  for (size_t i = 0; i < source.d.size(); ++i) source.d[i] = (short)reconstructed[i];
+  const Vol<short> source = to_grey(*recon_attr, reconstructed);          // irtkGreyImage source = _reconstructed, RG.cc:2031
   std::vector<Vol<short>> grey(n_slices);
   std::vector<M4> mo_inv(n_slices);
   std::vector<Target> targets;
@@ -963,20 +1044,14 @@ int svrh_package_to_volume_ex(svr_ctx *ctx, const svr_ncc_backend *backend, cons
                               const svr_image_attr *attrs, const double *const *stacks, const int *pack_num, int evenodd, int half, int half_iter,
                               double *transformations, const svr_image_attr *recon_attr, const float *reconstructed, long *n_evaluations_or_null,
                               char err[256]) {
+  Backend be{nullptr, nullptr};
   int sim = 0, radius = 0;
-  const bool known = parse_similarity(similarity, sim, radius);
-  const int nmi = sim == SVRH_SIM_NMI;
-  if (!known || (!ctx && !(nmi ? (const void *)nmi_backend : (const void *)backend)) || n_stacks < 1 || !attrs ||
-      !stacks || !pack_num || !transformations || !recon_attr || !reconstructed) {
+  if (!open_registration(ctx, backend, nmi_backend, similarity, n_stacks >= 1 && attrs && stacks && pack_num && transformations && recon_attr && reconstructed,
+                         n_evaluations_or_null, be, sim, radius)) {
     set_err(err, "svrh_package_to_volume: bad arguments");
     return 1;
   }
-  if (n_evaluations_or_null) *n_evaluations_or_null = 0;
-  const Backend be{ctx, nmi ? nullptr : backend, nmi ? nmi_backend : nullptr};
-  Vol<short> source;
-  source.a = *recon_attr;
-  source.d.resize(source.n());
-  for (size_t i = 0; i < source.d.size(); ++i) source.d[i] = (short)reconstructed[i];
+  const Vol<short> source = to_grey(*recon_attr, reconstructed);
   struct Pack { Vol<short> grey; M4 mo_inv; int first; std::vector<int> slices; };
   std::vector<Pack> packs;
   int first_slice = 0;

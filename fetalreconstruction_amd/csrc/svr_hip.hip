@@ -1046,7 +1046,7 @@ __global__ __launch_bounds__(64) void k_probe_pixel(PsfArgs a, uint32_t idx, flo
   if (lane == 0) { centre[0] = P.cxi; centre[1] = P.cyi; centre[2] = P.czi; }
 }
 
-#include "svr_small.inc"   // list compaction, reductions, the EM / scale / bias / volume kernels, the NCC cost of the IRTK registration
+#include "svr_small.inc"   // list compaction, reductions, the EM / scale / bias / volume kernels
 #include "svr_bias.inc"    // the bias path's Gaussians through the LDS (bias_mode 1)
 
 }  // namespace
@@ -1232,19 +1232,13 @@ struct svr_ctx {
   size_t pyr_full_cap[2] = {0, 0}, pyr_work_cap = 0;
   void *d_pyr_meta = nullptr;
   size_t pyr_meta_cap = 0;
-  int *d_ncc_idx = nullptr;              // grow-only scratch of svr_ncc_evaluate
-  double *d_ncc_m = nullptr;
-  long long *d_ncc_s = nullptr;
-  size_t ncc_cap = 0;
-  unsigned char *d_nmi_io = nullptr;     // grow-only scratch of svr_nmi_evaluate (svr_nmi.inc): requests in, sums and histograms out
-  size_t nmi_cap = 0;
-  std::vector<unsigned char> nmi_staging;
+  unsigned char *d_sim_io = nullptr;     // grow-only arena of svr_ncc / svr_nmi / svr_lncc_evaluate (sim_evaluate, svr_sim.inc): inputs | outputs | test map
+  size_t sim_cap = 0;
+  std::vector<unsigned char> sim_staging;
   double *d_nmi_terms = nullptr;         // c log c for c = 0 .. nmi_terms_n - 1, from the host's libm
   size_t nmi_terms_n = 0;
   unsigned *d_nmi_merge = nullptr;       // merge slots of split evaluations + their counters, all zero between calls
   size_t nmi_slots = 0;
-  unsigned char *d_lncc_io = nullptr;    // grow-only scratch of svr_lncc_evaluate (svr_lncc.inc): requests in, {N, S} and the k maps out
-  size_t lncc_cap = 0;
   float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
   double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
   double *d_qual_partial = nullptr, *d_qual_sums = nullptr;   // svr_slice_quality (svr_quality.inc): likewise
@@ -2298,9 +2292,7 @@ void svr_destroy(svr_ctx *ctx) {
   free_dev(ctx->d_reg_targets);
   free_dev(ctx->d_reg_source);
   free_dev(ctx->d_pyr_full[0]); free_dev(ctx->d_pyr_full[1]); free_dev(ctx->d_pyr_a); free_dev(ctx->d_pyr_b); free_dev(ctx->d_pyr_meta);
-  free_dev(ctx->d_ncc_idx); free_dev(ctx->d_ncc_m); free_dev(ctx->d_ncc_s);
-  free_dev(ctx->d_nmi_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
-  free_dev(ctx->d_lncc_io);
+  free_dev(ctx->d_sim_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
   free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
   free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums);
   free_dev(ctx->d_ssim_partial); free_dev(ctx->d_ssim_sums); free_dev(ctx->d_ssim_map);
@@ -3669,86 +3661,6 @@ int svr_normalise_bias(svr_ctx *ctx, int iter, float sigma_bias) {
   return svr_normalise_bias_finish(ctx, sigma_bias);
 }
 
-// ---- slice-to-volume registration cost --------------------------------------------------
-int svr_ncc_set_targets(svr_ctx *ctx, int n, int tx, int ty, const int16_t *targets) {
-  SVR_ENTER(ctx);
-  if (!ctx || !targets || n <= 0 || tx <= 0 || ty <= 0) return SVR_E_ARG;
-  HIPCHK(hipSetDevice(ctx->device));
-  free_dev(ctx->d_reg_targets);
-  const size_t bytes = (size_t)n * tx * ty * sizeof(short);
-  HIPCHK(hipMalloc(&ctx->d_reg_targets, bytes));
-  HIPCHK(hipMemcpyAsync(ctx->d_reg_targets, targets, bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->reg_n = n; ctx->reg_tx = tx; ctx->reg_ty = ty;
-  return SVR_OK;
-}
-
-int svr_ncc_set_source(svr_ctx *ctx, const uint32_t size[3], const int16_t *source_or_null) {
-  SVR_ENTER(ctx);
-  if (!ctx) return SVR_E_ARG;
-  if (!source_or_null) NEED(ctx->nv > 0, "no source given and no reconstruction volume");
-  uint32_t sx = source_or_null ? size[0] : ctx->vx, sy = source_or_null ? size[1] : ctx->vy,
-           sz = source_or_null ? size[2] : ctx->vz;
-  const size_t n = (size_t)sx * sy * sz;
-  if (n == 0) return SVR_E_ARG;
-  free_dev(ctx->d_reg_source);
-  HIPCHK(hipMalloc(&ctx->d_reg_source, n * sizeof(short)));
-  if (source_or_null) {
-    HIPCHK(hipMemcpyAsync(ctx->d_reg_source, source_or_null, n * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    // irtkGreyImage source = _reconstructed  (RG.cc:2031): static_cast<short> of every voxel
-    hipLaunchKernelGGL(k_f32_to_i16, dim3(nblk(n)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_reg_source, n);
-    KCHK("k_f32_to_i16");
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->reg_vx = sx; ctx->reg_vy = sy; ctx->reg_vz = sz;
-  return SVR_OK;
-}
-
-int svr_ncc_evaluate(svr_ctx *ctx, int n_eval, const int *target_index, const double *matrices,
-                     int64_t *sums6, double *ncc) {
-  SVR_ENTER(ctx);
-  if (!ctx || n_eval <= 0 || !target_index || !matrices) return SVR_E_ARG;
-  NEED(ctx->d_reg_targets && ctx->d_reg_source, "svr_ncc_set_targets / svr_ncc_set_source first");
-  for (int i = 0; i < n_eval; ++i)
-    if (target_index[i] < 0 || target_index[i] >= ctx->reg_n) return fail(ctx, SVR_E_ARG, "target index out of range");
-  // grow-only scratch of the context (the optimiser calls this ~60 k times per registration pass)
-  if ((size_t)n_eval > ctx->ncc_cap) {
-    free_dev(ctx->d_ncc_idx); free_dev(ctx->d_ncc_m); free_dev(ctx->d_ncc_s);
-    ctx->ncc_cap = 0;
-    const size_t cap = std::max<size_t>(256, (size_t)n_eval * 3 / 2);
-    HIPCHK(hipMalloc(&ctx->d_ncc_idx, cap * sizeof(int)));
-    HIPCHK(hipMalloc(&ctx->d_ncc_m, cap * 16 * sizeof(double)));
-    HIPCHK(hipMalloc(&ctx->d_ncc_s, cap * 6 * sizeof(long long)));
-    ctx->ncc_cap = cap;
-  }
-  int *d_idx = ctx->d_ncc_idx;
-  double *d_m = ctx->d_ncc_m;
-  long long *d_s = ctx->d_ncc_s;
-  std::vector<long long> h((size_t)n_eval * 6);
-  hipError_t e = hipMemcpyAsync(d_idx, target_index, n_eval * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_m, matrices, (size_t)n_eval * 16 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_ncc, dim3(n_eval), dim3(256), 0, ctx->stream, ctx->d_reg_targets, ctx->reg_tx, ctx->reg_ty,
-                       d_idx, d_m, ctx->d_reg_source, (int)ctx->reg_vx, (int)ctx->reg_vy, (int)ctx->reg_vz, d_s);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_s, h.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return fail(ctx, (int)e, "svr_ncc_evaluate");
-  for (int i = 0; i < n_eval; ++i) {
-    const long long *s = &h[6 * (size_t)i];
-    if (sums6) for (int k = 0; k < 6; ++k) sums6[6 * (size_t)i + k] = s[k];
-    if (ncc) {
-      // irtkCrossCorrelationSimilarityMetric::Evaluate (…Metric.h:158-165)
-      const double n = (double)s[0], x = (double)s[1], y = (double)s[2], x2 = (double)s[3], y2 = (double)s[4],
-                   xy = (double)s[5];
-      ncc[i] = n > 0 ? (xy - (x * y) / n) / (sqrt(x2 - x * x / n) * sqrt(y2 - y * y / n)) : 0.0;
-    }
-  }
-  return SVR_OK;
-}
-
 // ---- measurement -----------------------------------------------------------------------
 int svr_timer_enable(svr_ctx *ctx, int enable) {
   SVR_ENTER(ctx);
@@ -3892,6 +3804,7 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 
 #include "svr_reg.inc"
 #include "svr_pyr.inc"
+#include "svr_sim.inc"
 #include "svr_nmi.inc"
 #include "svr_lncc.inc"
 #include "svr_motion.inc"

@@ -1,10 +1,9 @@
 // svr_lncc.inc -- local (windowed) normalised cross correlation of the default (IRTK) registration on the device; included by
 // svr_hip.hip.  A deviation from the reference, which has no local metric (--useLNCC, DESIGN 9).
 //
-// The sampling is k_ncc's (svr_small.inc), operation for operation: the source position from the evaluation's 4 x 4 in double, the
-// strict inside test, double trilinear in EvaluateInside's order, value >= 0, IRTK round().  V = the target pixels (tv >= 0) that
-// pass all of it; both operands are then integers in 0..32767.  With radius R the window of pixel p is the (2R+1)^2 box around
-// it, clipped to the plane and restricted to V.  Over the window, in exact integers,
+// The samples are sim_sample's (svr_sim.inc): V = the target pixels it keeps; both operands are then integers in 0..32767.  With
+// radius R the window of pixel p is the (2R+1)^2 box around it, clipped to the plane and restricted to V.  Over the window, in
+// exact integers,
 //   m, St, Ss, Stt, Sss, Sts,   A = m Sts - St Ss,   B = m Stt - St^2,   C = m Sss - Ss^2      (all below 2^53)
 // p is counted iff p in V, m >= ((2R+1)^2 + 1) / 2 and B > 0 (the target window has structure).  A counted pixel scores q = 0 if
 // C == 0, else q = (A / B) * (A / C) negated when A < 0 -- the signed squared local correlation, two IEEE double divisions and one
@@ -47,10 +46,7 @@ __global__ __launch_bounds__(256) void k_lncc(const short *targets, int tx, int 
   __shared__ long long red[4][2];
   const int e = blockIdx.x;
   const short *tgt = targets + (size_t)target_index[e] * tx * ty;
-  const double *M = mats + 16 * (size_t)e;
-  const double m00 = M[0], m01 = M[1], m03 = M[3], m10 = M[4], m11 = M[5], m13 = M[7], m20 = M[8], m21 = M[9], m23 = M[11];
-  const double sx2 = vx - 1, sy2 = vy - 1, sz2 = vz - 1;
-  const size_t o3 = vx, o5 = (size_t)vx * vy;
+  const SimPlane P = sim_plane(mats, e, source, vx, vy, vz);
   const int CW = 1 << cw_log2, WIN = CW + 2 * R, NR = LNCC_BH + 2 * R, SEG = (LNCC_BH * CW) >> 8;   // rows a thread walks per band
   const int c = threadIdx.x & (CW - 1), g = threadIdx.x >> cw_log2;
   const int need = ((2 * R + 1) * (2 * R + 1) + 1) / 2;
@@ -65,20 +61,8 @@ __global__ __launch_bounds__(256) void k_lncc(const short *targets, int tx, int 
         unsigned pk = 0;
         if (j >= 0 && j < ty && i >= 0 && i < tx) {
           const int tv = tgt[(size_t)j * tx + i];
-          if (tv >= 0) {
-            const double X = m00 * i + m01 * j + m03, Y = m10 * i + m11 * j + m13, Z = m20 * i + m21 * j + m23;
-            if ((X > 0) && (X < sx2) && (Y > 0) && (Y < sy2) && (Z > 0) && (Z < sz2)) {
-              const int a = (int)X, b = (int)Y, cz = (int)Z;
-              const double t1 = X - a, u1 = Y - b, v1 = Z - cz, t2 = 1 - t1, u2 = 1 - u1, v2 = 1 - v1;
-              const short *q = source + a + (size_t)b * o3 + (size_t)cz * o5;
-              const double value = (t1 * (u2 * (v2 * q[1] + v1 * q[o5 + 1]) + u1 * (v2 * q[o3 + 1] + v1 * q[o5 + o3 + 1])) +
-                                    t2 * (u2 * (v2 * q[0] + v1 * q[o5]) + u1 * (v2 * q[o3] + v1 * q[o5 + o3])));
-              if (value >= 0) {
-                const int sv = value > 0 ? (int)(value + 0.5) : (int)(value - 0.5);   // irtkCommon.h:85-88
-                pk = (unsigned)tv | 0x8000u | ((unsigned)sv << 16);
-              }
-            }
-          }
+          int sv;
+          if (sim_sample(P, i, j, tv, sv)) pk = (unsigned)tv | 0x8000u | ((unsigned)sv << 16);
         }
         lncc_pk[((j + R) % NR) * WIN + cc] = pk;
       }
@@ -142,42 +126,24 @@ int svr_lncc_evaluate(svr_ctx *ctx, int n_eval, const int *target_index, const d
   if (!ctx || n_eval <= 0 || !target_index || !matrices || !sums2) return SVR_E_ARG;
   NEED(ctx->d_reg_targets && ctx->d_reg_source, "svr_ncc_set_targets / svr_ncc_set_source first");
   if (radius < 1 || radius > LNCC_RMAX) return fail(ctx, SVR_E_ARG, "svr_lncc_evaluate: radius out of range (1..7)");
-  for (int i = 0; i < n_eval; ++i)
-    if (target_index[i] < 0 || target_index[i] >= ctx->reg_n) return fail(ctx, SVR_E_ARG, "target index out of range");
   const int tx = ctx->reg_tx, ty = ctx->reg_ty;
   const size_t npix = (size_t)tx * ty;
-  // grow-only scratch of the context: matrices | sums | target indices | the k maps (tests only)
-  const size_t b_mats = (size_t)n_eval * 16 * sizeof(double), b_sums = (size_t)n_eval * 2 * sizeof(long long), b_idx = (size_t)n_eval * sizeof(int),
-               o_map = (b_mats + b_sums + b_idx + 7) / 8 * 8, b_map = k_or_null ? (size_t)n_eval * npix * sizeof(int) : 0, need = o_map + b_map;
-  if (need > ctx->lncc_cap) {
-    free_dev(ctx->d_lncc_io);
-    ctx->lncc_cap = 0;
-    const size_t cap = need * 3 / 2 + 4096;
-    HIPCHK(hipMalloc(&ctx->d_lncc_io, cap));
-    ctx->lncc_cap = cap;
-  }
-  unsigned char *d = ctx->d_lncc_io;
-  double *d_m = reinterpret_cast<double *>(d);
-  long long *d_s = reinterpret_cast<long long *>(d + b_mats);
-  int *d_idx = reinterpret_cast<int *>(d + b_mats + b_sums);
-  int *d_map = k_or_null ? reinterpret_cast<int *>(d + o_map) : nullptr;
   // columns a workgroup takes at once: the plane's width rounded up to a power of two, 32..256 (wider planes go in strips)
   int cw_log2 = 5;
   while (cw_log2 < 8 && (1 << cw_log2) < tx) ++cw_log2;
   const size_t lds = (size_t)(LNCC_BH + 2 * radius) * ((1 << cw_log2) + 2 * radius) * sizeof(unsigned);
   static_assert((LNCC_BH + 2 * LNCC_RMAX) * (256 + 2 * LNCC_RMAX) * sizeof(unsigned) + 64 <= 65536, "k_lncc: LDS beyond a static allocation");
+  // matrices | target indices in; {N, S} and (tests) the k maps out
+  const size_t b_mats = (size_t)n_eval * 16 * sizeof(double), b_map = k_or_null ? (size_t)n_eval * npix * sizeof(int) : 0;
   std::vector<long long> h((size_t)n_eval * 2);
-  hipError_t e = hipMemcpyAsync(d_idx, target_index, b_idx, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_m, matrices, b_mats, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_lncc, dim3(n_eval), dim3(256), lds, ctx->stream, ctx->d_reg_targets, tx, ty, d_idx, d_m, ctx->d_reg_source,
-                       (int)ctx->reg_vx, (int)ctx->reg_vy, (int)ctx->reg_vz, radius, cw_log2, d_s, d_map);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_s, b_sums, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && k_or_null) e = hipMemcpyAsync(k_or_null, d_map, b_map, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return fail(ctx, (int)e, "svr_lncc_evaluate");
+  if (int rc = sim_evaluate(ctx, "svr_lncc_evaluate", target_index, n_eval, {{matrices, b_mats}, {target_index, n_eval * sizeof(int)}}, h.data(),
+                            h.size() * sizeof(long long), k_or_null, b_map, 0, [&](unsigned char *d, unsigned char *d_out, unsigned char *d_map) {
+                              hipLaunchKernelGGL(k_lncc, dim3(n_eval), dim3(256), lds, ctx->stream, ctx->d_reg_targets, tx, ty,
+                                                 reinterpret_cast<const int *>(d + b_mats), reinterpret_cast<const double *>(d), ctx->d_reg_source,
+                                                 (int)ctx->reg_vx, (int)ctx->reg_vy, (int)ctx->reg_vz, radius, cw_log2,
+                                                 reinterpret_cast<long long *>(d_out), reinterpret_cast<int *>(d_map));
+                            }))
+    return rc;
   for (size_t i = 0; i < h.size(); ++i) sums2[i] = h[i];
   return SVR_OK;
 }

@@ -1,10 +1,9 @@
 // svr_nmi.inc -- normalised mutual information of the default (IRTK) registration on the device; included by svr_hip.hip.
 //
 // irtkImageRigidRegistrationWithPadding::Evaluate (IRRWP.cc:534-610) with irtkNormalisedMutualInformationSimilarityMetric
-// over irtkHistogram_2D<double>: the sampling of k_ncc (svr_small.inc) -- double trilinear in EvaluateInside's order, IRTK
-// round(), value >= 0 -- but every sample adds one to the joint bin (target bin, source bin) instead of six moments.  The
-// source was binned before it is interpolated (irtkCalculateNumberOfBins, irtkUtil.cc:438-474: v > 0 -> int(v / width));
-// the target's bin is taken on the fly (tv / width).
+// over irtkHistogram_2D<double>: the samples are sim_sample's (svr_sim.inc), and every sample adds one to the joint bin (target
+// bin, source bin) instead of six moments.  The source was binned before it is interpolated (irtkCalculateNumberOfBins,
+// irtkUtil.cc:438-474: v > 0 -> int(v / width)); the target's bin is taken on the fly (tv / width).
 //
 // One evaluation = one candidate matrix on all planes of a target (1 for a slice, nz for a package): the entropies are not
 // additive over planes, so the histogram spans them all.  A workgroup builds the histogram of a run of planes in LDS with
@@ -67,31 +66,20 @@ __global__ __launch_bounds__(256) void k_nmi(const short *targets, int tx, int t
   for (int k = threadIdx.x; k < NMI_H; k += 256) h[k] = 0;
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();
-  // ---- the samples of planes [p0, p1): k_ncc's arithmetic -------------------------------------------------------------
-  const double sx2 = vx - 1, sy2 = vy - 1, sz2 = vz - 1;
-  const size_t o3 = vx, o5 = (size_t)vx * vy;
+  // ---- the samples of planes [p0, p1) --------------------------------------------------------------------------------------
   const int npix = tx * ty;
   for (int pl = b.p0; pl < b.p1; ++pl) {
     const short *tgt = targets + (size_t)target_index[pl] * npix;
-    const double *M = mats + 16 * (size_t)pl;
-    const double m00 = M[0], m01 = M[1], m03 = M[3], m10 = M[4], m11 = M[5], m13 = M[7], m20 = M[8], m21 = M[9], m23 = M[11];
+    const SimPlane P = sim_plane(mats, pl, source, vx, vy, vz);
     for (int p = threadIdx.x; p < npix; p += 256) {
       const int tv = tgt[p];
       if (tv < 0) continue;
       const int j = p / tx, i = p - j * tx;
-      const double X = m00 * i + m01 * j + m03, Y = m10 * i + m11 * j + m13, Z = m20 * i + m21 * j + m23;
-      if ((X > 0) && (X < sx2) && (Y > 0) && (Y < sy2) && (Z > 0) && (Z < sz2)) {
-        const int a = (int)X, bb = (int)Y, c = (int)Z;
-        const double t1 = X - a, u1 = Y - bb, v1 = Z - c, t2 = 1 - t1, u2 = 1 - u1, v2 = 1 - v1;
-        const short *q = source + a + (size_t)bb * o3 + (size_t)c * o5;
-        const double value = (t1 * (u2 * (v2 * q[1] + v1 * q[o5 + 1]) + u1 * (v2 * q[o3 + 1] + v1 * q[o5 + o3 + 1])) +
-                              t2 * (u2 * (v2 * q[0] + v1 * q[o5]) + u1 * (v2 * q[o3] + v1 * q[o5 + o3])));
-        if (value >= 0) {
-          const int sb = (int)(value + 0.5);                   // irtkCommon.h:85-88 for value >= 0
-          const int tb = tv / width;
-          if (tb < nbt && sb < nbs) atomicAdd(&h[sb * nbt + tb], 1u);
-          else bad = 1;                                        // irtkHistogram_2D::Add would exit: the caller's bins are wrong
-        }
+      int sb;                                                  // the sampler's two-sided round(): a sample has value >= 0, where it
+      if (sim_sample(P, i, j, tv, sb)) {                       // gives the same integer as (int)(value + 0.5) (irtkCommon.h:85-88)
+        const int tb = tv / width;
+        if (tb < nbt && sb < nbs) atomicAdd(&h[sb * nbt + tb], 1u);
+        else bad = 1;                                          // irtkHistogram_2D::Add would exit: the caller's bins are wrong
       }
     }
   }
@@ -224,8 +212,6 @@ int svr_nmi_evaluate(svr_ctx *ctx, int n_eval, const int *planes_per_eval, const
     planes += np;
     max_count = std::max(max_count, (size_t)np * npix);        // no count of an evaluation exceeds its target pixels
   }
-  for (size_t i = 0; i < planes; ++i)
-    if (target_index[i] < 0 || target_index[i] >= ctx->reg_n) return fail(ctx, SVR_E_ARG, "target index out of range");
   if (max_count >= (1ull << 32)) return fail(ctx, SVR_E_ARG, "svr_nmi_evaluate: an evaluation of 2^32 pixels or more");
   // the term table t[c] = c log c with the host's libm (the values of the host restatement), grown with the counts
   if (ctx->nmi_terms_n <= max_count) {
@@ -251,43 +237,21 @@ int svr_nmi_evaluate(svr_ctx *ctx, int n_eval, const int *planes_per_eval, const
     ctx->nmi_slots = cap;
   }
   unsigned *d_merge = ctx->d_nmi_merge, *d_counters = d_merge ? d_merge + ctx->nmi_slots * (NMI_H + 1) : nullptr;
-  // one upload: matrices | blocks | evaluations | target indices; then the results | the histograms
+  // matrices | blocks | evaluations | target indices in; the results and (tests) the histograms out
   const size_t b_mats = planes * 16 * sizeof(double), b_blocks = blocks.size() * sizeof(NmiBlock), b_evs = evs.size() * sizeof(NmiEval),
-               b_idx = planes * sizeof(int), b_out = (size_t)n_eval * 4 * sizeof(double);
-  const size_t b_in = b_mats + b_blocks + b_evs + b_idx, o_out = (b_in + 7) / 8 * 8;
-  const size_t b_hist = hist_or_null ? (size_t)n_eval * NMI_H * sizeof(unsigned) : 0, need = o_out + b_out + b_hist;
-  if (need > ctx->nmi_cap) {
-    free_dev(ctx->d_nmi_io);
-    ctx->nmi_cap = 0;
-    const size_t cap = need * 3 / 2 + 4096;
-    HIPCHK(hipMalloc(&ctx->d_nmi_io, cap));
-    ctx->nmi_cap = cap;
-  }
-  ctx->nmi_staging.resize(b_in);
-  unsigned char *hs = ctx->nmi_staging.data();
-  memcpy(hs, matrices, b_mats);
-  memcpy(hs + b_mats, blocks.data(), b_blocks);
-  memcpy(hs + b_mats + b_blocks, evs.data(), b_evs);
-  memcpy(hs + b_mats + b_blocks + b_evs, target_index, b_idx);
-  unsigned char *d = ctx->d_nmi_io;
-  const double *d_mats = reinterpret_cast<const double *>(d);
-  const NmiBlock *d_blocks = reinterpret_cast<const NmiBlock *>(d + b_mats);
-  const NmiEval *d_evs = reinterpret_cast<const NmiEval *>(d + b_mats + b_blocks);
-  const int *d_idx = reinterpret_cast<const int *>(d + b_mats + b_blocks + b_evs);
-  double *d_out = reinterpret_cast<double *>(d + o_out);
-  unsigned *d_hist = hist_or_null ? reinterpret_cast<unsigned *>(d + o_out + b_out) : nullptr;
+               b_out = (size_t)n_eval * 4 * sizeof(double), b_hist = hist_or_null ? (size_t)n_eval * NMI_H * sizeof(unsigned) : 0;
   std::vector<double> h4((size_t)n_eval * 4);
-  hipError_t e = hipMemcpyAsync(d, hs, b_in, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_nmi, dim3((unsigned)blocks.size()), dim3(256), 0, ctx->stream, ctx->d_reg_targets, ctx->reg_tx, ctx->reg_ty, d_idx,
-                       d_mats, ctx->d_reg_source, (int)ctx->reg_vx, (int)ctx->reg_vy, (int)ctx->reg_vz, d_blocks, d_evs, source_nbins,
-                       ctx->d_nmi_terms, d_merge, d_counters, d_out, d_hist);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h4.data(), d_out, b_out, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && hist_or_null) e = hipMemcpyAsync(hist_or_null, d_hist, b_hist, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return fail(ctx, (int)e, "svr_nmi_evaluate");
+  if (int rc = sim_evaluate(ctx, "svr_nmi_evaluate", target_index, planes,
+                            {{matrices, b_mats}, {blocks.data(), b_blocks}, {evs.data(), b_evs}, {target_index, planes * sizeof(int)}}, h4.data(), b_out,
+                            hist_or_null, b_hist, 0, [&](unsigned char *d, unsigned char *d_out, unsigned char *d_hist) {
+                              hipLaunchKernelGGL(k_nmi, dim3((unsigned)blocks.size()), dim3(256), 0, ctx->stream, ctx->d_reg_targets, ctx->reg_tx, ctx->reg_ty,
+                                                 reinterpret_cast<const int *>(d + b_mats + b_blocks + b_evs), reinterpret_cast<const double *>(d),
+                                                 ctx->d_reg_source, (int)ctx->reg_vx, (int)ctx->reg_vy, (int)ctx->reg_vz,
+                                                 reinterpret_cast<const NmiBlock *>(d + b_mats), reinterpret_cast<const NmiEval *>(d + b_mats + b_blocks),
+                                                 source_nbins, ctx->d_nmi_terms, d_merge, d_counters, reinterpret_cast<double *>(d_out),
+                                                 reinterpret_cast<unsigned *>(d_hist));
+                            }))
+    return rc;
   for (int i = 0; i < n_eval; ++i)
     if (h4[4 * (size_t)i] < 0) return fail(ctx, SVR_E_ARG, "svr_nmi_evaluate: a sample fell outside the bins (wrong widths or bin counts)");
   memcpy(out4, h4.data(), b_out);

@@ -590,63 +590,3 @@ __global__ void k_divexp(float *recon, const float *bias, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { float a = recon[i]; if (a != -1.0f) recon[i] = a / expf(-bias[i]); }
 }
-
-// ------------------------------------------------------------------------------------------
-// slice-to-volume NCC cost (the CPU-default registration metric, SURVEY 8a16):
-// irtkImageRigidRegistrationWithPadding::Evaluate + irtkCrossCorrelationSimilarityMetric.
-// One workgroup per (target slice, candidate transform): every target pixel >= 0 is mapped into the
-// source volume, trilinearly interpolated in double in EvaluateInside's operation order, rounded
-// like IRTK's round(), and the six integer moments are accumulated exactly in int64 and reduced
-// with wavefront shuffles -- order-independent, so the moments equal the serial CPU loop's.
-// ------------------------------------------------------------------------------------------
-__global__ void k_f32_to_i16(const float *in, short *out, size_t n) {   // static_cast<short>(float): truncation
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (short)in[i];
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void k_ncc(const short *targets, int tx, int ty, const int *target_index,
-                                             const double *mats, const short *source, int vx, int vy, int vz,
-                                             long long *sums) {
-  __shared__ long long sm[4][6];
-  const int e = blockIdx.x;
-  const short *tgt = targets + (size_t)target_index[e] * tx * ty;
-  const double *M = mats + 16 * (size_t)e;
-  const double m00 = M[0], m01 = M[1], m03 = M[3], m10 = M[4], m11 = M[5], m13 = M[7], m20 = M[8], m21 = M[9],
-               m23 = M[11];
-  const double sx2 = vx - 1, sy2 = vy - 1, sz2 = vz - 1;
-  const size_t o3 = vx, o5 = (size_t)vx * vy;
-  long long a_n = 0, a_x = 0, a_y = 0, a_x2 = 0, a_y2 = 0, a_xy = 0;
-  for (int p = threadIdx.x; p < tx * ty; p += 256) {
-    const int tv = tgt[p];
-    if (tv < 0) continue;
-    const int j = p / tx, i = p - j * tx;
-    const double X = m00 * i + m01 * j + m03, Y = m10 * i + m11 * j + m13, Z = m20 * i + m21 * j + m23;
-    if ((X > 0) && (X < sx2) && (Y > 0) && (Y < sy2) && (Z > 0) && (Z < sz2)) {
-      const int a = (int)X, b = (int)Y, c = (int)Z;
-      const double t1 = X - a, u1 = Y - b, v1 = Z - c, t2 = 1 - t1, u2 = 1 - u1, v2 = 1 - v1;
-      const short *q = source + a + (size_t)b * o3 + (size_t)c * o5;
-      const double value = (t1 * (u2 * (v2 * q[1] + v1 * q[o5 + 1]) + u1 * (v2 * q[o3 + 1] + v1 * q[o5 + o3 + 1])) +
-                            t2 * (u2 * (v2 * q[0] + v1 * q[o5]) + u1 * (v2 * q[o3] + v1 * q[o5 + o3])));
-      if (value >= 0) {
-        const int sv = value > 0 ? (int)(value + 0.5) : (int)(value - 0.5);   // irtkCommon.h:85-88
-        a_n += 1; a_x += tv; a_y += sv; a_x2 += (long long)tv * tv; a_y2 += (long long)sv * sv;
-        a_xy += (long long)tv * sv;
-      }
-    }
-  }
-  long long v[6] = {a_n, a_x, a_y, a_x2, a_y2, a_xy};
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    v[k] = wave_sum_i64(v[k]);
-    if (lane == 0) sm[w][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) sums[6 * (size_t)e + threadIdx.x] = sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
-}

@@ -1,5 +1,5 @@
-"""One P4 slice-to-volume pass of the IRTK schedule (280 slices) with CC and with the windowed cross correlation (--useLNCC) at radius
-3 and 7, every similarity on the GPU, in one process: reconstructs once, then registers from the true transformations; prints wall time,
+"""One P4 slice-to-volume pass of the IRTK schedule (280 slices) with CC, with NMI (--useNMI) and with the windowed cross correlation
+(--useLNCC) at radius 3 and 7, every similarity on the GPU, in one process: reconstructs once, then registers from the true transformations; prints wall time,
 evaluations, the ratio to the CC pass and the schedule's own split (SVR_REG_TIMING=1 on stderr).
 usage: lncc_timing.py [p4|s8 ...]"""
 import os
@@ -23,7 +23,7 @@ for which in sys.argv[1:] or ["p4"]:
     vol = rec.syncCPU().reshape(P.vsize[::-1])
     rattr = geo.ImageAttributes(*P.vsize, *P.vdim)
     T = P.slice_t.reshape(-1, 4, 4).astype(np.float64)
-    cases = (("cc", None), ("lncc", 3), ("lncc", 7))
+    cases = (("cc", None), ("nmi", None), ("lncc", 3), ("lncc", 7))
     per_eval = {}
     for rep in range(2):                                  # the second round is the measurement (first calls allocate)
         for sim, radius in cases:
@@ -34,4 +34,4 @@ for which in sys.argv[1:] or ["p4"]:
             print(f"{which} {sim}{'' if radius is None else ' R=' + str(radius)}: {P.ns} slices, wall {wall:.3f} s, {nev} similarity evaluations, "
                   f"{1e6 * wall / nev:.2f} us each", flush=True)
     for sim, radius in cases[1:]:
-        print(f"{which} lncc R={radius} / cc, wall per evaluation: {per_eval[(sim, radius)] / per_eval[('cc', None)]:.2f}x", flush=True)
+        print(f"{which} {sim}{'' if radius is None else ' R=' + str(radius)} / cc, wall per evaluation: {per_eval[(sim, radius)] / per_eval[('cc', None)]:.2f}x", flush=True)
