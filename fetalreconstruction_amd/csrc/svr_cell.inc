@@ -92,41 +92,30 @@ struct CellArgs {
 struct CellState {
   bool valid = false, usable = true;
   CellArgs a;
-  int *d_centres = nullptr;            // int4 per active pixel (svr_ctx::d_cellc: shared by the scatter's and the gather's lists)
-  uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
-  uint32_t *d_head = nullptr, *d_runid = nullptr;
-  CellRec *d_recs = nullptr;
-  CellRun *d_runs = nullptr;
-  uint32_t *d_cell_first = nullptr, *d_cell_last = nullptr, *d_items = nullptr, *d_item_flag = nullptr, *d_item_pos = nullptr;
-  uint4 *d_ents = nullptr;
-  size_t cap_iflag = 0, cap_ipos = 0, cap_ents = 0;
-  int *d_item_of = nullptr;
-  f2 *d_stage = nullptr;
-  unsigned char *d_rowcol = nullptr;
-  size_t cap_rowcol = 0;
-  float *d_gf = nullptr;               // gather: 1 / v_PSF_sums per sorted pixel, 0 = not a PSF pixel
-  f2 *d_part = nullptr;                // gather: the units' partial sums [unit][sorted pixel] (a run's pixels of one plane: neighbours)
-  size_t cap_gf = 0, cap_part = 0;
-  uint32_t *d_pid = nullptr;           // table ids of the sorted records (cell_pids)
-  unsigned char *d_act = nullptr;      // PSF-pixel flags of the sorted records for the scatter that writes the table (k_cell_factors)
-  size_t cap_pid = 0, cap_act = 0;
+  int *d_centres = nullptr;            // (alias) int4 per active pixel (svr_ctx::d_cellc: shared by the scatter's and the gather's lists)
+  DevBuf<uint64_t> d_keys, d_keys2;
+  DevBuf<uint32_t> d_head, d_runid;
+  DevBuf<CellRec> d_recs;
+  DevBuf<CellRun> d_runs;
+  DevBuf<uint32_t> d_cell_first, d_cell_last, d_items, d_item_flag, d_item_pos;
+  DevBuf<uint4> d_ents;
+  DevBuf<int> d_item_of;
+  DevBuf<f2> d_stage;
+  DevBuf<unsigned char> d_rowcol;
+  DevBuf<float> d_gf;                  // gather: 1 / v_PSF_sums per sorted pixel, 0 = not a PSF pixel
+  DevBuf<f2> d_part;                   // gather: the units' partial sums [unit][sorted pixel] (a run's pixels of one plane: neighbours)
+  DevBuf<uint32_t> d_pid;              // table ids of the sorted records (cell_pids)
+  DevBuf<unsigned char> d_act;         // PSF-pixel flags of the sorted records for the scatter that writes the table (k_cell_factors)
   bool pid_valid = false;
   bool gf_valid = false;               // d_gf matches v_PSF_sums (it changes with a Gaussian pass, not with an SR iteration: CH_PSF_SUMS)
-  void *d_tmp = nullptr;
-  int *d_range = nullptr;              // [2][6] min / max of the centres, [12] dropped pixels
-  size_t cap_px = 0, cap_runs = 0, cap_cells = 0, cap_tab = 0, cap_items = 0, cap_stage = 0, cap_tmp = 0;
+  DevBuf<unsigned char> d_tmp;         // the sorts' and scans' temporary storage (bytes)
+  DevBuf<int> d_range;                 // [2][6] min / max of the centres, [12] dropped pixels
   uint32_t n_sorted = 0, n_runs = 0, n_cells = 0;
   uint64_t dead_units = 0;             // (pixel, plane) units of the sorted pixels that are dead (unit_is_dead)
   int ns_support = 0;
 };
 
-void cell_free(CellState *c) {
-  if (!c) return;
-  free_dev(c->d_keys); free_dev(c->d_keys2); free_dev(c->d_head); free_dev(c->d_runid);
-  free_dev(c->d_recs); free_dev(c->d_runs); free_dev(c->d_cell_first); free_dev(c->d_cell_last); free_dev(c->d_items);
-  free_dev(c->d_item_of); free_dev(c->d_ents); free_dev(c->d_item_flag); free_dev(c->d_item_pos); free_dev(c->d_stage); free_dev(c->d_rowcol); free_dev(c->d_gf); free_dev(c->d_part); free_dev(c->d_pid); free_dev(c->d_act); free_dev(c->d_tmp); free_dev(c->d_range);
-  delete c;
-}
+void cell_free(CellState *c) { delete c; }
 
 __device__ __forceinline__ int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
 // floordiv(a, b) for -2^16 <= a < 2^16 and b <= 1024 by multiplication: m = ceil(2^32 / b), q = ceil(2^16 / b); a + b q is in [0, 2^18), where
@@ -1387,16 +1376,6 @@ __global__ void k_cell_gauss1_finish(PsfArgs a, CellArgs ca, const CellRec *recs
   }
 }
 
-template <class T>
-int cell_grow(svr_ctx *ctx, T *&p, size_t &cap, size_t want) {
-  if (want <= cap) return SVR_OK;
-  free_dev(p);
-  cap = 0;
-  HIPCHK(hipMalloc(&p, want * sizeof(T)));
-  cap = want;
-  return SVR_OK;
-}
-
 // (Re)build the cell structures for the current slice geometry.  On anything the layout cannot hold (centres beyond +-32000: the records
 // keep them as shorts; more than 1024 planes in a class, 2^18 cells or more, more than 16384 pixels of one slice in one cell around one
 // band of planes, a slice grid of more than 2^20 pixels, more than 2^17 slices: the fields of items[] and of the sort key; LDS boxes
@@ -1477,21 +1456,12 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_active;
   a.n = n;
-  int r;
-  {
-    size_t cap = cs.cap_px;
-    if (n > cap) {
-      free_dev(cs.d_keys); free_dev(cs.d_keys2); free_dev(cs.d_head); free_dev(cs.d_runid); free_dev(cs.d_recs);
-      cs.cap_px = 0;
-      HIPCHK(hipMalloc(&cs.d_keys, (size_t)n * sizeof(uint64_t)));
-      HIPCHK(hipMalloc(&cs.d_keys2, (size_t)n * sizeof(uint64_t)));
-      HIPCHK(hipMalloc(&cs.d_head, (size_t)n * sizeof(uint32_t)));
-      HIPCHK(hipMalloc(&cs.d_runid, (size_t)n * sizeof(uint32_t)));
-      HIPCHK(hipMalloc(&cs.d_recs, (size_t)n * sizeof(CellRec)));
-      cs.cap_px = n;
-    }
-  }
-  if (!cs.d_range) HIPCHK(hipMalloc(&cs.d_range, 16 * sizeof(int)));
+  HIPCHK(cs.d_keys.reserve(n));
+  HIPCHK(cs.d_keys2.reserve(n));
+  HIPCHK(cs.d_head.reserve(n));
+  HIPCHK(cs.d_runid.reserve(n));
+  HIPCHK(cs.d_recs.reserve(n));
+  HIPCHK(cs.d_range.reserve(16));
   int hr[16];
   for (int c = 0; c < 2; ++c) for (int k = 0; k < 3; ++k) { hr[6 * c + 2 * k] = INT_MAX; hr[6 * c + 2 * k + 1] = INT_MIN; }
   hr[12] = hr[13] = hr[14] = hr[15] = 0;
@@ -1499,12 +1469,7 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   // the centres and their ranges do not depend on the cell size: the scatter's and the gather's lists share one pass (invalidate
   // drops it with the lists)
   if (!ctx->cellc_valid || ctx->cellc_n != n) {
-    if ((size_t)n > ctx->cellc_cap) {
-      free_dev(ctx->d_cellc);
-      ctx->cellc_cap = 0;
-      HIPCHK(hipMalloc(&ctx->d_cellc, (size_t)n * 4 * sizeof(int)));
-      ctx->cellc_cap = n;
-    }
+    HIPCHK(ctx->d_cellc.reserve((size_t)n * 4));
     hipLaunchKernelGGL(k_cell_centres, dim3(std::min<size_t>(nblk(n), 2048)), dim3(256), 0, ctx->stream, a, NC, ctx->d_cellc, cs.d_range);
     KCHK("k_cell_centres");
     HIPCHK(hipMemcpyAsync(ctx->cellc_range, cs.d_range, sizeof(hr), hipMemcpyDeviceToHost, ctx->stream));
@@ -1570,20 +1535,15 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   if (svr_sort_keys_u64(nullptr, &tb, cs.d_keys, cs.d_keys2, n, 64, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: sort (size query)");
   if (svr_inclusive_sum_u32(nullptr, &tb2, cs.d_head, cs.d_runid, n, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: scan (size query)");
   tb = std::max(tb, tb2);
-  if (tb > cs.cap_tmp) {
-    free_dev(cs.d_tmp);
-    cs.cap_tmp = 0;
-    HIPCHK(hipMalloc(&cs.d_tmp, tb));
-    cs.cap_tmp = tb;
-  }
-  size_t tbs = cs.cap_tmp;
+  HIPCHK(cs.d_tmp.reserve(tb));
+  size_t tbs = cs.d_tmp.capacity();
   if (svr_sort_keys_u64(cs.d_tmp, &tbs, cs.d_keys, cs.d_keys2, n, 64, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: sort");
   mark("keys, sort");
   const uint32_t ns_ = cs.n_sorted;
   if (ctx->pvr) hipLaunchKernelGGL((k_cell_records<PVR_N, true>), dim3(nblk(ns_)), dim3(256), 0, ctx->stream, a, cs.d_keys2, ns_, cs.d_recs, cs.d_head, reinterpret_cast<unsigned int *>(cs.d_range + 13));
   else hipLaunchKernelGGL((k_cell_records<PSF_SUPPORT, false>), dim3(nblk(ns_)), dim3(256), 0, ctx->stream, a, cs.d_keys2, ns_, cs.d_recs, cs.d_head, reinterpret_cast<unsigned int *>(cs.d_range + 13));
   KCHK("k_cell_records");
-  tbs = cs.cap_tmp;
+  tbs = cs.d_tmp.capacity();
   if (svr_inclusive_sum_u32(cs.d_tmp, &tbs, cs.d_head, cs.d_runid, ns_, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: scan");
   uint32_t nruns = 0;
   HIPCHK(hipMemcpyAsync(&nruns, cs.d_runid + (ns_ - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1596,22 +1556,12 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
     cs.dead_units = du;
   }
   mark("records, scan");
-  if ((r = cell_grow(ctx, cs.d_runs, cs.cap_runs, (size_t)nruns))) return r;
-  if (ncells > cs.cap_cells) {
-    free_dev(cs.d_cell_first); free_dev(cs.d_cell_last);
-    cs.cap_cells = 0;
-    HIPCHK(hipMalloc(&cs.d_cell_first, ncells * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&cs.d_cell_last, ncells * sizeof(uint32_t)));
-    cs.cap_cells = ncells;
-  }
+  HIPCHK(cs.d_runs.reserve(nruns));
+  HIPCHK(cs.d_cell_first.reserve(ncells));
+  HIPCHK(cs.d_cell_last.reserve(ncells));
   const size_t tab = (size_t)ncells * ca.ngs;
-  if (tab > cs.cap_tab) {
-    free_dev(cs.d_item_of); free_dev(cs.d_items);
-    cs.cap_tab = 0;
-    HIPCHK(hipMalloc(&cs.d_item_of, tab * sizeof(int)));
-    HIPCHK(hipMalloc(&cs.d_items, tab * sizeof(uint32_t)));
-    cs.cap_tab = tab;
-  }
+  HIPCHK(cs.d_item_of.reserve(tab));
+  HIPCHK(cs.d_items.reserve(tab));
   HIPCHK(hipMemsetAsync(cs.d_cell_first, 0, ncells * sizeof(uint32_t), ctx->stream));
   HIPCHK(hipMemsetAsync(cs.d_cell_last, 0, ncells * sizeof(uint32_t), ctx->stream));
   hipLaunchKernelGGL(k_cell_runs, dim3(nblk(ns_)), dim3(256), 0, ctx->stream, cs.d_keys2, cs.d_head, cs.d_runid, ns_, cs.d_runs);
@@ -1621,7 +1571,7 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
                      cs.d_cell_last, ctx->d_counter + 1);
   KCHK("k_cell_run_ranges");
   if (need_stage) {
-    if ((r = cell_grow(ctx, cs.d_rowcol, cs.cap_rowcol, nrowcol))) return r;
+    HIPCHK(cs.d_rowcol.reserve(nrowcol));
     HIPCHK(hipMemsetAsync(cs.d_rowcol, 0, nrowcol, ctx->stream));
     hipLaunchKernelGGL(k_cell_rowcol, dim3(nblk(nruns)), dim3(256), 0, ctx->stream, ca, cs.d_runs, nruns, cs.d_rowcol);
     KCHK("k_cell_rowcol");
@@ -1630,19 +1580,14 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   ca.recs = cs.d_recs; ca.runs = cs.d_runs; ca.cell_first = cs.d_cell_first; ca.cell_last = cs.d_cell_last;
   ca.items = cs.d_items; ca.item_of = cs.d_item_of;
   {
-    if ((r = cell_grow(ctx, cs.d_item_flag, cs.cap_iflag, tab))) return r;
-    if ((r = cell_grow(ctx, cs.d_item_pos, cs.cap_ipos, tab))) return r;
+    HIPCHK(cs.d_item_flag.reserve(tab));
+    HIPCHK(cs.d_item_pos.reserve(tab));
     hipLaunchKernelGGL(k_cell_item_flags, dim3(nblk(tab)), dim3(256), 0, ctx->stream, ca, NC, NH, (uint32_t)ncells, cs.d_item_flag);
     KCHK("k_cell_item_flags");
     size_t tb3 = 0;
     if (svr_inclusive_sum_u32(nullptr, &tb3, cs.d_item_flag, cs.d_item_pos, tab, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: scan (size query)");
-    if (tb3 > cs.cap_tmp) {
-      free_dev(cs.d_tmp);
-      cs.cap_tmp = 0;
-      HIPCHK(hipMalloc(&cs.d_tmp, tb3));
-      cs.cap_tmp = tb3;
-    }
-    tb3 = cs.cap_tmp;
+    HIPCHK(cs.d_tmp.reserve(tb3));
+    tb3 = cs.d_tmp.capacity();
     if (svr_inclusive_sum_u32(cs.d_tmp, &tb3, cs.d_item_flag, cs.d_item_pos, tab, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: scan of the item flags");
     hipLaunchKernelGGL(k_cell_items, dim3(nblk(tab)), dim3(256), 0, ctx->stream, ca, (uint32_t)tab, cs.d_item_flag, cs.d_item_pos, cs.d_items, cs.d_item_of);
     KCHK("k_cell_items");
@@ -1658,64 +1603,46 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   uint32_t nents = 0;
   {
     // launch order (heaviest first) and parts (see k_cell_item_work)
-    uint64_t *k1 = nullptr, *k2 = nullptr;
-    uint32_t *it2 = nullptr, *work = nullptr, *parts = nullptr, *epos = nullptr;
-    auto drop = [&]() { free_dev(k1); free_dev(k2); free_dev(it2); free_dev(work); free_dev(parts); free_dev(epos); };
+    DevBuf<uint64_t> k1, k2;
+    DevBuf<uint32_t> it2, work, parts, epos;
     const bool order = ctx->cell_order > 0 && nitems > 1;
-    int rc = SVR_OK;
-    do {
-      if (hipMalloc(&k1, (size_t)nitems * 8) != hipSuccess || hipMalloc(&k2, (size_t)nitems * 8) != hipSuccess || hipMalloc(&it2, (size_t)nitems * 4) != hipSuccess ||
-          hipMalloc(&work, (size_t)nitems * 4) != hipSuccess || hipMalloc(&parts, (size_t)nitems * 4) != hipSuccess || hipMalloc(&epos, (size_t)nitems * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(ctx, SVR_E_STATE, "cell_prepare: out of device memory (item order)");
-        break;
-      }
-      hipLaunchKernelGGL(k_cell_item_work, dim3(nblk(nitems)), dim3(256), 0, ctx->stream, ca, NC, NH, nitems, order ? ctx->cell_order - 1 : 0, work, k1);
-      size_t tb4 = 0, tb5 = 0;
-      if (svr_sort_keys_u64(nullptr, &tb4, k1, k2, nitems, 64, ctx->stream) || svr_inclusive_sum_u32(nullptr, &tb5, parts, epos, nitems, ctx->stream)) { rc = fail(ctx, SVR_E_STATE, "cell_prepare: item sort (size query)"); break; }
-      tb4 = std::max(tb4, tb5);
-      if (tb4 > cs.cap_tmp) {
-        free_dev(cs.d_tmp); cs.cap_tmp = 0;
-        if (hipMalloc(&cs.d_tmp, tb4) != hipSuccess) { (void)hipGetLastError(); rc = fail(ctx, SVR_E_STATE, "cell_prepare: out of device memory (item order)"); break; }
-        cs.cap_tmp = tb4;
-      }
-      size_t tbs2 = cs.cap_tmp;
-      if (order && svr_sort_keys_u64(cs.d_tmp, &tbs2, k1, k2, nitems, 64, ctx->stream)) { rc = fail(ctx, SVR_E_STATE, "cell_prepare: item sort"); break; }
-      // the launch's work ~ every sorted pixel on the NS planes of its footprint; its fair share per wavefront slot / cell_balance
-      const double total = (double)cs.n_sorted * NS;
-      const uint32_t target = ctx->cell_balance > 0 ? (uint32_t)std::min(4.0e9, std::max(64.0, total / (1024.0 * ctx->cell_balance))) : 0u;
-      if (hipMemcpyAsync(it2, cs.d_items, (size_t)nitems * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = fail(ctx, SVR_E_STATE, "cell_prepare: copy"); break; }
-      hipLaunchKernelGGL(k_cell_items_reorder, dim3(nblk(nitems)), dim3(256), 0, ctx->stream, nitems, order ? k2 : (const uint64_t *)nullptr, it2, work, target, (uint32_t)ca.split, cs.d_items, parts);
-      tbs2 = cs.cap_tmp;
-      if (svr_inclusive_sum_u32(cs.d_tmp, &tbs2, parts, epos, nitems, ctx->stream)) { rc = fail(ctx, SVR_E_STATE, "cell_prepare: scan of the parts"); break; }
-      if (hipMemcpyAsync(&nents, epos + (nitems - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = fail(ctx, SVR_E_STATE, "cell_prepare: item order"); break; }
-      if (nents >= (1u << 28)) { if (getenv("SVR_TUNE_DEBUG")) fprintf(stderr, "[cell] %u entries: beyond item_of's 28 bits, fallback\n", nents); nents = 0; break; }
-      if (nents > cs.cap_ents) {
-        free_dev(cs.d_ents); cs.cap_ents = 0;
-        if (hipMalloc(&cs.d_ents, (size_t)nents * sizeof(uint4)) != hipSuccess) { (void)hipGetLastError(); rc = fail(ctx, SVR_E_STATE, "cell_prepare: out of device memory (entries)"); break; }
-        cs.cap_ents = nents;
-      }
-      hipLaunchKernelGGL(k_cell_entries, dim3(nblk(nitems)), dim3(256), 0, ctx->stream, ca, nitems, cs.d_items, parts, epos, cs.d_ents, cs.d_item_of);
-      if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = fail(ctx, SVR_E_STATE, "cell_prepare: entries"); break; }
-    } while (0);
-    drop();
-    if (rc) return rc;
+    if (k1.reserve(nitems) != hipSuccess || k2.reserve(nitems) != hipSuccess || it2.reserve(nitems) != hipSuccess ||
+        work.reserve(nitems) != hipSuccess || parts.reserve(nitems) != hipSuccess || epos.reserve(nitems) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, SVR_E_STATE, "cell_prepare: out of device memory (item order)");
+    }
+    hipLaunchKernelGGL(k_cell_item_work, dim3(nblk(nitems)), dim3(256), 0, ctx->stream, ca, NC, NH, nitems, order ? ctx->cell_order - 1 : 0, work, k1);
+    size_t tb4 = 0, tb5 = 0;
+    if (svr_sort_keys_u64(nullptr, &tb4, k1, k2, nitems, 64, ctx->stream) || svr_inclusive_sum_u32(nullptr, &tb5, parts, epos, nitems, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: item sort (size query)");
+    tb4 = std::max(tb4, tb5);
+    if (cs.d_tmp.reserve(tb4) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, SVR_E_STATE, "cell_prepare: out of device memory (item order)"); }
+    size_t tbs2 = cs.d_tmp.capacity();
+    if (order && svr_sort_keys_u64(cs.d_tmp, &tbs2, k1, k2, nitems, 64, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: item sort");
+    // the launch's work ~ every sorted pixel on the NS planes of its footprint; its fair share per wavefront slot / cell_balance
+    const double total = (double)cs.n_sorted * NS;
+    const uint32_t target = ctx->cell_balance > 0 ? (uint32_t)std::min(4.0e9, std::max(64.0, total / (1024.0 * ctx->cell_balance))) : 0u;
+    if (hipMemcpyAsync(it2, cs.d_items, (size_t)nitems * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return fail(ctx, SVR_E_STATE, "cell_prepare: copy");
+    hipLaunchKernelGGL(k_cell_items_reorder, dim3(nblk(nitems)), dim3(256), 0, ctx->stream, nitems, order ? k2 : (const uint64_t *)nullptr, it2, work, target, (uint32_t)ca.split, cs.d_items, parts);
+    tbs2 = cs.d_tmp.capacity();
+    if (svr_inclusive_sum_u32(cs.d_tmp, &tbs2, parts, epos, nitems, ctx->stream)) return fail(ctx, SVR_E_STATE, "cell_prepare: scan of the parts");
+    if (hipMemcpyAsync(&nents, epos + (nitems - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, SVR_E_STATE, "cell_prepare: item order");
+    if (nents >= (1u << 28)) { if (getenv("SVR_TUNE_DEBUG")) fprintf(stderr, "[cell] %u entries: beyond item_of's 28 bits, fallback\n", nents); cs.valid = true; return SVR_OK; }
+    if (cs.d_ents.reserve(nents) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, SVR_E_STATE, "cell_prepare: out of device memory (entries)"); }
+    hipLaunchKernelGGL(k_cell_entries, dim3(nblk(nitems)), dim3(256), 0, ctx->stream, ca, nitems, cs.d_items, parts, epos, cs.d_ents, cs.d_item_of);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, SVR_E_STATE, "cell_prepare: entries");
     if (!nents) { cs.valid = true; return SVR_OK; }         // (unusable: the atomic flush takes over)
     ca.ents = cs.d_ents; ca.nents = nents;
     mark("items by work, parts");
   }
   const size_t stage = need_stage ? (size_t)nents * ca.PP : 0;
-  if (stage > cs.cap_stage) {
-    free_dev(cs.d_stage);
-    cs.cap_stage = 0;
+  if (stage > cs.d_stage.capacity()) {
+    cs.d_stage.reset();
     size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || stage * sizeof(f2) + (size_t(1) << 30) > fr || hipMalloc(&cs.d_stage, stage * sizeof(f2)) != hipSuccess) {
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess || stage * sizeof(f2) + (size_t(1) << 30) > fr || cs.d_stage.reserve(stage) != hipSuccess) {
       (void)hipGetLastError();
-      cs.d_stage = nullptr;
       cs.valid = true;                                   // does not fit: the atomic flush takes over
       return SVR_OK;
     }
-    cs.cap_stage = stage;
   }
   mark("staging buffer");
   ca.stage = cs.d_stage;
@@ -1754,14 +1681,9 @@ int coeff_order(svr_ctx *ctx, uint32_t n_active, const uint32_t **list) {
   if (r) return r;
   if (!ctx->cell || !ctx->cell->usable || !ctx->cell->n_sorted) return SVR_OK;
   CellState &cs = *ctx->cell;
-  if (n_active > ctx->coeff_order_cap) {
-    free_dev(ctx->d_coeff_order);
-    ctx->coeff_order_cap = 0;
-    HIPCHK(hipMalloc(&ctx->d_coeff_order, (size_t)n_active * sizeof(uint32_t)));
-    ctx->coeff_order_cap = n_active;
-  }
-  unsigned char *mark = nullptr;
-  HIPCHK(hipMalloc(&mark, ctx->np));
+  HIPCHK(ctx->d_coeff_order.reserve(n_active));
+  DevBuf<unsigned char> mark;
+  HIPCHK(mark.reserve(ctx->np));
   HIPCHK(hipMemsetAsync(mark, 0, ctx->np, ctx->stream));
   hipLaunchKernelGGL(k_coeff_order_sorted, dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, cs.d_recs, cs.n_sorted, ctx->d_coeff_order, mark);
   KCHK("k_coeff_order_sorted");
@@ -1771,7 +1693,6 @@ int coeff_order(svr_ctx *ctx, uint32_t n_active, const uint32_t **list) {
     KCHK("k_coeff_order_rest");
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(mark);
   *list = ctx->d_coeff_order;
   return SVR_OK;
 }
@@ -1784,8 +1705,7 @@ __global__ void k_cell_pids(const CellRec *recs, uint32_t n, const uint32_t *coe
 int cell_pids(svr_ctx *ctx, CellState &cs, const PsfArgs &a, CellArgs &ca) {
   if (!a.coeff) return SVR_OK;
   if (!cs.pid_valid) {
-    int r;
-    if ((r = cell_grow(ctx, cs.d_pid, cs.cap_pid, (size_t)cs.n_sorted))) return r;
+    HIPCHK(cs.d_pid.reserve(cs.n_sorted));
     hipLaunchKernelGGL(k_cell_pids, dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, cs.d_recs, cs.n_sorted, a.coeff_id, cs.d_pid);
     KCHK("k_cell_pids");
     cs.pid_valid = true;
@@ -1802,8 +1722,7 @@ int launch_cell_scatter(svr_ctx *ctx, const PsfArgs &a, int gauss, float *out0, 
   const int NS = cs.ns_support, NC = (NS - 1) / 2, NH = NS - 1 - NC;
   { const int rp = cell_pids(ctx, cs, a, ca); if (rp) return rp; }
   if (store) {
-    const int rg = cell_grow(ctx, cs.d_act, cs.cap_act, (size_t)cs.n_sorted);
-    if (rg) return rg;
+    HIPCHK(cs.d_act.reserve(cs.n_sorted));
     ca.act = cs.d_act;
   }
   hipLaunchKernelGGL(k_cell_factors, dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, a, gauss, cs.d_recs, cs.n_sorted, store ? cs.d_act : (unsigned char *)nullptr);
@@ -1812,9 +1731,11 @@ int launch_cell_scatter(svr_ctx *ctx, const PsfArgs &a, int gauss, float *out0, 
   const dim3 block(64);
   ca.dbg = getenv("SVR_CELL_DBG") ? atoi(getenv("SVR_CELL_DBG")) : 0;
   const char *trace_file = getenv("SVR_CELL_TRACE");
-  if (trace_file) HIPCHK(hipMalloc(&ca.trace, (size_t)ca.nents * 3 * sizeof(unsigned long long)));
+  DevBuf<unsigned long long> trace, stats;
+  if (trace_file) { HIPCHK(trace.reserve((size_t)ca.nents * 3)); ca.trace = trace; }
   if (ca.dbg == 2) {
-    HIPCHK(hipMalloc(&ca.stats, 8 * sizeof(unsigned long long)));
+    HIPCHK(stats.reserve(8));
+    ca.stats = stats;
     HIPCHK(hipMemsetAsync(ca.stats, 0, 8 * sizeof(unsigned long long), ctx->stream));
   }
   {
@@ -1835,14 +1756,12 @@ int launch_cell_scatter(svr_ctx *ctx, const PsfArgs &a, int gauss, float *out0, 
     HIPCHK(hipMemcpyAsync(h.data(), ca.trace, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (FILE *f = fopen(trace_file, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
-    (void)hipFree(ca.trace);
   }
   if (ca.dbg == 2) {
     unsigned long long h[8];
     HIPCHK(hipMemcpyAsync(h, ca.stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     fprintf(stderr, "[cell stats] chunk visits %llu, with work %llu, sum of longest live lists %llu (ideal %llu), live units %llu, dead units %llu\n", h[0], h[1], h[2], (h[3] + 3) / 4, h[3], h[4]);
-    (void)hipFree(ca.stats);
   }
   {
     // covering cells per axis: a source coordinate lies in the boxes of floor((NS - 2 + C) / C) + 1 cells at most
@@ -1873,7 +1792,7 @@ int launch_cell_gauss1(svr_ctx *ctx, CellState &cs, const PsfArgs &a) {
   CellArgs ca = cs.a;
   const int NS = cs.ns_support;
   int r;
-  if ((r = cell_grow(ctx, cs.d_part, cs.cap_part, (size_t)cs.n_sorted * NS))) return r;
+  HIPCHK(cs.d_part.reserve((size_t)cs.n_sorted * NS));
   const size_t lds = (size_t)ca.PP * sizeof(f2);
   r = in_pieces(ca.nents, 64, [&](uint32_t off, uint32_t cnt) {
     if (ctx->pvr) hipLaunchKernelGGL((fwd_cell_kernel<PVR_N, true, 0, true>), dim3(cnt), dim3(64), lds, ctx->stream, a, ca, (const float *)nullptr, cs.d_part, (uint32_t)cs.n_sorted, off);
@@ -1882,7 +1801,7 @@ int launch_cell_gauss1(svr_ctx *ctx, CellState &cs, const PsfArgs &a) {
     return (int)SVR_OK;
   });
   if (r) return r;
-  const double *pd = reinterpret_cast<const double *>(cs.d_part);
+  const double *pd = reinterpret_cast<const double *>(cs.d_part.get());
   if (ctx->pvr) hipLaunchKernelGGL((k_cell_gauss1_finish<PVR_N, true>), dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, a, ca, cs.d_recs, pd, cs.n_sorted);
   else hipLaunchKernelGGL((k_cell_gauss1_finish<PSF_SUPPORT, false>), dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, a, ca, cs.d_recs, pd, cs.n_sorted);
   KCHK("k_cell_gauss1_finish");
@@ -1895,8 +1814,8 @@ int launch_cell_gather(svr_ctx *ctx, CellState &cs, const PsfArgs &a, bool store
   CellArgs ca = cs.a;
   const int NS = cs.ns_support;
   int r;
-  if ((r = cell_grow(ctx, cs.d_gf, cs.cap_gf, (size_t)cs.n_sorted))) return r;
-  if ((r = cell_grow(ctx, cs.d_part, cs.cap_part, (size_t)cs.n_sorted * NS))) return r;
+  HIPCHK(cs.d_gf.reserve(cs.n_sorted));
+  HIPCHK(cs.d_part.reserve((size_t)cs.n_sorted * NS));
   if ((r = cell_pids(ctx, cs, a, ca))) return r;
   if (!cs.gf_valid || a.flag) {                            // (1 / v_PSF_sums per sorted pixel: once per Gaussian pass, not once per SR iteration)
     hipLaunchKernelGGL(k_cell_gfactors, dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, a, cs.d_recs, cs.n_sorted, cs.d_gf);

@@ -128,17 +128,19 @@ int channel_scatter_run(svr_ctx *ctx, const float *channel, const unsigned char 
   if ((r = cell_prepare(ctx))) return r;
   if (!ctx->cell || !ctx->cell->usable)
     return fail(ctx, SVR_E_STATE, "svr_channel_scatter: the cell lists cannot hold this geometry, and channels have no fallback onto the atomic scatters");
-  HIPCHK(hipMalloc(&ctx->d_channel, ctx->np * sizeof(float)));
-  HIPCHK(hipMemcpyAsync(ctx->d_channel, channel, ctx->np * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  DevBuf<float> d_channel;                                  // the channel and its per-slice switches: nothing is kept beyond the call (the
+  DevBuf<unsigned char> d_unit_on;                          // coefficient table sizes itself by the memory that is free)
+  HIPCHK(d_channel.reserve(ctx->np));
+  HIPCHK(hipMemcpyAsync(d_channel, channel, ctx->np * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (unit_on) {
-    HIPCHK(hipMalloc(&ctx->d_unit_on, ctx->ns));
-    HIPCHK(hipMemcpyAsync(ctx->d_unit_on, unit_on, ctx->ns, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(d_unit_on.reserve(ctx->ns));
+    HIPCHK(hipMemcpyAsync(d_unit_on, unit_on, ctx->ns, hipMemcpyHostToDevice, ctx->stream));
   }
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
-  a.channel = ctx->d_channel;
-  a.unit_on = unit_on ? ctx->d_unit_on : nullptr;
+  a.channel = d_channel;
+  a.unit_on = d_unit_on;
   a.ch_flags = flags;
   a.ch_match = match;
   if (table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
@@ -164,9 +166,7 @@ int svr_channel_scatter(svr_ctx *ctx, const float *channel, const unsigned char 
   if (pass_path(ctx, PASS_BACK).family != FAM_CELLS)
     return fail(ctx, SVR_E_STATE, "svr_channel_scatter: needs the cell scatter (back_mode 5); channels have no fallback onto the atomic scatters");
   if (slice_weights && (r = svr_update_slice_weights(ctx, slice_weights))) return r;
-  r = channel_scatter_run(ctx, channel, unit_on, flags, match);
-  free_dev(ctx->d_channel); free_dev(ctx->d_unit_on);       // nothing is kept: the coefficient table sizes itself by the memory that is free
-  return r;
+  return channel_scatter_run(ctx, channel, unit_on, flags, match);
 }
 
 int svr_channel_finish(svr_ctx *ctx, float background, float *out_or_null) {
@@ -187,9 +187,9 @@ int svr_channel_vote(svr_ctx *ctx, float label, int first) {
   if (!ctx) return SVR_E_ARG;
   NEED(ctx->nv > 0, "reconstruction volume not initialised");
   if (first) {
-    free_dev(ctx->d_vote_best); free_dev(ctx->d_vote_label);
-    HIPCHK(hipMalloc(&ctx->d_vote_best, ctx->nv * sizeof(float)));
-    HIPCHK(hipMalloc(&ctx->d_vote_label, ctx->nv * sizeof(float)));
+    ctx->d_vote_best.reset(); ctx->d_vote_label.reset();
+    HIPCHK(ctx->d_vote_best.reserve(ctx->nv));
+    HIPCHK(ctx->d_vote_label.reserve(ctx->nv));
   }
   NEED(ctx->d_vote_best && ctx->d_vote_label, "no vote in flight (the first label's call says first = 1)");
   if (!same_16(ctx->addon(), ctx->d_vote_best) || !same_16(ctx->addon(), ctx->d_vote_label))
@@ -214,7 +214,7 @@ int svr_channel_vote_fetch(svr_ctx *ctx, float background_label, float *labels_o
   if (e == hipSuccess && confidence_or_null) e = hipMemcpyAsync(confidence_or_null, ctx->d_vote_best, ctx->nv * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) r = fail(ctx, (int)e, std::string("svr_channel_vote_fetch: ") + hipGetErrorString(e));
-  free_dev(ctx->d_vote_best); free_dev(ctx->d_vote_label); // the vote is over, whether the download worked or not
+  ctx->d_vote_best.reset(); ctx->d_vote_label.reset();     // the vote is over, whether the download worked or not
   return r;
 }
 

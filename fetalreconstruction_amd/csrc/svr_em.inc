@@ -36,25 +36,20 @@ struct SliceEm {
   int ns = 0, world = 1, rank = 0, maxn = 0;
   std::vector<int> rlo;                       // [world + 1] ranges of the host object's numbering
   std::vector<int> h_by_ref;                  // [ns] host index of the unit with reference index t
-  int *d_rlo = nullptr, *d_by_ref = nullptr;  // [world + 1]; [ns]: host index of the slice with reference index t
-  unsigned char *d_excl = nullptr;            // [ns] force-excluded (host numbering)
-  float *d_send = nullptr, *d_recv = nullptr; // [3][maxn]; [world][3][maxn]
-  float *d_pot = nullptr, *d_scale = nullptr, *d_w = nullptr, *d_inside = nullptr;   // [ns] global vectors, host numbering
-  float *d_raw = nullptr;                     // [ns] the potentials as the ranks sent them (patch form: d_pot takes them through d_src)
-  int *d_src = nullptr;                       // patch form: host index of the unit whose potential unit g reads, -1 = none (0); NULL = its own
+  DevBuf<int> d_rlo, d_by_ref;                // [world + 1]; [ns]: host index of the slice with reference index t
+  DevBuf<unsigned char> d_excl;               // [ns] force-excluded (host numbering)
+  DevBuf<float> d_send, d_recv;               // [3][maxn]; [world][3][maxn]
+  DevBuf<float> d_pot, d_scale, d_w, d_inside;   // [ns] global vectors, host numbering
+  DevBuf<float> d_raw;                        // [ns] the potentials as the ranks sent them (patch form: d_pot takes them through d_src)
+  DevBuf<int> d_src;                          // patch form: host index of the unit whose potential unit g reads, -1 = none (0); NULL = its own
   int patch_form = 0;                         // irtkPatchBasedReconstruction's EM: float Gaussian, the potentials through d_src
-  double *d_sc = nullptr;                     // {mean_s, mean_s2, sigma_s, sigma_s2, mix_s}
+  DevBuf<double> d_sc;                        // {mean_s, mean_s2, sigma_s, sigma_s2, mix_s}
   double step = 0.0001;
   bool ready = false;
 };
 
 void slice_em_invalidate(SliceEm *p) { if (p) p->ready = false; }   // svr_init_storage_volumes: new slice count, svr_slice_em_setup again
-void slice_em_free(SliceEm *p) {
-  if (!p) return;
-  free_dev(p->d_rlo); free_dev(p->d_by_ref); free_dev(p->d_excl); free_dev(p->d_send); free_dev(p->d_recv); free_dev(p->d_pot);
-  free_dev(p->d_scale); free_dev(p->d_w); free_dev(p->d_inside); free_dev(p->d_sc); free_dev(p->d_raw); free_dev(p->d_src);
-  delete p;
-}
+void slice_em_free(SliceEm *p) { delete p; }
 
 // the M-step's scalars with the previous {sigma, mix} read from device memory (k_mstep_scalars / k_mstep_scalars_ranks take them as arguments)
 __global__ void k_mstep_scalars_dev(const double *s5_or_all, int world, int iter, float step, int pvr, float *em) {
@@ -323,13 +318,9 @@ int svr_slice_em_setup(svr_ctx *ctx, int ns_global, int world, int rank, const i
   NEED(ctx->ns > 0, "initStorageVolumes first");
   if (rank_lo[0] != 0 || rank_lo[world] != ns_global || rank_lo[rank + 1] - rank_lo[rank] != (int)ctx->ns)
     return fail(ctx, SVR_E_ARG, "svr_slice_em_setup: the ranks' ranges do not match the engine's slices");
-  if (!ctx->sem) ctx->sem = new SliceEm();
-  SliceEm &p = *ctx->sem;
-  p.ready = false;
+  slice_em_free(ctx->sem);                              // a fresh object: the old buffers go before the new ones come
+  SliceEm &p = *(ctx->sem = new SliceEm());
   ctx->sem_weights_current = false;
-  free_dev(p.d_rlo); free_dev(p.d_by_ref); free_dev(p.d_excl); free_dev(p.d_send); free_dev(p.d_recv); free_dev(p.d_pot); free_dev(p.d_scale);
-  free_dev(p.d_w); free_dev(p.d_inside); free_dev(p.d_sc); free_dev(p.d_raw); free_dev(p.d_src);
-  p.patch_form = 0;
   p.ns = ns_global; p.world = world; p.rank = rank; p.step = step;
   p.rlo.assign(rank_lo, rank_lo + world + 1);
   p.maxn = 1;
@@ -349,17 +340,17 @@ int svr_slice_em_setup(svr_ctx *ctx, int ns_global, int world, int rank, const i
     }
   }
   const size_t n = (size_t)ns_global;
-  HIPCHK(hipMalloc(&p.d_rlo, (world + 1) * sizeof(int)));
-  HIPCHK(hipMalloc(&p.d_by_ref, n * sizeof(int)));
-  HIPCHK(hipMalloc(&p.d_excl, n));
-  HIPCHK(hipMalloc(&p.d_send, (size_t)3 * p.maxn * sizeof(float)));
-  HIPCHK(hipMalloc(&p.d_recv, (size_t)world * 3 * p.maxn * sizeof(float)));
-  HIPCHK(hipMalloc(&p.d_pot, n * sizeof(float)));
-  HIPCHK(hipMalloc(&p.d_scale, n * sizeof(float)));
-  HIPCHK(hipMalloc(&p.d_w, n * sizeof(float)));
-  HIPCHK(hipMalloc(&p.d_inside, n * sizeof(float)));
-  HIPCHK(hipMalloc(&p.d_sc, 8 * sizeof(double)));
-  HIPCHK(hipMalloc(&p.d_raw, n * sizeof(float)));
+  HIPCHK(p.d_rlo.reserve(world + 1));
+  HIPCHK(p.d_by_ref.reserve(n));
+  HIPCHK(p.d_excl.reserve(n));
+  HIPCHK(p.d_send.reserve((size_t)3 * p.maxn));
+  HIPCHK(p.d_recv.reserve((size_t)world * 3 * p.maxn));
+  HIPCHK(p.d_pot.reserve(n));
+  HIPCHK(p.d_scale.reserve(n));
+  HIPCHK(p.d_w.reserve(n));
+  HIPCHK(p.d_inside.reserve(n));
+  HIPCHK(p.d_sc.reserve(8));
+  HIPCHK(p.d_raw.reserve(n));
   p.h_by_ref = by_ref;
   HIPCHK(hipMemcpyAsync(p.d_rlo, p.rlo.data(), (world + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(p.d_by_ref, by_ref.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -368,7 +359,7 @@ int svr_slice_em_setup(svr_ctx *ctx, int ns_global, int world, int rank, const i
   HIPCHK(hipMemsetAsync(p.d_scale, 0, n * sizeof(float), ctx->stream));
   HIPCHK(hipMemsetAsync(p.d_inside, 0, n * sizeof(float), ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));            // (by_ref is this function's memory)
-  if (!ctx->d_em) HIPCHK(hipMalloc(&ctx->d_em, 4 * sizeof(float)));
+  HIPCHK(ctx->d_em.reserve(4));
   p.ready = true;
   return SVR_OK;
 }
@@ -382,7 +373,7 @@ int svr_slice_em_set_patch_form(svr_ctx *ctx, const int *source_ref_or_null) {
   NEED(ctx->sem && ctx->sem->ready, "svr_slice_em_setup first");
   SliceEm &p = *ctx->sem;
   p.patch_form = 1;
-  free_dev(p.d_src);
+  p.d_src.reset();
   if (!source_ref_or_null) return SVR_OK;
   std::vector<int> src((size_t)p.ns, -1);
   for (int t = 0; t < p.ns; ++t) {
@@ -390,7 +381,7 @@ int svr_slice_em_set_patch_form(svr_ctx *ctx, const int *source_ref_or_null) {
     if (u >= p.ns) return fail(ctx, SVR_E_ARG, "svr_slice_em_set_patch_form: source out of range");
     src[p.h_by_ref[t]] = u < 0 ? -1 : p.h_by_ref[u];
   }
-  HIPCHK(hipMalloc(&p.d_src, (size_t)p.ns * sizeof(int)));
+  HIPCHK(p.d_src.reserve((size_t)p.ns));
   HIPCHK(hipMemcpyAsync(p.d_src, src.data(), (size_t)p.ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
@@ -421,7 +412,7 @@ int svr_mstep_estep_device(svr_ctx *ctx, int iter, float step, void **send, void
   int r;
   if (iter > 0) {
     if (p.world > 1) {
-      NEED(ctx->d_em_all && (size_t)p.world <= ctx->em_all_cap, "svr_mstep_partial + the launcher's all-gather first");
+      NEED((size_t)p.world * 8 <= ctx->d_em_all.capacity(), "svr_mstep_partial + the launcher's all-gather first");
       hipLaunchKernelGGL(k_mstep_scalars_dev, dim3(1), dim3(1), 0, ctx->stream, ctx->d_em_all, p.world, iter, step, ctx->pvr ? 1 : 0, ctx->d_em);
     } else {
       // (round 6: k_mstep, then ONE workgroup for the chunk sums, the slice sums and the scalars: k_mstep_finish)

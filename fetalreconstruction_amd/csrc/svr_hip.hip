@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/svr_hip.h"
+#include "svr_devbuf.h"
 
 // csrc/svr_sort.hip: radix sort / prefix sum of the vendor's primitives library for the work lists of svr_cell.inc
 int svr_sort_keys_u64(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, size_t n, int end_bit, hipStream_t stream);
@@ -1071,36 +1072,33 @@ struct svr_ctx {
   uint32_t vx = 0, vy = 0, vz = 0;
   float vdim[3] = {1, 1, 1};
   size_t nv = 0;
-  float *d_recon_volw = nullptr;   // recon | volw
-  float *d_addon_cmap = nullptr;   // addon | cmap
-  float *d_mask = nullptr, *d_snap = nullptr, *d_recon_new = nullptr;
-  float *recon_cur = nullptr;   // the volume: d_recon_volw or d_recon_new (the fused volume update writes the other one, svr_regul.inc)
+  DevBuf<float> d_recon_volw;   // recon | volw
+  DevBuf<float> d_addon_cmap;   // addon | cmap
+  DevBuf<float> d_mask, d_snap, d_recon_new;
+  float *recon_cur = nullptr;   // (alias) the volume: d_recon_volw or d_recon_new (the fused volume update writes the other one, svr_regul.inc)
   int reg_tile = -1;            // k_regul_fused's tile: -1 = by the volume's extent, 0 = 64 x 8, 1 = 32 x 16, 2 = 32 x 8
   int reg_mode = 1;             // volume update: 1 = k_regul_fused (one kernel, LDS planes, float32 weights), 0 = k_reg_prep + k_regularize (fp64 weights)
   bool prep_pending = false;    // reg_mode 1, non-adaptive: Prep's own changes of addon / cmap are applied when somebody reads the buffers
   bool cmap_from_scatter = false;   // cmap is what the scatter wrote (zero outside the mask): the update skips tiles outside the mask's box
-  float2 *d_volm = nullptr;   // {V m, m}, refreshed before every SVR forward projection
+  DevBuf<float2> d_volm;   // {V m, m}, refreshed before every SVR forward projection
   bool have_mask = false;
   // bounding box of mask != 0 (inclusive), from the host copy handed to svr_set_mask: the scatter only ever writes mask voxels,
   // so a sharded run need not all-reduce the rest of a volume pair (svr_pair_pack / svr_pair_unpack)
   int mbox_lo[3] = {0, 0, 0}, mbox_hi[3] = {-1, -1, -1};
   bool mbox_valid = false;
-  float *d_pair_pack = nullptr;
-  size_t pair_pack_cap = 0;
+  DevBuf<float> d_pair_pack;
 
   // slice grid
   uint32_t sx = 0, sy = 0, ns = 0;
   size_t np = 0;
-  float *d_slices = nullptr, *d_weights = nullptr, *d_simslices = nullptr, *d_simweights = nullptr,
-        *d_psf_sums = nullptr;
-  unsigned char *d_siminside = nullptr;
-  int *d_voxcount = nullptr;
+  DevBuf<float> d_slices, d_weights, d_simslices, d_simweights, d_psf_sums;
+  DevBuf<unsigned char> d_siminside;
+  DevBuf<int> d_voxcount;
   bool have_slices = false;
   bool have_sim = false;                // d_simslices / d_simweights hold a forward projection (svr_simulate_slices, or a test's svr_debug_set)
   bool sem_weights_current = false;     // d_slice_weights holds the device-side EM's weights (svr_slice_em_run) and nobody has written it since
-  float *d_scales = nullptr, *d_slice_weights = nullptr, *d_scales_host_copy = nullptr,
-        *d_tmp_ns = nullptr;
-  unsigned char *d_slice_inside = nullptr;
+  DevBuf<float> d_scales, d_slice_weights, d_scales_host_copy, d_tmp_ns;
+  DevBuf<unsigned char> d_slice_inside;
   std::vector<float> h_slice_weights;             // RC.cu:1346.  h_scales (RC.cu:1345) lives on the device: d_scales_host_copy
   bool have_scales = false;
   // per-slice vectors go up through pinned slots without a stream synchronisation (upload_ns); what each device vector holds
@@ -1118,7 +1116,7 @@ struct svr_ctx {
   size_t down_cap = 0, down_used = 0;
   struct DownItem { void *dst; size_t off, bytes; };
   std::vector<DownItem> down_items;
-  float *d_em = nullptr;                          // {sigma, mix, m} of the fused M-step + E-step (svr_mstep_estep)
+  DevBuf<float> d_em;                             // {sigma, mix, m} of the fused M-step + E-step (svr_mstep_estep)
 
   // geometry
   std::vector<float> slice_dims;   // ns*3
@@ -1128,11 +1126,10 @@ struct svr_ctx {
   float psf_c0[3] = {0, 0, 0};
   float quality_factor = 1.0f;
   bool have_dims = false, have_mats = false, have_psf = false, sc_dirty = true;
-  SliceConst *d_sc = nullptr;
+  DevBuf<SliceConst> d_sc;
 
   // work lists
-  uint32_t *d_active = nullptr, *d_psf_list = nullptr, *d_counter = nullptr, *d_tiles = nullptr,
-           *d_tiles_fb = nullptr;
+  DevBuf<uint32_t> d_active, d_psf_list, d_counter, d_tiles, d_tiles_fb;
   uint32_t n_active = 0, n_psf = 0, n_tiles = 0;
   int tiles_x = 0, tiles_y = 0, tile_w = 4, tile_h = 4;
   int reg_blind = 4;        // GPU slice-to-volume registration: line-search steps per host round trip, the active count on the device (0: a round trip per step)
@@ -1140,11 +1137,10 @@ struct svr_ctx {
   int reg_batch = 1;        // GPU slice-to-volume registration: the twelve evaluations of a gradient as one launch sequence (0: one by one)
   int pvr_reg_levels = 3, pvr_reg_steps = 4, pvr_reg_iterations = 20;   // PatchBased2D3DRegistration_gpu2 schedule (tests shorten it)
   bool psf_list_valid = false;
-  unsigned char *d_gauss_flag = nullptr;   // pixels whose sume passed in the current Gaussian pass
-  uint32_t *d_tiles_tmp = nullptr;         // tile list of the Gaussian passes
-  size_t tiles_tmp_cap = 0;                // its capacity in tiles (the tile shapes can change between calls)
+  DevBuf<unsigned char> d_gauss_flag;      // pixels whose sume passed in the current Gaussian pass
+  DevBuf<uint32_t> d_tiles_tmp;            // tile list of the Gaussian passes (grows: the tile shapes can change between calls)
   int gauss_mode = 1;                      // 1 = unit-based pass 1 (fwd_unit_kernel<GAUSS1>) + the LDS scatter, 0 = psf_kernel<MODE_GAUSS>
-  uint32_t *d_tiles_fwd = nullptr;   // tiles of fwd_tw x fwd_th pixels for fwd_unit_kernel
+  DevBuf<uint32_t> d_tiles_fwd;      // tiles of fwd_tw x fwd_th pixels for fwd_unit_kernel
   uint32_t n_tiles_fwd = 0;
   bool tiles_back_valid = false, tiles_fwd_valid = false;   // the tile lists belong to the current PSF list (ensure_tiles_back / ensure_tiles_fwd)
   int fwd_tw = 4, fwd_th = 4, fwd_tiles_x = 0, fwd_tiles_y = 0;
@@ -1157,7 +1153,7 @@ struct svr_ctx {
   bool fwd_tile_user = false, tile_user = false;
   int pvr = 0;              // 1: patch-to-volume constants and kernels (svr_set_option "pvr")
   int pvr_mode = 1;         // PVR kernels: 1 = the unit-based gather / wave-owned scatter with support 12, 0 = wave-per-pixel (pvr_kernel)
-  unsigned char *d_spx = nullptr;
+  DevBuf<unsigned char> d_spx;
   int back_mode = 5;        // 5 = cell-owned planes, staged and combined in a fixed order: no atomics (svr_cell.inc; the default for SVR on the fly --
                             // patch-based runs and the coefficient table take 4 unless the mode was set explicitly),
                             // 4 = wave-owned LDS planes (back_wave_kernel), 3 = the workgroup kernel for every tile (back_slot_kernel<8>),
@@ -1174,7 +1170,7 @@ struct svr_ctx {
   void note_fallback(int kind, const char *what) {
     if (!fallbacks[kind]++) fprintf(stderr, "svr: %s -- counted in svr_fallbacks()[%d]\n", what, kind);
   }
-  uint32_t *d_tiles_fb2 = nullptr;
+  DevBuf<uint32_t> d_tiles_fb2;
   bool wave_cap_user = false;
   bool back_mode_user = false;   // svr_set_option("back_mode") was called: no automatic choice between 5 and 4
   bool fwd_mode_user = false;    // likewise "fwd_mode"
@@ -1184,11 +1180,9 @@ struct svr_ctx {
   // the COEFF instantiations of the scatter and the gather instead of being re-evaluated in every SR iteration.  The
   // reference's GPU path recomputes them (a 2015 GPU had 6-12 GB); 288 GB of HBM hold them for every workload of
   // BASELINE.json (P4: 19 GB, S8: 174 GB).  Values are bit-identical to the on-the-fly evaluation by construction.
-  float4 *d_coeff = nullptr;
-  uint32_t *d_coeff_id = nullptr;
-  uint32_t *d_coeff_order = nullptr;   // the active pixels in the order of their places in the table (coeff_order)
-  size_t coeff_order_cap = 0;
-  size_t coeff_cap = 0;        // pixels the allocation holds
+  DevBuf<float4> d_coeff;
+  DevBuf<uint32_t> d_coeff_id;
+  DevBuf<uint32_t> d_coeff_order;   // the active pixels in the order of their places in the table (coeff_order)
   CoeffState coeff_state = COEFF_NONE;   // (table_holds)
   int coeff_mode = 1;          // option "coeff_table": 0 = evaluate on the fly, 1 = stream the table (falls back to 0 if it does not fit).  Round 6: ON by
                                // default for slice-to-volume runs (written by the first gather of the SR iterations, coeff_lazy: P4 +7 %, S8 +5 % with one
@@ -1197,20 +1191,19 @@ struct svr_ctx {
   bool coeff_user = false;     // svr_set_option("coeff_table") was called: the "pvr" option leaves the mode alone
   int coeff_lazy = 1;          // option "coeff_lazy" (round 6): 1 = the table is written by the first gather of the SR iterations after a new slice geometry
                                // (fwd_cell_kernel<.., 3>: the evaluation that pass needs anyway) instead of by k_coeff_build; passes before it evaluate
-  const uint32_t *coeff_list = nullptr;   // the active pixels in table order (d_coeff_order, or d_active), while coeff_ids_valid
+  const uint32_t *coeff_list = nullptr;   // (alias) the active pixels in table order (d_coeff_order, or d_active), while coeff_ids_valid
   bool coeff_ids_valid = false;   // d_coeff_order / d_coeff_id match the current cell lists (dropped with them): a table thrown away without a new
                                   // geometry (svr_set_option coeff_invalidate) keeps its pixels' places
   int wave_groups = 1, wave_cap = 2096;      // back_wave_kernel: wavefronts per tile, box voxels of a wavefront's four planes (14 LDS granules of 1280 B with the static part: 9 wavefronts per CU)
 
   // reductions
-  double *d_partial = nullptr, *d_per_slice = nullptr, *d_out = nullptr;
-  double *d_em_all = nullptr;       // [world][8]: every rank's M-step sums (svr_mstep_partial / svr_mstep_estep_ranks)
-  size_t em_all_cap = 0;
+  DevBuf<double> d_partial, d_per_slice, d_out;
+  DevBuf<double> d_em_all;          // [world][8]: every rank's M-step sums (svr_mstep_partial / svr_mstep_estep_ranks)
   int chunks = 0;
 
   // bias correction (allocated only when bias correction is enabled)
-  float *d_bias = nullptr, *d_wb = nullptr, *d_wr = nullptr, *d_buffer = nullptr;       // slice grid
-  float *d_bias_vol = nullptr, *d_volume_weights = nullptr, *d_maskC = nullptr, *d_mbuf = nullptr;   // volume
+  DevBuf<float> d_bias, d_wb, d_wr, d_buffer;                        // slice grid
+  DevBuf<float> d_bias_vol, d_volume_weights, d_maskC, d_mbuf;       // volume
   float mask_sigma_bias = 12.0f;
   // option "bias_mode": 1 (default) = NormaliseBias scatters on the cell kernels, CorrectBias on the LDS kernel of svr_bias.inc, the NormaliseBias
   // tail on its LDS kernels from BIAS_LDS_TAIL_MIN voxels on (below, the stencils are as fast: P4 0.18 vs 0.20 ms); 2 = the same with the LDS
@@ -1227,29 +1220,17 @@ struct svr_ctx {
   bool maskC_valid = false;
 
   // registration cost (NCC)
-  short *d_reg_targets = nullptr, *d_reg_source = nullptr;
-  short *d_pyr_full[2] = {nullptr, nullptr}, *d_pyr_a = nullptr, *d_pyr_b = nullptr;   // device pyramid of the registration (svr_pyr_*)
-  size_t pyr_full_cap[2] = {0, 0}, pyr_work_cap = 0;
-  void *d_pyr_meta = nullptr;
-  size_t pyr_meta_cap = 0;
-  unsigned char *d_sim_io = nullptr;     // grow-only arena of svr_ncc / svr_nmi / svr_lncc_evaluate (sim_evaluate, svr_sim.inc): inputs | outputs | test map
-  size_t sim_cap = 0;
+  DevBuf<short> d_reg_targets, d_reg_source;
+  DevBuf<short> d_pyr_full[2], d_pyr_a, d_pyr_b;   // device pyramid of the registration (svr_pyr_*)
+  DevBuf<unsigned char> d_pyr_meta;
+  DevBuf<unsigned char> d_sim_io;        // grow-only arena of svr_ncc / svr_nmi / svr_lncc_evaluate (sim_evaluate, svr_sim.inc): inputs | outputs | test map
   std::vector<unsigned char> sim_staging;
-  double *d_nmi_terms = nullptr;         // c log c for c = 0 .. nmi_terms_n - 1, from the host's libm
+  DevBuf<double> d_nmi_terms;            // c log c for c = 0 .. nmi_terms_n - 1, from the host's libm
   size_t nmi_terms_n = 0;
-  unsigned *d_nmi_merge = nullptr;       // merge slots of split evaluations + their counters, all zero between calls
+  DevBuf<unsigned> d_nmi_merge;          // merge slots of split evaluations + their counters, all zero between calls
   size_t nmi_slots = 0;
-  float *d_mot_x = nullptr;              // svr_stack_motion (svr_motion.inc): the slices, the chunks' partial Gram matrices and their sum;
-  double *d_mot_partial = nullptr, *d_mot_g = nullptr;   // allocated by a call and freed before it returns
-  double *d_qual_partial = nullptr, *d_qual_sums = nullptr;   // svr_slice_quality (svr_quality.inc): likewise
-  double *d_ssim_partial = nullptr, *d_ssim_sums = nullptr;   // svr_slice_ssim (svr_ssim.inc): likewise
-  float *d_ssim_map = nullptr;
-  float *d_channel = nullptr;            // svr_channel_scatter (svr_channel.inc): the channel and its per-slice switches, likewise freed before the call returns
-  unsigned char *d_unit_on = nullptr;
-  float *d_vote_best = nullptr, *d_vote_label = nullptr;      // svr_channel_vote: the running maximum and its label, [nv] each, from the first vote to svr_channel_vote_fetch
+  DevBuf<float> d_vote_best, d_vote_label;                    // svr_channel_vote: the running maximum and its label, [nv] each, from the first vote to svr_channel_vote_fetch
   bool have_em = false;                  // d_weights hold EM posteriors (svr_initialize_em_values or a later E-step; a test's svr_debug_set)
-  float *d_seed_src = nullptr, *d_seed_out = nullptr;          // svr_resample_to_reconstruction (svr_seed.inc): likewise
-  double *d_seed_partial = nullptr;
   int last_quality_chunks = -1;          // chunks per slice of the last svr_slice_quality (read-only option "quality_chunks"; -1 = not launched yet)
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
   uint32_t reg_vx = 0, reg_vy = 0, reg_vz = 0;
@@ -1263,8 +1244,7 @@ struct svr_ctx {
   bool vol_clean[2] = {false, false};   // d_recon_volw / d_recon_new known to be zero outside the dilated mask (svr_slab.inc)
   CellState *cell = nullptr;      // the scatter's cell lists
   CellState *cell_g = nullptr;    // the gather's, when it works on another cell size (cell_prepare_gather)
-  int *d_cellc = nullptr;         // centre voxel + class of every active pixel (k_cell_centres), shared by the two
-  size_t cellc_cap = 0;
+  DevBuf<int> d_cellc;            // centre voxel + class of every active pixel (k_cell_centres), shared by the two
   uint32_t cellc_n = 0;
   bool cellc_valid = false;
   int cellc_range[16] = {0};
@@ -1325,10 +1305,8 @@ void reg_free(RegState *r);
 void cell_free(CellState *c);
 
 // The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
-// of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  The buffers of
-// svr_stack_motion (svr_motion.inc) cache nothing between calls -- they are freed before the call returns -- and have no line there;
-// nor have those of svr_slice_quality (svr_quality.inc), svr_slice_ssim (svr_ssim.inc) and svr_resample_to_reconstruction (svr_seed.inc), nor the channel buffer of
-// svr_channel_scatter (svr_channel.inc); the vote arrays of svr_channel_vote live from the first vote to the fetch and have one.
+// of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  Buffers that
+// live for one call are locals of their entry point; the vote arrays of svr_channel_vote live from the first vote to the fetch and have a line.
 enum Change : unsigned {
   CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
   CH_TAPS = 1u << 1,              // new slice constants, generatePSFVolume: the table and the cell lists
@@ -1346,12 +1324,6 @@ enum Change : unsigned {
   CH_TABLE_IDS = 1u << 13,        // the pixels got new places in the table: the records' table ids
 };
 void invalidate(svr_ctx *ctx, unsigned changes);
-
-template <class T>
-void free_dev(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
 
 constexpr size_t TIMER_BATCH = 256;
 inline hipEvent_t timer_event(svr_ctx *c) {
@@ -1408,32 +1380,32 @@ inline unsigned nblk(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1)
 
 void free_volume(svr_ctx *c) {
   c->recon_cur = nullptr;
-  free_dev(c->d_recon_volw);
-  free_dev(c->d_addon_cmap);
-  free_dev(c->d_snap);
-  free_dev(c->d_recon_new);
-  free_dev(c->d_volm);
+  c->d_recon_volw.reset();
+  c->d_addon_cmap.reset();
+  c->d_snap.reset();
+  c->d_recon_new.reset();
+  c->d_volm.reset();
 }
 void free_slices(svr_ctx *c) {
-  free_dev(c->d_slices); free_dev(c->d_weights); free_dev(c->d_simslices); free_dev(c->d_simweights);
-  free_dev(c->d_psf_sums); free_dev(c->d_siminside); free_dev(c->d_voxcount); free_dev(c->d_scales);
-  free_dev(c->d_slice_weights); free_dev(c->d_scales_host_copy); free_dev(c->d_tmp_ns);
+  c->d_slices.reset(); c->d_weights.reset(); c->d_simslices.reset(); c->d_simweights.reset();
+  c->d_psf_sums.reset(); c->d_siminside.reset(); c->d_voxcount.reset(); c->d_scales.reset();
+  c->d_slice_weights.reset(); c->d_scales_host_copy.reset(); c->d_tmp_ns.reset();
   c->mir_scales.clear(); c->mir_slice_weights.clear(); c->mir_scales_copy.clear();
   if (c->h_up) { (void)hipStreamSynchronize(c->stream); (void)hipHostFree(c->h_up); c->h_up = nullptr; }
   if (c->h_down) { (void)hipStreamSynchronize(c->stream); (void)hipHostFree(c->h_down); c->h_down = nullptr; c->down_cap = c->down_used = 0; c->down_items.clear(); }
-  free_dev(c->d_em);
+  c->d_em.reset();
   for (int k = 0; k < svr_ctx::UP_SLOTS; ++k) {
     if (c->up_ev[k]) { (void)hipEventDestroy(c->up_ev[k]); c->up_ev[k] = nullptr; }
     c->up_busy[k] = false;
   }
-  free_dev(c->d_slice_inside); free_dev(c->d_sc); free_dev(c->d_active); free_dev(c->d_psf_list);
-  free_dev(c->d_tiles);
-  free_dev(c->d_tiles_fwd);
-  free_dev(c->d_gauss_flag);
-  free_dev(c->d_tiles_tmp);
-  free_dev(c->d_tiles_fb);
-  free_dev(c->d_tiles_fb2);
-  free_dev(c->d_partial); free_dev(c->d_per_slice);
+  c->d_slice_inside.reset(); c->d_sc.reset(); c->d_active.reset(); c->d_psf_list.reset();
+  c->d_tiles.reset();
+  c->d_tiles_fwd.reset();
+  c->d_gauss_flag.reset();
+  c->d_tiles_tmp.reset();
+  c->d_tiles_fb.reset();
+  c->d_tiles_fb2.reset();
+  c->d_partial.reset(); c->d_per_slice.reset();
 }
 
 // builds the per-slice constants (host float math, literal order) and uploads them
@@ -1556,11 +1528,11 @@ int ensure_tiles_fwd(svr_ctx *ctx) {
   int r = ensure_psf_list(ctx);
   if (r || ctx->tiles_fwd_valid) return r;
   uint32_t n = 0;
-  free_dev(ctx->d_tiles_fwd);
+  ctx->d_tiles_fwd.reset();
   ctx->fwd_tiles_x = (int)((ctx->sx + ctx->fwd_tw - 1) / ctx->fwd_tw);
   ctx->fwd_tiles_y = (int)((ctx->sy + ctx->fwd_th - 1) / ctx->fwd_th);
   const uint32_t total_f = (uint32_t)ctx->fwd_tiles_x * ctx->fwd_tiles_y * ctx->ns;
-  HIPCHK(hipMalloc(&ctx->d_tiles_fwd, (size_t)total_f * sizeof(uint32_t)));
+  HIPCHK(ctx->d_tiles_fwd.reserve((size_t)total_f));
   HIPCHK(hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
   if ((r = build_tile_list(ctx, ctx->d_psf_sums, nullptr, ctx->fwd_tiles_x, ctx->fwd_tiles_y, ctx->fwd_tw, ctx->fwd_th, ctx->d_tiles_fwd, ctx->d_counter))) return r;
   HIPCHK(hipMemcpyAsync(&n, ctx->d_counter, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
@@ -1601,8 +1573,8 @@ int ensure_bias_buffers(svr_ctx *ctx) {
   if (ctx->disable_bias) return SVR_OK;
   if (ctx->np && !ctx->d_bias) {
     const size_t fb = ctx->np * sizeof(float);
-    HIPCHK(hipMalloc(&ctx->d_bias, fb)); HIPCHK(hipMalloc(&ctx->d_wb, fb));
-    HIPCHK(hipMalloc(&ctx->d_wr, fb)); HIPCHK(hipMalloc(&ctx->d_buffer, fb));
+    HIPCHK(ctx->d_bias.reserve(ctx->np)); HIPCHK(ctx->d_wb.reserve(ctx->np));
+    HIPCHK(ctx->d_wr.reserve(ctx->np)); HIPCHK(ctx->d_buffer.reserve(ctx->np));
     HIPCHK(hipMemsetAsync(ctx->d_bias, 0, fb, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_wb, 0, fb, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_wr, 0, fb, ctx->stream));
@@ -1610,8 +1582,8 @@ int ensure_bias_buffers(svr_ctx *ctx) {
   }
   if (ctx->nv && !ctx->d_bias_vol) {
     const size_t vb = ctx->nv * sizeof(float);
-    HIPCHK(hipMalloc(&ctx->d_bias_vol, vb)); HIPCHK(hipMalloc(&ctx->d_volume_weights, vb));
-    HIPCHK(hipMalloc(&ctx->d_maskC, vb)); HIPCHK(hipMalloc(&ctx->d_mbuf, vb));
+    HIPCHK(ctx->d_bias_vol.reserve(ctx->nv)); HIPCHK(ctx->d_volume_weights.reserve(ctx->nv));
+    HIPCHK(ctx->d_maskC.reserve(ctx->nv)); HIPCHK(ctx->d_mbuf.reserve(ctx->nv));
     HIPCHK(hipMemsetAsync(ctx->d_bias_vol, 0, vb, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_volume_weights, 0, vb, ctx->stream));
   }
@@ -1696,24 +1668,21 @@ bool table_holds(const svr_ctx *ctx, CoeffState need) { return ctx->coeff_mode &
 int coeff_prepare(svr_ctx *ctx, const uint32_t **list) {
   // every pixel with s != -1: the Gaussian pass walks them all, the PSF pixels of the SR iterations are a subset
   const size_t npx = ctx->n_active;
-  if (npx > ctx->coeff_cap) {
-    free_dev(ctx->d_coeff);
-    ctx->coeff_cap = 0;
+  const size_t bytes = npx * (ctx->pvr ? CoeffLayout<PVR_N>::PIXEL_BYTES : CoeffLayout<PSF_SUPPORT>::PIXEL_BYTES);   // (whole float4s)
+  if (bytes / sizeof(float4) > ctx->d_coeff.capacity()) {      // more pixels than the allocation holds (one layout per allocation: the "pvr" option raises CH_TABLE_OFF)
+    ctx->d_coeff.reset();
     size_t fr = 0, tot = 0;
-    const size_t bytes = npx * (ctx->pvr ? CoeffLayout<PVR_N>::PIXEL_BYTES : CoeffLayout<PSF_SUPPORT>::PIXEL_BYTES);
     const char *cap_gb = getenv("SVR_COEFF_MAX_GB");     // optional ceiling on the table (GiB): a deployment knob, and how the tests reach the fallback
     const bool over = cap_gb && (double)bytes > atof(cap_gb) * 1073741824.0;
     // the bias buffers are allocated before the first pass (svr_set_flags / ready); any still missing count in the headroom
     const size_t bias_later = ctx->disable_bias ? 0 : (ctx->d_bias ? 0 : 4 * ctx->np * sizeof(float)) + (ctx->d_bias_vol ? 0 : 4 * ctx->nv * sizeof(float));
-    if (over || hipMemGetInfo(&fr, &tot) != hipSuccess || bytes + bias_later + (size_t(2) << 30) > fr || hipMalloc(&ctx->d_coeff, bytes) != hipSuccess) {
+    if (over || hipMemGetInfo(&fr, &tot) != hipSuccess || bytes + bias_later + (size_t(2) << 30) > fr || ctx->d_coeff.reserve(bytes / sizeof(float4)) != hipSuccess) {
       (void)hipGetLastError();
-      ctx->d_coeff = nullptr;
       ctx->coeff_mode = 0;                                 // does not fit: evaluate on the fly (svr_get_option tells)
       return SVR_OK;
     }
-    ctx->coeff_cap = npx;
   }
-  if (!ctx->d_coeff_id) HIPCHK(hipMalloc(&ctx->d_coeff_id, ctx->np * sizeof(uint32_t)));   // (freed by svr_init_storage_volumes, whose changes drop the ids)
+  HIPCHK(ctx->d_coeff_id.reserve(ctx->np));   // (freed by svr_init_storage_volumes, whose changes drop the ids)
   if (ctx->coeff_ids_valid && ctx->coeff_list) { *list = ctx->coeff_list; return SVR_OK; }
   *list = ctx->d_active;
   // The pixels get their places in the table in the order of the scatter's cell lists (cell, slice, band, position): what a
@@ -1874,7 +1843,7 @@ void invalidate(svr_ctx *ctx, unsigned ch) {
   if (ch & (CH_SLICE_PIXELS | CH_PSF_SUMS | CH_TILE_SHAPE)) ctx->psf_list_valid = false;
   if (ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_TABLE | CH_TABLE_OFF)) ctx->coeff_state = COEFF_NONE;
   if ((ch & CH_PSF_SUMS) && ctx->coeff_state == COEFF_PSF) ctx->coeff_state = COEFF_NONE;
-  if (ch & CH_TABLE_OFF) { free_dev(ctx->d_coeff); ctx->coeff_cap = 0; }
+  if (ch & CH_TABLE_OFF) ctx->d_coeff.reset();
   const bool cells = ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_CELL_SHAPE | CH_TABLE_OFF);
   if (cells) ctx->cellc_valid = ctx->coeff_ids_valid = false;   // (the pixels' places in the table follow the scatter's lists)
   for (CellState *cs : {ctx->cell, ctx->cell_g}) {
@@ -1888,7 +1857,7 @@ void invalidate(svr_ctx *ctx, unsigned ch) {
   if (ch & (CH_VOLUME_GRID | CH_MASK_BLUR)) ctx->maskC_valid = false;
   if (ch & CH_VOLUME_VALUES) ctx->vol_clean[ctx->recon_cur == ctx->d_recon_new ? 1 : 0] = false;
   if (ch & (CH_VOLUME_GRID | CH_SCATTER_TARGETS)) ctx->cmap_from_scatter = false;
-  if (ch & CH_VOLUME_GRID) { free_dev(ctx->d_vote_best); free_dev(ctx->d_vote_label); }   // (a vote in flight was over the old grid)
+  if (ch & CH_VOLUME_GRID) { ctx->d_vote_best.reset(); ctx->d_vote_label.reset(); }   // (a vote in flight was over the old grid)
 }
 
 // The tile shape of the unit gather (fwd_unit_kernel: fwd_mode 1, and the coefficient table's gather) from the geometry, not from a
@@ -1914,13 +1883,13 @@ void tile_shape_rule(const svr_ctx *ctx, bool table, int &w, int &h) {
 int set_scatter_tile(svr_ctx *ctx, int w, int h) {
   ctx->tile_w = w; ctx->tile_h = h;
   if (!ctx->np) return SVR_OK;
-  free_dev(ctx->d_tiles); free_dev(ctx->d_tiles_fb); free_dev(ctx->d_tiles_fb2);
+  ctx->d_tiles.reset(); ctx->d_tiles_fb.reset(); ctx->d_tiles_fb2.reset();
   ctx->tiles_x = (int)((ctx->sx + w - 1) / w);
   ctx->tiles_y = (int)((ctx->sy + h - 1) / h);
-  const size_t nb = (size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns * sizeof(uint32_t);
-  HIPCHK(hipMalloc(&ctx->d_tiles, nb));
-  HIPCHK(hipMalloc(&ctx->d_tiles_fb, nb));
-  HIPCHK(hipMalloc(&ctx->d_tiles_fb2, nb));
+  const size_t nb = (size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns;
+  HIPCHK(ctx->d_tiles.reserve(nb));
+  HIPCHK(ctx->d_tiles_fb.reserve(nb));
+  HIPCHK(ctx->d_tiles_fb2.reserve(nb));
   invalidate(ctx, CH_TILE_SHAPE);
   return SVR_OK;
 }
@@ -2010,7 +1979,7 @@ int launch_pixels(svr_ctx *ctx, const PsfArgs &a, void (*kernel)(PsfArgs), const
 }
 // {V m, m} per voxel for the gathers' boxes (patch-based: V through the 8-voxel average) -> a.volm
 int pack_volm(svr_ctx *ctx, PsfArgs &a) {
-  if (!ctx->d_volm) HIPCHK(hipMalloc(&ctx->d_volm, ctx->nv * sizeof(float2)));
+  HIPCHK(ctx->d_volm.reserve(ctx->nv));
   if (ctx->pvr) hipLaunchKernelGGL(k_pack_volm_pvr, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, a.vg);
   else hipLaunchKernelGGL(k_pack_volm, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, ctx->nv);
   KCHK(ctx->pvr ? "k_pack_volm_pvr" : "k_pack_volm");
@@ -2129,7 +2098,7 @@ int svr_create(int device, svr_ctx **out) {
   e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete ctx; return (int)e; }
   ctx->own_stream = true;
-  if (hipMalloc(&ctx->d_counter, 64) != hipSuccess || hipMalloc(&ctx->d_out, 16 * sizeof(double)) != hipSuccess) {
+  if (ctx->d_counter.reserve(16) != hipSuccess || ctx->d_out.reserve(16) != hipSuccess) {
     svr_destroy(ctx);
     return (int)hipErrorOutOfMemory;
   }
@@ -2284,31 +2253,12 @@ void svr_destroy(svr_ctx *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
-  free_volume(ctx);
-  free_slices(ctx);
-  free_dev(ctx->d_mask); free_dev(ctx->d_pair_pack);
-  free_dev(ctx->d_bias); free_dev(ctx->d_wb); free_dev(ctx->d_wr); free_dev(ctx->d_buffer);
-  free_dev(ctx->d_bias_vol); free_dev(ctx->d_volume_weights); free_dev(ctx->d_maskC); free_dev(ctx->d_mbuf);
-  free_dev(ctx->d_reg_targets);
-  free_dev(ctx->d_reg_source);
-  free_dev(ctx->d_pyr_full[0]); free_dev(ctx->d_pyr_full[1]); free_dev(ctx->d_pyr_a); free_dev(ctx->d_pyr_b); free_dev(ctx->d_pyr_meta);
-  free_dev(ctx->d_sim_io); free_dev(ctx->d_nmi_terms); free_dev(ctx->d_nmi_merge);
-  free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
-  free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums);
-  free_dev(ctx->d_ssim_partial); free_dev(ctx->d_ssim_sums); free_dev(ctx->d_ssim_map);
-  free_dev(ctx->d_channel); free_dev(ctx->d_unit_on); free_dev(ctx->d_vote_best); free_dev(ctx->d_vote_label);
-  free_dev(ctx->d_seed_src); free_dev(ctx->d_seed_out); free_dev(ctx->d_seed_partial);
-  free_dev(ctx->d_coeff); free_dev(ctx->d_coeff_id); free_dev(ctx->d_coeff_order);
+  free_slices(ctx);              // (the pinned slots and their events; the device buffers go with the context's members)
   reg_free(ctx->reg);
   cell_free(ctx->cell);
   cell_free(ctx->cell_g);
-  free_dev(ctx->d_cellc);
   slab_free(ctx->slab);
   slice_em_free(ctx->sem);
-  free_dev(ctx->d_spx);
-  free_dev(ctx->d_counter);
-  free_dev(ctx->d_out);
-  free_dev(ctx->d_em_all);
   timers_resolve(ctx);
   if (ctx->ev_open) (void)hipEventDestroy(ctx->ev_open);
   for (hipEvent_t e : ctx->ev_free) (void)hipEventDestroy(e);
@@ -2361,14 +2311,14 @@ int svr_init_reconstruction_volume(svr_ctx *ctx, const uint32_t size[3], const f
   size_t nv = (size_t)size[0] * size[1] * size[2];
   if (nv == 0 || nv >= 0xFFFFFFFFull) return fail(ctx, SVR_E_ARG, "volume size out of range");
   free_volume(ctx);
-  free_dev(ctx->d_bias_vol); free_dev(ctx->d_volume_weights); free_dev(ctx->d_maskC); free_dev(ctx->d_mbuf);
+  ctx->d_bias_vol.reset(); ctx->d_volume_weights.reset(); ctx->d_maskC.reset(); ctx->d_mbuf.reset();
   ctx->vx = size[0]; ctx->vy = size[1]; ctx->vz = size[2];
   memcpy(ctx->vdim, dim, 3 * sizeof(float));
   ctx->nv = nv;
   invalidate(ctx, CH_VOLUME_GRID);
-  HIPCHK(hipMalloc(&ctx->d_recon_volw, 2 * nv * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_addon_cmap, 2 * nv * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_recon_new, nv * sizeof(float)));
+  HIPCHK(ctx->d_recon_volw.reserve(2 * nv));
+  HIPCHK(ctx->d_addon_cmap.reserve(2 * nv));
+  HIPCHK(ctx->d_recon_new.reserve(nv));
   ctx->recon_cur = ctx->d_recon_volw;
   ctx->prep_pending = false;
   HIPCHK(hipMemsetAsync(ctx->d_recon_volw, 0, 2 * nv * sizeof(float), ctx->stream));   // RC.cu:1199-1229
@@ -2386,8 +2336,8 @@ int svr_set_mask(svr_ctx *ctx, const uint32_t size[3], const float dim[3], const
   NEED(ctx->nv > 0, "InitReconstructionVolume first");
   if ((size_t)size[0] * size[1] * size[2] != ctx->nv || size[0] != ctx->vx || size[1] != ctx->vy)
     return fail(ctx, SVR_E_ARG, "mask grid differs from the reconstruction volume");
-  free_dev(ctx->d_mask);
-  HIPCHK(hipMalloc(&ctx->d_mask, ctx->nv * sizeof(float)));
+  ctx->d_mask.reset();
+  HIPCHK(ctx->d_mask.reserve(ctx->nv));
   HIPCHK(hipMemcpyAsync(ctx->d_mask, data, ctx->nv * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->have_mask = true;
@@ -2437,12 +2387,7 @@ int svr_pair_pack(svr_ctx *ctx, int which, size_t n_floats, void **packed, size_
   const int bx = ctx->mbox_hi[0] - ctx->mbox_lo[0] + 1, by = ctx->mbox_hi[1] - ctx->mbox_lo[1] + 1, bz = ctx->mbox_hi[2] - ctx->mbox_lo[2] + 1;
   const size_t nb = (size_t)bx * by * bz;
   if (nb * 5 > ctx->nv * 4) return SVR_OK;                // the box is more than 80 % of the volume: not worth two copies
-  if (nb * nvols > ctx->pair_pack_cap) {
-    free_dev(ctx->d_pair_pack);
-    ctx->pair_pack_cap = 0;
-    HIPCHK(hipMalloc(&ctx->d_pair_pack, nb * nvols * sizeof(float)));
-    ctx->pair_pack_cap = nb * nvols;
-  }
+  HIPCHK(ctx->d_pair_pack.reserve(nb * nvols));
   hipLaunchKernelGGL(k_pair_pack, dim3(nblk(nb * nvols)), dim3(256), 0, ctx->stream, vol, ctx->d_pair_pack, nvols, ctx->nv, (int)ctx->vx, (int)ctx->vy,
                      ctx->mbox_lo[0], ctx->mbox_lo[1], ctx->mbox_lo[2], bx, by, bz, 0, (float *)nullptr);
   KCHK("k_pair_pack");
@@ -2474,40 +2419,40 @@ int svr_init_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const float d
   // work-items (in_pieces), like the reference's MAX_SLICES_PER_RUN chunks (RC.cu:2207-2219, 2414-2432, 2701-2716)
   if (np == 0 || np >= (1ull << 31)) return fail(ctx, SVR_E_ARG, "slice grid out of range: 1 .. 2^31 - 1 pixels per context (shard the slices over more ranks)");
   free_slices(ctx);
-  free_dev(ctx->d_bias); free_dev(ctx->d_wb); free_dev(ctx->d_wr); free_dev(ctx->d_buffer);
+  ctx->d_bias.reset(); ctx->d_wb.reset(); ctx->d_wr.reset(); ctx->d_buffer.reset();
   ctx->sx = size[0]; ctx->sy = size[1]; ctx->ns = size[2];
   ctx->np = np;
   ctx->have_slices = false; ctx->have_sim = false; ctx->have_scales = false; ctx->have_dims = false; ctx->have_mats = false;
   ctx->have_em = false;
   ctx->n_active = ctx->n_psf = 0;
   invalidate(ctx, CH_SLICE_GEOMETRY | CH_SLICE_PIXELS | CH_TABLE_OFF);
-  free_dev(ctx->d_coeff_id);
+  ctx->d_coeff_id.reset();
   const size_t fb = np * sizeof(float);
-  HIPCHK(hipMalloc(&ctx->d_slices, fb));
-  HIPCHK(hipMalloc(&ctx->d_weights, fb));
-  HIPCHK(hipMalloc(&ctx->d_simslices, fb));
-  HIPCHK(hipMalloc(&ctx->d_simweights, fb));
-  HIPCHK(hipMalloc(&ctx->d_psf_sums, fb));
-  HIPCHK(hipMalloc(&ctx->d_siminside, np));
-  HIPCHK(hipMalloc(&ctx->d_voxcount, np * sizeof(int)));
-  HIPCHK(hipMalloc(&ctx->d_active, np * sizeof(uint32_t)));
-  HIPCHK(hipMalloc(&ctx->d_psf_list, np * sizeof(uint32_t)));
+  HIPCHK(ctx->d_slices.reserve(np));
+  HIPCHK(ctx->d_weights.reserve(np));
+  HIPCHK(ctx->d_simslices.reserve(np));
+  HIPCHK(ctx->d_simweights.reserve(np));
+  HIPCHK(ctx->d_psf_sums.reserve(np));
+  HIPCHK(ctx->d_siminside.reserve(np));
+  HIPCHK(ctx->d_voxcount.reserve(np));
+  HIPCHK(ctx->d_active.reserve(np));
+  HIPCHK(ctx->d_psf_list.reserve(np));
   ctx->tiles_x = (int)((ctx->sx + ctx->tile_w - 1) / ctx->tile_w);
   ctx->tiles_y = (int)((ctx->sy + ctx->tile_h - 1) / ctx->tile_h);
-  HIPCHK(hipMalloc(&ctx->d_tiles, (size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns * sizeof(uint32_t)));
-  HIPCHK(hipMalloc(&ctx->d_tiles_fb, (size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns * sizeof(uint32_t)));
-  HIPCHK(hipMalloc(&ctx->d_tiles_fb2, (size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns * sizeof(uint32_t)));
-  HIPCHK(hipMalloc(&ctx->d_scales, ctx->ns * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_slice_weights, ctx->ns * sizeof(float)));
+  HIPCHK(ctx->d_tiles.reserve((size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns));
+  HIPCHK(ctx->d_tiles_fb.reserve((size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns));
+  HIPCHK(ctx->d_tiles_fb2.reserve((size_t)ctx->tiles_x * ctx->tiles_y * ctx->ns));
+  HIPCHK(ctx->d_scales.reserve(ctx->ns));
+  HIPCHK(ctx->d_slice_weights.reserve(ctx->ns));
   ctx->sem_weights_current = false;
   slice_em_invalidate(ctx->sem);                          // the slice-level EM's arrays and rank ranges were set up for the old slice count
-  HIPCHK(hipMalloc(&ctx->d_scales_host_copy, ctx->ns * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_tmp_ns, ctx->ns * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_slice_inside, ctx->ns));
-  HIPCHK(hipMalloc(&ctx->d_sc, ctx->ns * sizeof(SliceConst)));
+  HIPCHK(ctx->d_scales_host_copy.reserve(ctx->ns));
+  HIPCHK(ctx->d_tmp_ns.reserve(ctx->ns));
+  HIPCHK(ctx->d_slice_inside.reserve(ctx->ns));
+  HIPCHK(ctx->d_sc.reserve(ctx->ns));
   ctx->chunks = (int)(((size_t)ctx->sx * ctx->sy + CHUNK_PIX - 1) / CHUNK_PIX);
-  HIPCHK(hipMalloc(&ctx->d_partial, (size_t)ctx->ns * ctx->chunks * REDUCE_MAXK * sizeof(double)));    // (reduce_partials' guard is the same constant)
-  HIPCHK(hipMalloc(&ctx->d_per_slice, (size_t)ctx->ns * REDUCE_MAXK * sizeof(double)));
+  HIPCHK(ctx->d_partial.reserve((size_t)ctx->ns * ctx->chunks * REDUCE_MAXK));    // (reduce_partials' guard is the same constant)
+  HIPCHK(ctx->d_per_slice.reserve((size_t)ctx->ns * REDUCE_MAXK));
   // RC.cu:1555-1568: everything cleared once at allocation (v_PSF_sums is never cleared again)
   HIPCHK(hipMemsetAsync(ctx->d_slices, 0, fb, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_weights, 0, fb, ctx->stream));
@@ -2682,17 +2627,13 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
   if (a.n && p1.family != FAM_PIXELS) {
     // pass 1 = the unit-based walk of the gather (sume, gate, v_PSF_sums, voxel-count flag), pass 2 = the scatter of the
     // back-projection with {recon|volw} as targets and unit voxel / slice weights
-    if (!ctx->d_gauss_flag) HIPCHK(hipMalloc(&ctx->d_gauss_flag, ctx->np));
+    HIPCHK(ctx->d_gauss_flag.reserve(ctx->np));
     HIPCHK(hipMemsetAsync(ctx->d_gauss_flag, 0, ctx->np, ctx->stream));
     // pass 1 keeps 4-pixel-wide tiles when the gather of the SR iterations chose 6 x 4 (measured: 6 x 4 costs pass 1 1.6 ms on P4)
     const int gtw = ctx->fwd_tw == 6 ? 4 : ctx->fwd_tw, gth = ctx->fwd_th;
     const int ftx = (int)((ctx->sx + gtw - 1) / gtw), fty = (int)((ctx->sy + gth - 1) / gth);
     const size_t max_tiles = std::max((size_t)ftx * fty, (size_t)ctx->tiles_x * ctx->tiles_y) * ctx->ns;
-    if (max_tiles > ctx->tiles_tmp_cap) {
-      free_dev(ctx->d_tiles_tmp);
-      HIPCHK(hipMalloc(&ctx->d_tiles_tmp, max_tiles * sizeof(uint32_t)));
-      ctx->tiles_tmp_cap = max_tiles;
-    }
+    HIPCHK(ctx->d_tiles_tmp.reserve(max_tiles));
     uint32_t n1 = 0, n2 = 0;
     a.flag = nullptr; a.flag_out = ctx->d_gauss_flag;
     CellState *gcs = nullptr;
@@ -2742,7 +2683,7 @@ int svr_gaussian_reconstruction_finish(svr_ctx *ctx, int *voxel_num) {
   hipLaunchKernelGGL(k_equalize, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->volw(), ctx->nv);
   KCHK("k_equalize");
   unsigned long long cnt = 0;
-  unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(ctx->d_out);
+  unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(ctx->d_out.get());
   HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(cnt), ctx->stream));
   hipLaunchKernelGGL(k_count_positive, dim3(std::min(nblk(ctx->np), 2048u)), dim3(256), 0, ctx->stream, ctx->d_voxcount, ctx->np, d_cnt);
   KCHK("k_count_positive");
@@ -2991,7 +2932,7 @@ int svr_mstep_estep(svr_ctx *ctx, int iter, float step, float em3[3], float *sli
   SVR_ENTER(ctx);
   if (!ctx || !em3 || !slice_potential) return SVR_E_ARG;
   NEED(ctx->have_slices && ctx->have_scales, "slices / scales not set");
-  if (!ctx->d_em) HIPCHK(hipMalloc(&ctx->d_em, 4 * sizeof(float)));
+  HIPCHK(ctx->d_em.reserve(4));
   int r = launch_mstep(ctx);
   if (r) return r;
   hipLaunchKernelGGL(k_mstep_scalars, dim3(1), dim3(1), 0, ctx->stream, ctx->d_out, iter, step, ctx->pvr ? 1 : 0, em3[0], em3[1], ctx->d_em);
@@ -3014,12 +2955,7 @@ int svr_mstep_partial(svr_ctx *ctx, int world, void **send, void **recv) {
   SVR_ENTER(ctx);
   if (!ctx || !send || !recv || world < 1) return SVR_E_ARG;
   NEED(ctx->have_slices && ctx->have_scales, "slices / scales not set");
-  if ((size_t)world > ctx->em_all_cap) {
-    free_dev(ctx->d_em_all);
-    ctx->em_all_cap = 0;
-    HIPCHK(hipMalloc(&ctx->d_em_all, (size_t)world * 8 * sizeof(double)));
-    ctx->em_all_cap = world;
-  }
+  HIPCHK(ctx->d_em_all.reserve((size_t)world * 8));
   int r = launch_mstep(ctx);
   if (r) return r;
   *send = ctx->d_out;
@@ -3029,8 +2965,8 @@ int svr_mstep_partial(svr_ctx *ctx, int world, void **send, void **recv) {
 int svr_mstep_estep_ranks(svr_ctx *ctx, int world, int iter, float step, float em3[3], float *slice_potential, float *scale_vec, uint8_t *slice_inside) {
   SVR_ENTER(ctx);
   if (!ctx || !em3 || !slice_potential || world < 1) return SVR_E_ARG;
-  NEED(ctx->have_slices && ctx->have_scales && ctx->d_em_all && (size_t)world <= ctx->em_all_cap, "svr_mstep_partial first");
-  if (!ctx->d_em) HIPCHK(hipMalloc(&ctx->d_em, 4 * sizeof(float)));
+  NEED(ctx->have_slices && ctx->have_scales && (size_t)world * 8 <= ctx->d_em_all.capacity(), "svr_mstep_partial first");
+  HIPCHK(ctx->d_em.reserve(4));
   hipLaunchKernelGGL(k_mstep_scalars_ranks, dim3(1), dim3(1), 0, ctx->stream, ctx->d_em_all, world, iter, step, ctx->pvr ? 1 : 0, em3[0], em3[1], ctx->d_em);
   KCHK("k_mstep_scalars_ranks");
   int r;
@@ -3169,7 +3105,7 @@ static int regul_settle(svr_ctx *ctx) {
 static int superresolution_update_planes(svr_ctx *ctx, int adaptive, float alpha, float min_intensity, float max_intensity, float delta,
                                          float lambda, int z_lo, int z_hi) {
   if (ctx->reg_mode == 0) {
-    if (!ctx->d_snap) HIPCHK(hipMalloc(&ctx->d_snap, ctx->nv * sizeof(float)));
+    HIPCHK(ctx->d_snap.reserve(ctx->nv));
     if (z_lo != 0 || z_hi != (int)ctx->vz) return fail(ctx, SVR_E_ARG, "reg_mode 0 updates whole volumes only");
     float *out = ctx->recon_cur == ctx->d_recon_volw ? ctx->d_recon_new : ctx->d_recon_volw;
     hipLaunchKernelGGL(k_reg_prep, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, adaptive, alpha, ctx->recon(),
@@ -3374,18 +3310,16 @@ int svr_restore_slice_intensities(svr_ctx *ctx, const float *stack_factors, int 
   NEED(ctx->have_slices, "slices not filled");
   for (uint32_t i = 0; i < ctx->ns; ++i)
     if (stack_index[i] < 0 || stack_index[i] >= n_stacks) return fail(ctx, SVR_E_ARG, "stack index out of range");
-  float *d_f = nullptr;
-  int *d_i = nullptr;
-  HIPCHK(hipMalloc(&d_f, n_stacks * sizeof(float)));
-  HIPCHK(hipMalloc(&d_i, ctx->ns * sizeof(int)));
+  DevBuf<float> d_f;
+  DevBuf<int> d_i;
+  HIPCHK(d_f.reserve(n_stacks));
+  HIPCHK(d_i.reserve(ctx->ns));
   HIPCHK(hipMemcpyAsync(d_f, stack_factors, n_stacks * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(d_i, stack_index, ctx->ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_restore, dim3(nblk(ctx->np)), dim3(256), 0, ctx->stream, ctx->d_slices, d_f, d_i,
                      (int)(ctx->sx * ctx->sy), ctx->np);
   hipError_t e = hipGetLastError();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_f);
-  (void)hipFree(d_i);
   if (e != hipSuccess) return fail(ctx, (int)e, "k_restore");
   return SVR_OK;
 }
@@ -3468,10 +3402,10 @@ int svr_debug_probe_pixel(svr_ctx *ctx, int slice, int px, int py, float *vals40
   if (r) return r;
   if (slice < 0 || slice >= (int)ctx->ns || px < 0 || px >= (int)ctx->sx || py < 0 || py >= (int)ctx->sy)
     return fail(ctx, SVR_E_ARG, "pixel out of range");
-  float *d_v = nullptr;
-  int *d_c = nullptr;
-  HIPCHK(hipMalloc(&d_v, 4096 * sizeof(float)));
-  HIPCHK(hipMalloc(&d_c, 3 * sizeof(int)));
+  DevBuf<float> d_v;
+  DevBuf<int> d_c;
+  HIPCHK(d_v.reserve(4096));
+  HIPCHK(d_c.reserve(3));
   PsfArgs a = make_args(ctx);
   uint32_t idx = (uint32_t)px + (uint32_t)py * ctx->sx + (uint32_t)slice * ctx->sx * ctx->sy;
   hipLaunchKernelGGL(k_probe_pixel, dim3(1), dim3(64), 0, ctx->stream, a, idx, d_v, d_c);
@@ -3479,8 +3413,6 @@ int svr_debug_probe_pixel(svr_ctx *ctx, int slice, int px, int py, float *vals40
   if (e == hipSuccess) e = hipMemcpyAsync(vals4096, d_v, 4096 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(centre3, d_c, 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_v);
-  (void)hipFree(d_c);
   if (e != hipSuccess) return fail(ctx, (int)e, "svr_debug_probe_pixel");
   return SVR_OK;
 }
@@ -3490,10 +3422,10 @@ int svr_set_spx_masks(svr_ctx *ctx, const char *masks_or_null) {
   SVR_ENTER(ctx);
   if (!ctx) return SVR_E_ARG;
   NEED(ctx->ns > 0, "initStorageVolumes first");
-  free_dev(ctx->d_spx);
+  ctx->d_spx.reset();
   if (!masks_or_null) return SVR_OK;
   const size_t bytes = (size_t)ctx->ns * 4096;
-  HIPCHK(hipMalloc(&ctx->d_spx, bytes));
+  HIPCHK(ctx->d_spx.reserve(bytes));
   HIPCHK(hipMemcpyAsync(ctx->d_spx, masks_or_null, bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
@@ -3759,8 +3691,8 @@ __global__ __launch_bounds__(256) void k_clock_probe(float *out, int n) {
 int svr_clock_probe(svr_ctx *ctx, int chain, double *ms) {
   SVR_ENTER(ctx);
   if (!ctx || !ms || chain <= 0) return SVR_E_ARG;
-  float *d = nullptr;
-  HIPCHK(hipMalloc(&d, 4096 * sizeof(float)));
+  DevBuf<float> d;
+  HIPCHK(d.reserve(4096));
   hipEvent_t a = nullptr, b = nullptr;
   hipError_t e = hipEventCreate(&a);
   if (e == hipSuccess) e = hipEventCreate(&b);
@@ -3776,7 +3708,6 @@ int svr_clock_probe(svr_ctx *ctx, int chain, double *ms) {
   }
   if (a) (void)hipEventDestroy(a);
   if (b) (void)hipEventDestroy(b);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(ctx, (int)e, std::string("svr_clock_probe: ") + hipGetErrorString(e));
   *ms = best;
   return SVR_OK;

@@ -115,10 +115,6 @@ bool jacobi_eigenvalues(std::vector<double> &a, int n, std::vector<double> &ev) 
   return done;
 }
 
-void motion_free(svr_ctx *ctx) {
-  free_dev(ctx->d_mot_x); free_dev(ctx->d_mot_partial); free_dev(ctx->d_mot_g);
-}
-
 int motion_gram(svr_ctx *ctx, const float *slices, int m, int n, std::vector<double> &g) {
   const int bands = (n + MOT_T - 1) / MOT_T, pairs = bands * (bands + 1) / 2;
   const size_t np = (size_t)bands * MOT_T, steps = ((size_t)m + MOT_T - 1) / MOT_T;
@@ -127,16 +123,20 @@ int motion_gram(svr_ctx *ctx, const float *slices, int m, int n, std::vector<dou
   const int chunk_len = (int)((steps + want - 1) / want) * MOT_T;
   const int chunks = (int)(((size_t)m + chunk_len - 1) / chunk_len);
   if (pairs > 65535) return fail(ctx, SVR_E_ARG, "svr_stack_motion: too many slices");
-  HIPCHK(hipMalloc(&ctx->d_mot_x, (size_t)m * n * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_mot_partial, (size_t)chunks * np * np * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_mot_g, (size_t)n * n * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(ctx->d_mot_x, slices, (size_t)m * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_gram, dim3(chunks, pairs), dim3(256), 0, ctx->stream, ctx->d_mot_x, m, n, chunk_len, bands, ctx->d_mot_partial);
+  // the slices, the chunks' partial Gram matrices and their sum: nothing is kept beyond the call (the coefficient table sizes itself by the
+  // memory that is free)
+  DevBuf<float> d_x;
+  DevBuf<double> d_partial, d_g;
+  HIPCHK(d_x.reserve((size_t)m * n));
+  HIPCHK(d_partial.reserve((size_t)chunks * np * np));
+  HIPCHK(d_g.reserve((size_t)n * n));
+  HIPCHK(hipMemcpyAsync(d_x, slices, (size_t)m * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_gram, dim3(chunks, pairs), dim3(256), 0, ctx->stream, d_x, m, n, chunk_len, bands, d_partial);
   KCHK("k_gram");
-  hipLaunchKernelGGL(k_gram_sum, dim3((n + 63) / 64, n), dim3(64), 0, ctx->stream, ctx->d_mot_partial, n, (int)np, chunks, ctx->d_mot_g);
+  hipLaunchKernelGGL(k_gram_sum, dim3((n + 63) / 64, n), dim3(64), 0, ctx->stream, d_partial, n, (int)np, chunks, d_g);
   KCHK("k_gram_sum");
   g.resize((size_t)n * n);
-  HIPCHK(hipMemcpyAsync(g.data(), ctx->d_mot_g, g.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(g.data(), d_g, g.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
@@ -154,7 +154,6 @@ int svr_stack_motion(svr_ctx *ctx, const float *slices, int m, int n, double *si
   if (n > 65535) return fail(ctx, SVR_E_ARG, "svr_stack_motion: too many slices");
   std::vector<double> g, ev;
   const int rc = motion_gram(ctx, slices, m, n, g);
-  motion_free(ctx);                        // nothing is kept: the coefficient table sizes itself by the memory that is free
   if (rc) return rc;
   if (!jacobi_eigenvalues(g, n, ev)) return fail(ctx, SVR_E_STATE, "svr_stack_motion: the eigenvalue iteration did not converge");
   std::sort(ev.begin(), ev.end(), std::greater<double>());

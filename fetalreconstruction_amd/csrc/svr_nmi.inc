@@ -219,20 +219,18 @@ int svr_nmi_evaluate(svr_ctx *ctx, int n_eval, const int *planes_per_eval, const
     std::vector<double> tt(n);
     tt[0] = 0;
     for (size_t k = 1; k < n; ++k) tt[k] = (double)k * log((double)k);
-    free_dev(ctx->d_nmi_terms);
-    ctx->nmi_terms_n = 0;
-    HIPCHK(hipMalloc(&ctx->d_nmi_terms, n * sizeof(double)));
+    ctx->nmi_terms_n = 0;                                  // (the entries that were uploaded, not the allocation's size: none until the copy below is through)
+    HIPCHK(ctx->d_nmi_terms.reserve(n));
     HIPCHK(hipMemcpyAsync(ctx->d_nmi_terms, tt.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->nmi_terms_n = n;
   }
   // merge slots and their counters: zeroed once when they grow, left zero by every call
   if ((size_t)slots > ctx->nmi_slots) {
-    free_dev(ctx->d_nmi_merge);
-    ctx->nmi_slots = 0;
+    ctx->nmi_slots = 0;                                    // (the slots that are laid out and zeroed: where the counters start)
     const size_t cap = std::max<size_t>(64, (size_t)slots * 3 / 2);
     const size_t bytes = cap * (NMI_H + 1) * sizeof(unsigned) + cap * sizeof(unsigned);
-    HIPCHK(hipMalloc(&ctx->d_nmi_merge, bytes));
+    HIPCHK(ctx->d_nmi_merge.reserve(bytes / sizeof(unsigned)));
     HIPCHK(hipMemsetAsync(ctx->d_nmi_merge, 0, bytes, ctx->stream));
     ctx->nmi_slots = cap;
   }

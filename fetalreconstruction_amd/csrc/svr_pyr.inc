@@ -136,9 +136,9 @@ int svr_ncc_alloc_targets(svr_ctx *ctx, int n, int tx, int ty) {
   SVR_ENTER(ctx);
   if (!ctx || n <= 0 || tx <= 0 || ty <= 0) return SVR_E_ARG;
   HIPCHK(hipSetDevice(ctx->device));
-  free_dev(ctx->d_reg_targets);
+  ctx->d_reg_targets.reset();
   const size_t count = (size_t)n * tx * ty;
-  HIPCHK(hipMalloc(&ctx->d_reg_targets, count * sizeof(short)));
+  HIPCHK(ctx->d_reg_targets.reserve(count));
   hipLaunchKernelGGL(k_pyr_fill, dim3(nblk(count)), dim3(256), 0, ctx->stream, ctx->d_reg_targets, count, (short)-1);
   KCHK("k_pyr_fill");
   ctx->reg_n = n; ctx->reg_tx = tx; ctx->reg_ty = ty;
@@ -149,12 +149,7 @@ int svr_pyr_upload(svr_ctx *ctx, int slot, const int16_t *images, size_t count) 
   SVR_ENTER(ctx);
   if (!ctx || !images || count == 0 || slot < 0 || slot > 1) return SVR_E_ARG;
   HIPCHK(hipSetDevice(ctx->device));
-  if (ctx->pyr_full_cap[slot] < count) {
-    free_dev(ctx->d_pyr_full[slot]);
-    ctx->pyr_full_cap[slot] = 0;
-    HIPCHK(hipMalloc(&ctx->d_pyr_full[slot], count * sizeof(short)));
-    ctx->pyr_full_cap[slot] = count;
-  }
+  HIPCHK(ctx->d_pyr_full[slot].reserve(count));
   HIPCHK(hipMemcpyAsync(ctx->d_pyr_full[slot], images, count * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
@@ -170,7 +165,7 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
   const size_t nin = (size_t)in_dims[0] * in_dims[1] * in_dims[2], nout = (size_t)out_dims[0] * out_dims[1] * out_dims[2];
   if (nin == 0 || nout == 0 || nin >= (1ull << 31) || nout >= (1ull << 31)) return fail(ctx, SVR_E_ARG, "svr_pyr_level: image size out of range");
   if (n_images > 65535) return fail(ctx, SVR_E_ARG, "svr_pyr_level: at most 65535 images of one grid per call");
-  NEED(ctx->d_pyr_full[slot] && offset + nin * n_images <= ctx->pyr_full_cap[slot], "svr_pyr_upload first");
+  NEED(ctx->d_pyr_full[slot] && offset + nin * n_images <= ctx->d_pyr_full[slot].capacity(), "svr_pyr_upload first");
   if (!resample && nout != nin) return fail(ctx, SVR_E_ARG, "svr_pyr_level: a level that keeps the grid keeps its size");
   if (slot == 1) {
     NEED(ctx->d_reg_targets, "svr_ncc_alloc_targets first");
@@ -179,13 +174,8 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
       return fail(ctx, SVR_E_ARG, "svr_pyr_level: the planes do not fit the allocated targets");
   }
   const size_t work = (size_t)n_images * std::max(nin, nout);
-  if (ctx->pyr_work_cap < work) {
-    free_dev(ctx->d_pyr_a); free_dev(ctx->d_pyr_b);
-    ctx->pyr_work_cap = 0;
-    HIPCHK(hipMalloc(&ctx->d_pyr_a, work * sizeof(short)));
-    HIPCHK(hipMalloc(&ctx->d_pyr_b, work * sizeof(short)));
-    ctx->pyr_work_cap = work;
-  }
+  HIPCHK(ctx->d_pyr_a.reserve(work));
+  HIPCHK(ctx->d_pyr_b.reserve(work));
   // meta: the images' matrices and paddings, the three kernels, min / max
   const int sizes[3] = {size_x, size_y, size_z};
   const double *kers[3] = {kernel_x, kernel_y, kernel_z};
@@ -196,12 +186,7 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
   }
   const size_t img_bytes = sizeof(PyrImg) * (size_t)n_images, ker_bytes = sizeof(double) * std::max<size_t>(ker_total, 1),
                mm_bytes = 2 * sizeof(int) * (size_t)n_images, meta = img_bytes + ker_bytes + mm_bytes;
-  if (ctx->pyr_meta_cap < meta) {
-    free_dev(ctx->d_pyr_meta);
-    ctx->pyr_meta_cap = 0;
-    HIPCHK(hipMalloc(&ctx->d_pyr_meta, meta));
-    ctx->pyr_meta_cap = meta;
-  }
+  HIPCHK(ctx->d_pyr_meta.reserve(meta));
   std::vector<unsigned char> hmeta(img_bytes + ker_bytes, 0);
   PyrImg *hi = reinterpret_cast<PyrImg *>(hmeta.data());
   for (int i = 0; i < n_images; ++i) {
@@ -213,9 +198,9 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
   size_t koff[3], at = 0;
   for (int a = 0; a < 3; ++a) { koff[a] = at; if (sizes[a]) memcpy(hk + at, kers[a], sizeof(double) * sizes[a]); at += sizes[a]; }
   HIPCHK(hipMemcpyAsync(ctx->d_pyr_meta, hmeta.data(), hmeta.size(), hipMemcpyHostToDevice, ctx->stream));
-  const PyrImg *d_img = reinterpret_cast<const PyrImg *>(ctx->d_pyr_meta);
-  const double *d_ker = reinterpret_cast<const double *>(static_cast<unsigned char *>(ctx->d_pyr_meta) + img_bytes);
-  int *d_mn = reinterpret_cast<int *>(static_cast<unsigned char *>(ctx->d_pyr_meta) + img_bytes + ker_bytes), *d_mx = d_mn + n_images;
+  const PyrImg *d_img = reinterpret_cast<const PyrImg *>(ctx->d_pyr_meta.get());
+  const double *d_ker = reinterpret_cast<const double *>(ctx->d_pyr_meta.get() + img_bytes);
+  int *d_mn = reinterpret_cast<int *>(ctx->d_pyr_meta.get() + img_bytes + ker_bytes), *d_mx = d_mn + n_images;
   // blur: three passes, each from the previous one's shorts
   const short *cur = ctx->d_pyr_full[slot] + offset;
   short *bufs[2] = {ctx->d_pyr_a, ctx->d_pyr_b};
@@ -242,8 +227,8 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
   short *dst;
   int tx, ty;
   if (slot == 0) {
-    free_dev(ctx->d_reg_source);
-    HIPCHK(hipMalloc(&ctx->d_reg_source, nout * sizeof(short)));
+    ctx->d_reg_source.reset();
+    HIPCHK(ctx->d_reg_source.reserve(nout));
     ctx->reg_vx = lx; ctx->reg_vy = ly; ctx->reg_vz = lz;
     dst = ctx->d_reg_source; tx = lx; ty = ly; first_plane = 0;
   } else {

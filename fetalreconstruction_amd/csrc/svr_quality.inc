@@ -122,17 +122,18 @@ int slice_quality_run(svr_ctx *ctx, double *sums) {
   const size_t blocks = (size_t)ctx->ns * chunks, nout = (size_t)ctx->ns * QUAL_K;
   if (blocks >= (1ull << 31) || nout >= (1ull << 31)) return fail(ctx, SVR_E_ARG, "svr_slice_quality: too many slices");
   const float *bias = ctx->disable_bias ? (const float *)nullptr : ctx->d_bias;
-  HIPCHK(hipMalloc(&ctx->d_qual_partial, blocks * QUAL_K * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_qual_sums, nout * sizeof(double)));
+  DevBuf<double> d_partial, d_sums;                          // nothing is kept beyond the call: the coefficient table sizes itself by the memory that is free
+  HIPCHK(d_partial.reserve(blocks * QUAL_K));
+  HIPCHK(d_sums.reserve(nout));
   hipLaunchKernelGGL(bias ? k_slice_quality<true> : k_slice_quality<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_slices,
                      ctx->d_weights, ctx->d_simslices, ctx->d_simweights, ctx->d_scales_host_copy, bias, (int)n2, chunks, chunk_len,
-                     ctx->d_qual_partial);
+                     d_partial.get());
   KCHK("k_slice_quality");
-  hipLaunchKernelGGL(k_slice_quality_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_qual_partial, (int)ctx->ns,
-                     chunks, ctx->d_qual_sums);
+  hipLaunchKernelGGL(k_slice_quality_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, d_partial.get(), (int)ctx->ns,
+                     chunks, d_sums.get());
   KCHK("k_slice_quality_finish");
   ctx->last_quality_chunks = chunks;
-  HIPCHK(hipMemcpyAsync(sums, ctx->d_qual_sums, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(sums, d_sums.get(), nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
@@ -150,9 +151,7 @@ int svr_slice_quality(svr_ctx *ctx, double *sums) {
   NEED(ctx->have_sim, "no simulated slices (svr_simulate_slices first)");
   int r = ensure_bias_buffers(ctx);                          // (as every compute call: a bias path switched on before the slice grid existed)
   if (r) return r;
-  r = slice_quality_run(ctx, sums);
-  free_dev(ctx->d_qual_partial); free_dev(ctx->d_qual_sums); // nothing is kept: the coefficient table sizes itself by the memory that is free
-  return r;
+  return slice_quality_run(ctx, sums);
 }
 
 }  // extern "C"

@@ -16,19 +16,19 @@
 struct RegState {
   int W = 0, H = 0, ns = 0;
   size_t wh = 0;
-  float *resampled = nullptr, *target = nullptr, *tmp = nullptr, *reg = nullptr;   // [ns][H][W], .., [3ns].., [3][ns][H][W]
-  float *vol = nullptr;                                                            // snapshot of the reconstruction
-  float *ofs = nullptr, *mat = nullptr, *mat_orig = nullptr;                       // [ns][16]
-  float *sim = nullptr, *grad = nullptr;                                           // [5][ns], [7][ns]
-  int *active = nullptr, *active2 = nullptr, *active_prev = nullptr, *count = nullptr;
+  DevBuf<float> resampled, target, tmp, reg;                                       // [ns][H][W], .., [3ns].., [3][ns][H][W]
+  DevBuf<float> vol;                                                               // snapshot of the reconstruction
+  DevBuf<float> ofs, mat, mat_orig;                                                // [ns][16]
+  DevBuf<float> sim, grad;                                                         // [5][ns], [7][ns]
+  DevBuf<int> active, active2, active_prev, count;
   // batched gradient: the twelve variants of every slice in one launch sequence
-  float *regv = nullptr, *tmpv = nullptr, *matv = nullptr, *simv = nullptr, *sumBv = nullptr, *momv = nullptr;   // [36][ns][H][W] x 2, [12][ns][16], [12][ns], [36][ns], [36][ns][3]
-  int *cntBv = nullptr;
-  long long *dctr = nullptr;                                                       // [5] device part of `counters` (blind line-search steps); [4]: ls_max
+  DevBuf<float> regv, tmpv, matv, simv, sumBv, momv;   // [36][ns][H][W] x 2, [12][ns][16], [12][ns], [36][ns], [36][ns][3]
+  DevBuf<int> cntBv;
+  DevBuf<long long> dctr;                                                          // [5] device part of `counters` (blind line-search steps); [4]: ls_max
   int red_threads = 0;                                                             // 0: by image size; 256 / 1024 (option reg_red_threads, tests)
   int batch_state = 0;                                                             // 0 not tried, 1 ready, -1 no memory: literal sequence
-  float *sumA = nullptr, *sumB = nullptr, *mom = nullptr, *half = nullptr;         // [ns], [3][ns], [3][ns][3], [8][32]
-  int *cntA = nullptr, *cntB = nullptr;
+  DevBuf<float> sumA, sumB, mom, half;                                             // [ns], [3][ns], [3][ns][3], [8][32]
+  DevBuf<int> cntA, cntB;
   bool have_slices = false, have_ofs = false, prepared = false;
   int levels = 2, steps = 4, iterations = 20;
   float epsilon = 0.0001f;
@@ -633,16 +633,7 @@ void invert4d(const double *a, double *out) {
   for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) out[4 * i + j] = w[i][4 + j];
 }
 
-void reg_free(RegState *r) {
-  if (!r) return;
-  free_dev(r->resampled); free_dev(r->target); free_dev(r->tmp); free_dev(r->reg); free_dev(r->vol);
-  free_dev(r->ofs); free_dev(r->mat); free_dev(r->mat_orig); free_dev(r->sim); free_dev(r->grad);
-  free_dev(r->active); free_dev(r->active2); free_dev(r->active_prev); free_dev(r->count);
-  free_dev(r->dctr);
-  free_dev(r->regv); free_dev(r->tmpv); free_dev(r->matv); free_dev(r->simv); free_dev(r->sumBv); free_dev(r->momv); free_dev(r->cntBv);
-  free_dev(r->sumA); free_dev(r->sumB); free_dev(r->mom); free_dev(r->half); free_dev(r->cntA); free_dev(r->cntB);
-  delete r;
-}
+void reg_free(RegState *r) { delete r; }
 
 // generateGaussianKernel + the length rule of FilterGaussStack (GF.cu:56-87,195-196)
 int reg_gauss_kernel(float sigma, float *half) {
@@ -735,13 +726,13 @@ bool reg_batch_ready(svr_ctx *ctx) {
   RegState *r = ctx->reg;
   if (r->batch_state) return r->batch_state > 0;
   const size_t n = (size_t)36 * r->ns * r->wh;
-  bool ok = hipMalloc(&r->regv, n * sizeof(float)) == hipSuccess && hipMalloc(&r->tmpv, n * sizeof(float)) == hipSuccess &&
-            hipMalloc(&r->matv, (size_t)12 * 16 * r->ns * sizeof(float)) == hipSuccess && hipMalloc(&r->simv, (size_t)12 * r->ns * sizeof(float)) == hipSuccess &&
-            hipMalloc(&r->sumBv, (size_t)36 * r->ns * sizeof(float)) == hipSuccess && hipMalloc(&r->cntBv, (size_t)36 * r->ns * sizeof(int)) == hipSuccess &&
-            hipMalloc(&r->momv, (size_t)108 * r->ns * sizeof(float)) == hipSuccess;
+  bool ok = r->regv.reserve(n) == hipSuccess && r->tmpv.reserve(n) == hipSuccess &&
+            r->matv.reserve((size_t)12 * 16 * r->ns) == hipSuccess && r->simv.reserve((size_t)12 * r->ns) == hipSuccess &&
+            r->sumBv.reserve((size_t)36 * r->ns) == hipSuccess && r->cntBv.reserve((size_t)36 * r->ns) == hipSuccess &&
+            r->momv.reserve((size_t)108 * r->ns) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    free_dev(r->regv); free_dev(r->tmpv); free_dev(r->matv); free_dev(r->simv); free_dev(r->sumBv); free_dev(r->momv); free_dev(r->cntBv);
+    r->regv.reset(); r->tmpv.reset(); r->matv.reset(); r->simv.reset(); r->sumBv.reset(); r->momv.reset(); r->cntBv.reset();
   }
   r->batch_state = ok ? 1 : -1;
   return ok;
@@ -794,26 +785,26 @@ int svr_init_reg_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const flo
   r->W = (int)size[0]; r->H = (int)size[1]; r->ns = (int)size[2];
   r->wh = (size_t)r->W * r->H;
   const size_t n = (size_t)r->ns * r->wh;
-  HIPCHK(hipMalloc(&r->resampled, n * sizeof(float)));
-  HIPCHK(hipMalloc(&r->target, n * sizeof(float)));
-  HIPCHK(hipMalloc(&r->tmp, 3 * n * sizeof(float)));
-  HIPCHK(hipMalloc(&r->reg, 3 * n * sizeof(float)));
-  HIPCHK(hipMalloc(&r->ofs, 16 * sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->mat, 16 * sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->mat_orig, 16 * sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->sim, 5 * sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->grad, 7 * sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->active, sizeof(int) * r->ns));
-  HIPCHK(hipMalloc(&r->active2, sizeof(int) * r->ns));
-  HIPCHK(hipMalloc(&r->active_prev, sizeof(int) * r->ns));
-  HIPCHK(hipMalloc(&r->count, sizeof(int)));
-  HIPCHK(hipMalloc(&r->dctr, 5 * sizeof(long long)));
-  HIPCHK(hipMalloc(&r->sumA, sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->cntA, sizeof(int) * r->ns));
-  HIPCHK(hipMalloc(&r->sumB, 3 * sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->cntB, 3 * sizeof(int) * r->ns));
-  HIPCHK(hipMalloc(&r->mom, 9 * sizeof(float) * r->ns));
-  HIPCHK(hipMalloc(&r->half, 8 * 32 * sizeof(float)));
+  HIPCHK(r->resampled.reserve(n));
+  HIPCHK(r->target.reserve(n));
+  HIPCHK(r->tmp.reserve(3 * n));
+  HIPCHK(r->reg.reserve(3 * n));
+  HIPCHK(r->ofs.reserve(16 * r->ns));
+  HIPCHK(r->mat.reserve(16 * r->ns));
+  HIPCHK(r->mat_orig.reserve(16 * r->ns));
+  HIPCHK(r->sim.reserve(5 * r->ns));
+  HIPCHK(r->grad.reserve(7 * r->ns));
+  HIPCHK(r->active.reserve(r->ns));
+  HIPCHK(r->active2.reserve(r->ns));
+  HIPCHK(r->active_prev.reserve(r->ns));
+  HIPCHK(r->count.reserve(1));
+  HIPCHK(r->dctr.reserve(5));
+  HIPCHK(r->sumA.reserve(r->ns));
+  HIPCHK(r->cntA.reserve(r->ns));
+  HIPCHK(r->sumB.reserve(3 * r->ns));
+  HIPCHK(r->cntB.reserve(3 * r->ns));
+  HIPCHK(r->mom.reserve(9 * r->ns));
+  HIPCHK(r->half.reserve(8 * 32));
   HIPCHK(hipMemsetAsync(r->sim, 0, 5 * sizeof(float) * r->ns, ctx->stream));
   HIPCHK(hipMemsetAsync(r->grad, 0, 7 * sizeof(float) * r->ns, ctx->stream));
   return SVR_OK;
@@ -848,7 +839,7 @@ int svr_prepare_slice_to_volume_reg(svr_ctx *ctx) {
   NEED(ctx->reg, "svr_init_reg_storage_volumes first");
   NEED(ctx->d_recon_volw, "svr_init_reconstruction_volume first");
   RegState *r = ctx->reg;
-  if (!r->vol) HIPCHK(hipMalloc(&r->vol, ctx->nv * sizeof(float)));
+  HIPCHK(r->vol.reserve(ctx->nv));
   HIPCHK(hipMemcpyAsync(r->vol, ctx->recon(), ctx->nv * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   // RC.cu:3884-3900
   r->levels = 2; r->steps = 4; r->iterations = 20; r->epsilon = 0.0001f;
@@ -1067,27 +1058,26 @@ int svr_pvr_cc_patches(svr_ctx *ctx, const float *buffer_or_null, const float *R
   const int n = (int)ctx->ns, px = (int)ctx->sx, py = (int)ctx->sy;
   std::vector<float> M(16 * (size_t)n);
   for (int i = 0; i < n; ++i) matmul4(Tmats + 16 * (size_t)i, RI2W + 16 * (size_t)i, &M[16 * (size_t)i]);   // Tmat * RI2W (:152)
-  float *d_m = nullptr, *d_buf = nullptr;
-  double *d_s = nullptr;
+  DevBuf<float> d_m, d_buf;
+  DevBuf<double> d_s;
   std::vector<double> h(6 * (size_t)n);
-  HIPCHK(hipMalloc(&d_m, M.size() * sizeof(float)));
-  HIPCHK(hipMalloc(&d_s, h.size() * sizeof(double)));
+  HIPCHK(d_m.reserve(M.size()));
+  HIPCHK(d_s.reserve(h.size()));
   hipError_t e = hipMemcpyAsync(d_m, M.data(), M.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && buffer_or_null) {
-    e = hipMalloc(&d_buf, ctx->np * sizeof(float));
+    e = d_buf.reserve(ctx->np);
     if (e == hipSuccess) e = hipMemcpyAsync(d_buf, buffer_or_null, ctx->np * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
   }
   if (e == hipSuccess) {
     RegVol v;
     v.vol = ctx->recon(); v.vx = (int)ctx->vx; v.vy = (int)ctx->vy; v.vz = (int)ctx->vz;
     memcpy(v.W2I, ctx->reconW2I, 12 * sizeof(float));
-    hipLaunchKernelGGL(k_cc_patch, dim3(n), dim3(256), 0, ctx->stream, v, d_buf ? d_buf : ctx->d_slices, px, py, d_m, level,
+    hipLaunchKernelGGL(k_cc_patch, dim3(n), dim3(256), 0, ctx->stream, v, d_buf ? d_buf.get() : ctx->d_slices.get(), px, py, d_m, level,
                        d_s);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_s, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_m); (void)hipFree(d_s); if (d_buf) (void)hipFree(d_buf);
   if (e != hipSuccess) return fail(ctx, (int)e, "svr_pvr_cc_patches");
   for (int i = 0; i < n; ++i) {
     const double *s = &h[6 * (size_t)i];
@@ -1118,14 +1108,14 @@ int svr_pvr_register_patches(svr_ctx *ctx, const float *RI2W, const float *Mo, c
   const size_t mb = 16 * sizeof(float) * (size_t)n;
   std::vector<float> M(16 * (size_t)n);
   for (int i = 0; i < n; ++i) matmul4(T + 16 * (size_t)i, Mo + 16 * (size_t)i, &M[16 * (size_t)i]);       // initDevReconMatrices2
-  float *d_m = nullptr, *d_r = nullptr, *d_buf = nullptr, *d_tmp = nullptr, *d_half = nullptr;
-  int *d_ev = nullptr;
-  hipError_t e = hipMalloc(&d_m, mb);
-  if (e == hipSuccess) e = hipMalloc(&d_r, mb);
-  if (e == hipSuccess) e = hipMalloc(&d_buf, ctx->np * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_tmp, ctx->np * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_half, 40 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_ev, sizeof(int) * (size_t)n);
+  DevBuf<float> d_m, d_r, d_buf, d_tmp, d_half;
+  DevBuf<int> d_ev;
+  hipError_t e = d_m.reserve(16 * (size_t)n);
+  if (e == hipSuccess) e = d_r.reserve(16 * (size_t)n);
+  if (e == hipSuccess) e = d_buf.reserve(ctx->np);
+  if (e == hipSuccess) e = d_tmp.reserve(ctx->np);
+  if (e == hipSuccess) e = d_half.reserve(40);
+  if (e == hipSuccess) e = d_ev.reserve(n);
   if (e == hipSuccess) e = hipMemcpyAsync(d_m, M.data(), mb, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_r, RI2W, mb, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(d_ev, 0, sizeof(int) * (size_t)n, ctx->stream);
@@ -1159,7 +1149,6 @@ int svr_pvr_register_patches(svr_ctx *ctx, const float *RI2W, const float *Mo, c
   if (e == hipSuccess) e = hipMemcpyAsync(M.data(), d_m, mb, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(ev.data(), d_ev, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_m); (void)hipFree(d_r); (void)hipFree(d_buf); (void)hipFree(d_tmp); (void)hipFree(d_half); (void)hipFree(d_ev);
   if (e != hipSuccess) return fail(ctx, (int)e, "svr_pvr_register_patches");
   long long evals = 0;
   for (int i = 0; i < n; ++i) {

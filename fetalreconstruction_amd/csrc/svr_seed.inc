@@ -138,29 +138,31 @@ __global__ void k_seed_scale(float *__restrict__ out, const float *__restrict__ 
 int seed_run(svr_ctx *ctx, size_t ns, const uint32_t src_size[3], const float *src, const double m[12], float padding, int flags, float scale,
              float *out, double stats[5]) {
   const int blocks = (int)std::min<size_t>(SEED_MAX_BLOCKS, (ctx->nv + 255) / 256);
-  HIPCHK(hipMalloc(&ctx->d_seed_src, ns * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_seed_out, ctx->nv * sizeof(float)));
-  HIPCHK(hipMalloc(&ctx->d_seed_partial, ((size_t)blocks + 1) * 5 * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(ctx->d_seed_src, src, ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  DevBuf<float> d_src, d_out;                                  // nothing is kept beyond the call (see above)
+  DevBuf<double> d_partial;
+  HIPCHK(d_src.reserve(ns));
+  HIPCHK(d_out.reserve(ctx->nv));
+  HIPCHK(d_partial.reserve(((size_t)blocks + 1) * 5));
+  HIPCHK(hipMemcpyAsync(d_src, src, ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   SeedArgs a;
-  a.src = ctx->d_seed_src; a.mask = ctx->have_mask ? ctx->d_mask : nullptr; a.out = ctx->d_seed_out; a.partial = ctx->d_seed_partial;
+  a.src = d_src; a.mask = ctx->have_mask ? ctx->d_mask.get() : nullptr; a.out = d_out; a.partial = d_partial;
   for (int k = 0; k < 12; ++k) a.m[k] = m[k];
   a.nx = (int)src_size[0]; a.ny = (int)src_size[1]; a.nz = (int)src_size[2];
   a.vx = ctx->vx; a.vy = ctx->vy; a.nv = ctx->nv; a.padding = padding;
   hipLaunchKernelGGL(k_seed_resample, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
   KCHK("k_seed_resample");
-  double *d_stats = ctx->d_seed_partial + (size_t)blocks * 5;
-  hipLaunchKernelGGL(k_seed_finish, dim3(1), dim3(64), 0, ctx->stream, ctx->d_seed_partial, blocks, d_stats);
+  double *d_stats = d_partial + (size_t)blocks * 5;
+  hipLaunchKernelGGL(k_seed_finish, dim3(1), dim3(64), 0, ctx->stream, d_partial, blocks, d_stats);
   KCHK("k_seed_finish");
   if (flags & SVR_RESAMPLE_SCALE) {
-    hipLaunchKernelGGL(k_seed_scale, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_seed_out, a.mask, padding, scale, ctx->nv);
+    hipLaunchKernelGGL(k_seed_scale, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_out, a.mask, padding, scale, ctx->nv);
     KCHK("k_seed_scale");
   }
   if (flags & SVR_RESAMPLE_INSTALL) {
-    HIPCHK(hipMemcpyAsync(ctx->recon(), ctx->d_seed_out, ctx->nv * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->recon(), d_out, ctx->nv * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     invalidate(ctx, CH_VOLUME_VALUES);
   }
-  if (out) HIPCHK(hipMemcpyAsync(out, ctx->d_seed_out, ctx->nv * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out) HIPCHK(hipMemcpyAsync(out, d_out, ctx->nv * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipMemcpyAsync(stats, d_stats, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
@@ -187,9 +189,7 @@ int svr_resample_to_reconstruction(svr_ctx *ctx, const uint32_t src_size[3], con
   if (!std::isfinite(padding) || ((flags & SVR_RESAMPLE_SCALE) && !std::isfinite(scale)))
     return fail(ctx, SVR_E_ARG, "svr_resample_to_reconstruction: padding / scale not finite");
   NEED(ctx->nv > 0, "InitReconstructionVolume first");
-  const int r = seed_run(ctx, ns, src_size, src, src_from_recon, padding, flags, scale, out_or_null, stats);
-  free_dev(ctx->d_seed_src); free_dev(ctx->d_seed_out); free_dev(ctx->d_seed_partial);   // nothing is kept (see above)
-  return r;
+  return seed_run(ctx, ns, src_size, src, src_from_recon, padding, flags, scale, out_or_null, stats);
 }
 
 }  // extern "C"

@@ -50,7 +50,7 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
 }
 
 // ---- the evaluate calls' device scratch and launch chain ------------------------------------------------------------------------
-// One grow-only arena of the context (d_sim_io, sim_cap, sim_staging) serves svr_ncc_evaluate, svr_nmi_evaluate and
+// One grow-only arena of the context (d_sim_io, sim_staging) serves svr_ncc_evaluate, svr_nmi_evaluate and
 // svr_lncc_evaluate: inputs | outputs | optional test map, each part at 8-byte alignment.  sim_evaluate checks the target indices,
 // grows the arena (3/2 of the need, at least `floor` bytes), stages the inputs and uploads them in one copy, runs the caller's
 // launch(d_in, d_out, d_map), downloads the outputs (and the map) and waits.
@@ -64,13 +64,7 @@ int sim_evaluate(svr_ctx *ctx, const char *name, const int *target_index, size_t
   size_t b_in = 0;
   for (const SimSeg &s : inputs) b_in += s.bytes;
   const size_t o_out = (b_in + 7) / 8 * 8, o_map = (o_out + b_out + 7) / 8 * 8, need = o_map + b_map;
-  if (need > ctx->sim_cap) {
-    free_dev(ctx->d_sim_io);
-    ctx->sim_cap = 0;
-    const size_t cap = std::max(floor, need * 3 / 2 + 4096);
-    HIPCHK(hipMalloc(&ctx->d_sim_io, cap));
-    ctx->sim_cap = cap;
-  }
+  if (need > ctx->d_sim_io.capacity()) HIPCHK(ctx->d_sim_io.reserve(std::max(floor, need * 3 / 2 + 4096)));
   ctx->sim_staging.resize(b_in);
   size_t at = 0;
   for (const SimSeg &s : inputs) { memcpy(ctx->sim_staging.data() + at, s.p, s.bytes); at += s.bytes; }
@@ -135,9 +129,9 @@ int svr_ncc_set_targets(svr_ctx *ctx, int n, int tx, int ty, const int16_t *targ
   SVR_ENTER(ctx);
   if (!ctx || !targets || n <= 0 || tx <= 0 || ty <= 0) return SVR_E_ARG;
   HIPCHK(hipSetDevice(ctx->device));
-  free_dev(ctx->d_reg_targets);
+  ctx->d_reg_targets.reset();
   const size_t bytes = (size_t)n * tx * ty * sizeof(short);
-  HIPCHK(hipMalloc(&ctx->d_reg_targets, bytes));
+  HIPCHK(ctx->d_reg_targets.reserve((size_t)n * tx * ty));
   HIPCHK(hipMemcpyAsync(ctx->d_reg_targets, targets, bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->reg_n = n; ctx->reg_tx = tx; ctx->reg_ty = ty;
@@ -152,8 +146,8 @@ int svr_ncc_set_source(svr_ctx *ctx, const uint32_t size[3], const int16_t *sour
            sz = source_or_null ? size[2] : ctx->vz;
   const size_t n = (size_t)sx * sy * sz;
   if (n == 0) return SVR_E_ARG;
-  free_dev(ctx->d_reg_source);
-  HIPCHK(hipMalloc(&ctx->d_reg_source, n * sizeof(short)));
+  ctx->d_reg_source.reset();
+  HIPCHK(ctx->d_reg_source.reserve(n));
   if (source_or_null) {
     HIPCHK(hipMemcpyAsync(ctx->d_reg_source, source_or_null, n * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
   } else {

@@ -28,23 +28,18 @@
 
 struct SlabPlan {
   bool valid = false;
-  uint32_t *d_midx = nullptr, *d_didx = nullptr;     // voxel indices of mask != 0 / of its 3x3x3 dilation, natural order
+  DevBuf<uint32_t> d_midx, d_didx;                   // voxel indices of mask != 0 / of its 3x3x3 dilation, natural order
   uint32_t nm = 0, nd = 0;
   std::vector<uint32_t> mcum, dcum;                  // [vz + 1] mask / dilated voxels in the planes below z
   int world = 0, rank = -1;
   std::vector<int> zb;                               // [world + 1] slab r = planes [zb[r], zb[r + 1])
   std::vector<uint32_t> rs_start, rs_count, ag_start, ag_count;   // per rank: range of d_midx (slab + halo planes) / of d_didx (slab)
   uint32_t rs_chunk = 0, ag_chunk = 0;               // floats per rank and volume (padded to the largest rank's)
-  float *d_send = nullptr, *d_recv = nullptr;        // [world][2][rs_chunk] | [2][rs_chunk]; then [ag_chunk] | [world][ag_chunk]
-  size_t cap_send = 0, cap_recv = 0;
-  uint32_t *d_tab = nullptr;                         // [4][world] rs_start, rs_count, ag_start, ag_count on the device
+  DevBuf<float> d_send, d_recv;                      // [world][2][rs_chunk] | [2][rs_chunk]; then [ag_chunk] | [world][ag_chunk]
+  DevBuf<uint32_t> d_tab;                            // [4][world] rs_start, rs_count, ag_start, ag_count on the device
 };
 
-void slab_free(SlabPlan *p) {
-  if (!p) return;
-  free_dev(p->d_midx); free_dev(p->d_didx); free_dev(p->d_send); free_dev(p->d_recv); free_dev(p->d_tab);
-  delete p;
-}
+void slab_free(SlabPlan *p) { delete p; }
 
 __global__ void k_slab_flags(const float *mask, int vx, int vy, int vz, uint32_t *fm, uint32_t *fd) {
   const size_t n = (size_t)vx * vy * vz;
@@ -103,36 +98,31 @@ __global__ void k_slab_ag_unpack(float *vol, const uint32_t *didx, const uint32_
 
 static int slab_lists(svr_ctx *ctx, SlabPlan &p) {
   const size_t n = ctx->nv, plane = (size_t)ctx->vx * ctx->vy;
-  uint32_t *fm = nullptr, *fd = nullptr, *sc = nullptr, *d_cum = nullptr;
-  void *tmp = nullptr;
+  DevBuf<uint32_t> fm, fd, sc, d_cum;
+  DevBuf<unsigned char> tmp;
   size_t tb = 0;
-  auto cleanup = [&]() { free_dev(fm); free_dev(fd); free_dev(sc); free_dev(d_cum); free_dev(tmp); };
-  int rc = SVR_OK;
-  do {
-    if (hipMalloc(&fm, n * 4) != hipSuccess || hipMalloc(&fd, n * 4) != hipSuccess || hipMalloc(&sc, n * 4) != hipSuccess ||
-        hipMalloc(&d_cum, ((size_t)ctx->vz + 1) * 4) != hipSuccess) { rc = fail(ctx, SVR_E_STATE, "slab plan: out of device memory"); break; }
-    hipLaunchKernelGGL(k_slab_flags, dim3(nblk(n)), dim3(256), 0, ctx->stream, ctx->d_mask, (int)ctx->vx, (int)ctx->vy, (int)ctx->vz, fm, fd);
-    if (svr_inclusive_sum_u32(nullptr, &tb, fm, sc, n, ctx->stream)) { rc = fail(ctx, SVR_E_STATE, "slab plan: scan (size query)"); break; }
-    if (hipMalloc(&tmp, tb ? tb : 1) != hipSuccess) { rc = fail(ctx, SVR_E_STATE, "slab plan: out of device memory"); break; }
-    for (int pass = 0; pass < 2 && !rc; ++pass) {
-      uint32_t *&idx = pass ? p.d_didx : p.d_midx;
-      std::vector<uint32_t> &cum = pass ? p.dcum : p.mcum;
-      size_t t2 = tb;
-      if (svr_inclusive_sum_u32(tmp, &t2, pass ? fd : fm, sc, n, ctx->stream)) { rc = fail(ctx, SVR_E_STATE, "slab plan: scan"); break; }
-      hipLaunchKernelGGL(k_slab_plane_cum, dim3(nblk((size_t)ctx->vz + 1)), dim3(256), 0, ctx->stream, sc, plane, (int)ctx->vz, d_cum);
-      cum.assign((size_t)ctx->vz + 1, 0u);
-      if (hipMemcpyAsync(cum.data(), d_cum, cum.size() * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = fail(ctx, SVR_E_STATE, "slab plan: copy"); break; }
-      const uint32_t cnt = cum.back();
-      (pass ? p.nd : p.nm) = cnt;
-      free_dev(idx);
-      if (hipMalloc(&idx, (size_t)std::max(cnt, 1u) * 4) != hipSuccess) { rc = fail(ctx, SVR_E_STATE, "slab plan: out of device memory"); break; }
-      hipLaunchKernelGGL(k_slab_compact, dim3(nblk(n)), dim3(256), 0, ctx->stream, sc, n, idx);
-    }
-    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, SVR_E_STATE, "slab plan: kernels");
-  } while (0);
-  cleanup();
-  return rc;
+  if (fm.reserve(n) != hipSuccess || fd.reserve(n) != hipSuccess || sc.reserve(n) != hipSuccess ||
+      d_cum.reserve((size_t)ctx->vz + 1) != hipSuccess) return fail(ctx, SVR_E_STATE, "slab plan: out of device memory");
+  hipLaunchKernelGGL(k_slab_flags, dim3(nblk(n)), dim3(256), 0, ctx->stream, ctx->d_mask, (int)ctx->vx, (int)ctx->vy, (int)ctx->vz, fm, fd);
+  if (svr_inclusive_sum_u32(nullptr, &tb, fm, sc, n, ctx->stream)) return fail(ctx, SVR_E_STATE, "slab plan: scan (size query)");
+  if (tmp.reserve(tb ? tb : 1) != hipSuccess) return fail(ctx, SVR_E_STATE, "slab plan: out of device memory");
+  for (int pass = 0; pass < 2; ++pass) {
+    DevBuf<uint32_t> &idx = pass ? p.d_didx : p.d_midx;
+    std::vector<uint32_t> &cum = pass ? p.dcum : p.mcum;
+    size_t t2 = tb;
+    if (svr_inclusive_sum_u32(tmp, &t2, pass ? fd : fm, sc, n, ctx->stream)) return fail(ctx, SVR_E_STATE, "slab plan: scan");
+    hipLaunchKernelGGL(k_slab_plane_cum, dim3(nblk((size_t)ctx->vz + 1)), dim3(256), 0, ctx->stream, sc, plane, (int)ctx->vz, d_cum);
+    cum.assign((size_t)ctx->vz + 1, 0u);
+    if (hipMemcpyAsync(cum.data(), d_cum, cum.size() * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, SVR_E_STATE, "slab plan: copy");
+    const uint32_t cnt = cum.back();
+    (pass ? p.nd : p.nm) = cnt;
+    idx.reset();
+    if (idx.reserve(std::max(cnt, 1u)) != hipSuccess) return fail(ctx, SVR_E_STATE, "slab plan: out of device memory");
+    hipLaunchKernelGGL(k_slab_compact, dim3(nblk(n)), dim3(256), 0, ctx->stream, sc, n, idx);
+  }
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, SVR_E_STATE, "slab plan: kernels");
+  return SVR_OK;
 }
 
 // the plan of (mask, world, rank); chunk sizes in floats per rank (rs: both volumes of a rank's slab + halo; ag: a rank's slab)
@@ -170,13 +160,13 @@ static int slab_plan(svr_ctx *ctx, int world, int rank) {
   std::vector<uint32_t> tab;
   tab.insert(tab.end(), p.rs_start.begin(), p.rs_start.end()); tab.insert(tab.end(), p.rs_count.begin(), p.rs_count.end());
   tab.insert(tab.end(), p.ag_start.begin(), p.ag_start.end()); tab.insert(tab.end(), p.ag_count.begin(), p.ag_count.end());
-  free_dev(p.d_tab);
-  HIPCHK(hipMalloc(&p.d_tab, tab.size() * 4));
+  p.d_tab.reset();
+  HIPCHK(p.d_tab.reserve(tab.size()));
   HIPCHK(hipMemcpyAsync(p.d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const size_t need_send = std::max((size_t)world * 2 * p.rs_chunk, (size_t)p.ag_chunk), need_recv = std::max((size_t)2 * p.rs_chunk, (size_t)world * p.ag_chunk);
-  if (need_send > p.cap_send) { free_dev(p.d_send); p.cap_send = 0; HIPCHK(hipMalloc(&p.d_send, need_send * 4)); p.cap_send = need_send; }
-  if (need_recv > p.cap_recv) { free_dev(p.d_recv); p.cap_recv = 0; HIPCHK(hipMalloc(&p.d_recv, need_recv * 4)); p.cap_recv = need_recv; }
+  HIPCHK(p.d_send.reserve(need_send));
+  HIPCHK(p.d_recv.reserve(need_recv));
   p.world = world; p.rank = rank;
   return SVR_OK;
 }

@@ -133,18 +133,20 @@ int slice_ssim_run(svr_ctx *ctx, int R, double c1, double c2, double *sums, floa
   const size_t tiles = (size_t)tiles_x * tiles_y, blocks = (size_t)ctx->ns * tiles, nout = (size_t)ctx->ns * 2;
   if (tiles >= (1ull << 31) || blocks >= (1ull << 31) || nout >= (1ull << 31)) return fail(ctx, SVR_E_ARG, "svr_slice_ssim: too many slices");
   const float *bias = ctx->disable_bias ? (const float *)nullptr : ctx->d_bias;
-  HIPCHK(hipMalloc(&ctx->d_ssim_partial, blocks * 2 * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_ssim_sums, nout * sizeof(double)));
-  if (map) HIPCHK(hipMalloc(&ctx->d_ssim_map, ctx->np * sizeof(float)));
+  DevBuf<double> d_partial, d_sums;                          // nothing is kept beyond the call
+  DevBuf<float> d_map;
+  HIPCHK(d_partial.reserve(blocks * 2));
+  HIPCHK(d_sums.reserve(nout));
+  if (map) HIPCHK(d_map.reserve(ctx->np));
   hipLaunchKernelGGL(bias ? k_slice_ssim<true> : k_slice_ssim<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_slices,
                      ctx->d_simslices, ctx->d_simweights, ctx->d_scales_host_copy, bias, sx, sy, tiles_x, (int)tiles, R, c1, c2,
-                     ctx->d_ssim_partial, map ? ctx->d_ssim_map : (float *)nullptr);
+                     d_partial.get(), d_map.get());
   KCHK("k_slice_ssim");
-  hipLaunchKernelGGL(k_slice_ssim_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ssim_partial, (int)ctx->ns,
-                     (int)tiles, ctx->d_ssim_sums);
+  hipLaunchKernelGGL(k_slice_ssim_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, d_partial.get(), (int)ctx->ns,
+                     (int)tiles, d_sums.get());
   KCHK("k_slice_ssim_finish");
-  HIPCHK(hipMemcpyAsync(sums, ctx->d_ssim_sums, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (map) HIPCHK(hipMemcpyAsync(map, ctx->d_ssim_map, ctx->np * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(sums, d_sums.get(), nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (map) HIPCHK(hipMemcpyAsync(map, d_map.get(), ctx->np * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
@@ -165,9 +167,7 @@ int svr_slice_ssim(svr_ctx *ctx, int radius, double c1, double c2, double *sums,
   NEED(ctx->have_sim, "no simulated slices (svr_simulate_slices first)");
   int r = ensure_bias_buffers(ctx);                          // (as every compute call: a bias path switched on before the slice grid existed)
   if (r) return r;
-  r = slice_ssim_run(ctx, radius, c1, c2, sums, map_or_null);
-  free_dev(ctx->d_ssim_partial); free_dev(ctx->d_ssim_sums); free_dev(ctx->d_ssim_map);   // nothing is kept
-  return r;
+  return slice_ssim_run(ctx, radius, c1, c2, sums, map_or_null);
 }
 
 }  // extern "C"

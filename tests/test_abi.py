@@ -96,3 +96,21 @@ def test_the_hand_written_slice_of_rccl_h_matches_the_image_s_header(tmp_path):
         (d / "check.cpp").write_text(chk)
         bad = subprocess.run(cmd + ["-I" + str(d), str(d / "check.cpp")], capture_output=True, text=True)
         assert bad.returncode != 0 and what in bad.stderr, (what, bad.stderr[-1500:])
+
+
+def test_devbuf_on_counting_stand_ins_under_the_sanitizers(tmp_path):
+    """csrc/svr_devbuf.h owns every device allocation of the engine.  tests/devbuf_check.cpp drives it on counting stand-ins for hipMalloc /
+    hipFree (malloc / free, with a switch that fails the next allocation): no allocation at or below the capacity, free before allocate and
+    exactly n * sizeof(T) on growth, empty after a failed growth, moves, reset twice, as many frees as allocations -- built with
+    -fsanitize=address,undefined and run as a program of its own."""
+    import shutil
+    import subprocess
+    import pytest
+    if not shutil.which("g++"):
+        pytest.skip("no g++ in this image")
+    exe = tmp_path / "devbuf_check"
+    cc = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                         os.path.join(ROOT, "tests", "devbuf_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr[-3000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.startswith("ok:"), (run.stdout[-1500:], run.stderr[-3000:])
