@@ -1222,6 +1222,7 @@ struct svr_ctx {
   // registration cost (NCC)
   DevBuf<short> d_reg_targets, d_reg_source;
   DevBuf<short> d_pyr_full[2], d_pyr_a, d_pyr_b;   // device pyramid of the registration (svr_pyr_*)
+  size_t pyr_count[2] = {0, 0};                    // the elements the last svr_pyr_upload put into each slot (a kept block may be larger and hold an older upload's tail)
   DevBuf<unsigned char> d_pyr_meta;
   DevBuf<unsigned char> d_sim_io;        // grow-only arena of svr_ncc / svr_nmi / svr_lncc_evaluate (sim_evaluate, svr_sim.inc): inputs | outputs | test map
   std::vector<unsigned char> sim_staging;
@@ -2420,6 +2421,7 @@ int svr_init_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const float d
   if (np == 0 || np >= (1ull << 31)) return fail(ctx, SVR_E_ARG, "slice grid out of range: 1 .. 2^31 - 1 pixels per context (shard the slices over more ranks)");
   free_slices(ctx);
   ctx->d_bias.reset(); ctx->d_wb.reset(); ctx->d_wr.reset(); ctx->d_buffer.reset();
+  ctx->d_spx.reset();                                     // the superpixel masks are indexed by the old grid's slices: svr_set_spx_masks comes after the grid
   ctx->sx = size[0]; ctx->sy = size[1]; ctx->ns = size[2];
   ctx->np = np;
   ctx->have_slices = false; ctx->have_sim = false; ctx->have_scales = false; ctx->have_dims = false; ctx->have_mats = false;

@@ -149,9 +149,11 @@ int svr_pyr_upload(svr_ctx *ctx, int slot, const int16_t *images, size_t count) 
   SVR_ENTER(ctx);
   if (!ctx || !images || count == 0 || slot < 0 || slot > 1) return SVR_E_ARG;
   HIPCHK(hipSetDevice(ctx->device));
+  ctx->pyr_count[slot] = 0;                               // (the elements that were uploaded, not the block's size: none until the copy below is through)
   HIPCHK(ctx->d_pyr_full[slot].reserve(count));
   HIPCHK(hipMemcpyAsync(ctx->d_pyr_full[slot], images, count * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->pyr_count[slot] = count;
   return SVR_OK;
 }
 
@@ -165,7 +167,8 @@ int svr_pyr_level(svr_ctx *ctx, int slot, size_t offset, int n_images, const int
   const size_t nin = (size_t)in_dims[0] * in_dims[1] * in_dims[2], nout = (size_t)out_dims[0] * out_dims[1] * out_dims[2];
   if (nin == 0 || nout == 0 || nin >= (1ull << 31) || nout >= (1ull << 31)) return fail(ctx, SVR_E_ARG, "svr_pyr_level: image size out of range");
   if (n_images > 65535) return fail(ctx, SVR_E_ARG, "svr_pyr_level: at most 65535 images of one grid per call");
-  NEED(ctx->d_pyr_full[slot] && offset + nin * n_images <= ctx->d_pyr_full[slot].capacity(), "svr_pyr_upload first");
+  // against what the last upload holds, not the block's capacity: a kept block keeps an earlier, larger upload's tail
+  NEED(ctx->d_pyr_full[slot] && offset <= ctx->pyr_count[slot] && nin * n_images <= ctx->pyr_count[slot] - offset, "svr_pyr_upload first");
   if (!resample && nout != nin) return fail(ctx, SVR_E_ARG, "svr_pyr_level: a level that keeps the grid keeps its size");
   if (slot == 1) {
     NEED(ctx->d_reg_targets, "svr_ncc_alloc_targets first");

@@ -77,7 +77,8 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value);
  * PVRreconstructionGPU (patchBasedPSFReconstruction_gpu.cu, patchBasedSimulatePatches_gpu.cu,
  * patchBasedSuperresolution_gpu.cu): patches are handed over as the "slices" of the padded grid,
  * patch.scale / patch.patchWeight as the scale / slice-weight vectors.  Optional superpixel masks:
- * ImagePatch2D::spxMask, n_patches * 64*64 chars of '0'/'1' (NULL clears them). */
+ * ImagePatch2D::spxMask, n_patches * 64*64 chars of '0'/'1' (NULL clears them).  They belong to the slice grid: call this
+ * after svr_init_storage_volumes, which drops the masks of the grid before. */
 int svr_set_spx_masks(svr_ctx *ctx, const char *masks_or_null);
 
 /* ---- geometry / state upload -------------------------------------------------------- */
@@ -272,7 +273,8 @@ int svr_ncc_set_targets(svr_ctx *ctx, int n, int tx, int ty, const int16_t *targ
  * makes.  svr_pyr_upload keeps the unprocessed images of a registration pass on the device (slot 0: the source volume,
  * slot 1: the targets, images of one grid back to back); svr_pyr_level makes one level of `n_images` images of one grid
  * starting at element `offset` of the slot and leaves them where svr_ncc_evaluate reads them: slot 0 -> the NCC source
- * (n_images must be 1), slot 1 -> the target planes from `first_plane` on (svr_ncc_alloc_targets first).
+ * (n_images must be 1), slot 1 -> the target planes from `first_plane` on (svr_ncc_alloc_targets first).  The images of a
+ * level must lie inside the slot's LAST upload (`count` elements); a range that ends beyond it is refused.
  * kernel_x/y/z: the sampled Gaussian of each pass (size 0 = no pass on that axis); resample 0 = the level keeps the grid.
  * min_out / max_out[n_images]: range of the values above the padding before the shift (max < min: none). */
 typedef struct svr_pyr_image {
