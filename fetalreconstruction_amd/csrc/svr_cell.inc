@@ -481,6 +481,9 @@ struct SlotSum {
 #ifndef SVR_CELL_RING
 #define SVR_CELL_RING 2   // table rows in flight per slot (three: 168 VGPRs and 272 bytes of scratch)
 #endif
+#ifndef SVR_CELL_RING_ASM
+#define SVR_CELL_RING_ASM 1   // support-16 table scatter: the ring's loads issued and waited for by the kernel itself (gload16 / gload_wait); 0: the counted ring
+#endif
 // Wavefronts per SIMD the support-12 (patch-based) instantiations are compiled for.  They need 134-135 VGPRs when left at 3; at 4 the compiler
 // fits them into 128 with 48 bytes of scratch in the per-run set-up code (none in the row loop).  The issue rate of packed f32 rises from
 // 0.433 to 0.465e9 per SIMD with the fourth wavefront (profiles/r04_issue_rate.txt): the gather takes it (PVR4 8.27 -> 8.03 ms, PVR8spx
@@ -616,7 +619,74 @@ void back_cell_kernel(PsfArgs a, CellArgs ca, uint32_t b0) {
           u.bx = __shfl(r0.bx, src, 64); u.by = __shfl(r0.by, src, 64); u.bz = __shfl(r0.bz, src, 64);
         };
         if (ca.dbg == 0) {
-          if (COEFF == 1) {
+          if constexpr (COEFF == 1 && NS == 16 && !PVR && SVR_CELL_RING_ASM) {
+            // The support-16 table scatter (§5.1h): two units per slot in flight in a register ring the compiler cannot shorten.  The rows are loaded
+            // by gload16 (inline asm, not counted by hipcc: no s_waitcnt of its in front of the ring's readers, no copies of the ring parked behind
+            // one at the loop header -- what it makes of the counted ring of the branch below) and the kernel counts its own waits.  One back edge, no
+            // break: a trip uses entry 0, reissues it, uses entry 1, reissues it, and EVERY issue is four loads from every lane -- a lane whose slot has
+            // no further live unit reads the table's first bytes (as the gather's issue() does) and, its rowok false, writes nothing -- so the number
+            // of operations in flight depends neither on the lane nor on the trip.  The units of a slot are taken in the order of the branch below and
+            // added with the same fma2 into the same private box: the same bits.
+            constexpr int HQ = NS / 4;
+            nt_f4 ring[2][HQ];
+            Unit ru[2];
+            bool rv[2];
+            auto issue = [&](Unit &u, bool &valid, nt_f4 (&dst)[HQ]) {
+              valid = ml != 0u;
+              const int j = valid ? __builtin_ctz(ml) : 0;
+              ml &= ml - 1u;
+              u = fetch(j);
+              const float4 *row = valid ? coeff_row<NS>(a.coeff, (uint32_t)u.pid, P - u.cz + NC, y) : a.coeff + lane;
+              gload16<0 * CoeffLayout<NS>::ROW_PITCH * 16>(row, dst[0]);
+              gload16<1 * CoeffLayout<NS>::ROW_PITCH * 16>(row, dst[1]);
+              gload16<2 * CoeffLayout<NS>::ROW_PITCH * 16>(row, dst[2]);
+              gload16<3 * CoeffLayout<NS>::ROW_PITCH * 16>(row, dst[3]);
+            };
+            // (the ring lives inside this one condition, from its first issue to its drain, and the loop leaves from its bottom only: no path on
+            // which the compiler has to carry ring registers next to their successors, which it does by copying them -- while they are in flight)
+            if (__any(ml != 0u)) {
+            issue(ru[0], rv[0], ring[0]);
+            issue(ru[1], rv[1], ring[1]);
+            do {
+#pragma unroll
+              for (int r3 = 0; r3 < 2; ++r3) {
+                // this entry's four loads: the other entry's four, issued after them, stay in flight.  The kernel's other vector-memory operations
+                // around here are the next run's or chunk's recs / pid loads (request_run); wherever the compiler puts them, an operation younger
+                // than the loads waited for makes this wait stricter by itself at most, an older one has returned with them: never looser.
+                gload_wait<HQ>(ring[r3]);
+                const Unit u = ru[r3];
+                const bool valid = rv[r3];
+                if (r3 == 0 || __any(valid)) {              // (the odd tail: the last trip has entry 0 only)
+                  const int ay = u.cy + y - NC;
+                  const bool rowok = valid && ay < vgy;
+                  const int rbx = rowok ? (ay - loy) * PL + u.cx - NC : lox;
+                  // (the row in two halves -- the accumulators of a whole row next to the ring do not fit 168 registers)
+                  constexpr int PARTS = 2, PT = NS / PARTS;
+                  const f2 ff = (f2){u.f0, u.f1};
+#pragma unroll
+                  for (int hq = 0; hq < PARTS; ++hq) {
+                    f2 acc[PT];
+#pragma unroll
+                    for (int x = 0; x < PT; ++x) acc[x] = pb[rbx + hq * PT + x];
+                    if (rowok) {
+#pragma unroll
+                      for (int q = 0; q < PT / 4; ++q) {
+                        const nt_f4 c = ring[r3][hq * (PT / 4) + q];
+                        pb[rbx + hq * PT + 4 * q] = fma2(bc2(c.x), ff, acc[4 * q]);
+                        pb[rbx + hq * PT + 4 * q + 1] = fma2(bc2(c.y), ff, acc[4 * q + 1]);
+                        pb[rbx + hq * PT + 4 * q + 2] = fma2(bc2(c.z), ff, acc[4 * q + 2]);
+                        pb[rbx + hq * PT + 4 * q + 3] = fma2(bc2(c.w), ff, acc[4 * q + 3]);
+                      }
+                    }
+                  }
+                }
+                issue(ru[r3], rv[r3], ring[r3]);
+              }
+            } while (__any(rv[0]));
+            // the end of the chunk's lists: the ring is drained (its last two issues carry no unit) before its registers go to anybody else
+            gload_wait<0>(ring[0], ring[1]);
+            }
+          } else if (COEFF == 1) {
             // the taps come from the coefficient table: a ring of RING units per slot in flight (support 12, PVR4: two 5.8 ms, three
             // 6.1 ms, four spill: 9.5 ms)
             constexpr int RING = SVR_CELL_RING;

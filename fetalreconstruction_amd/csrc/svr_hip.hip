@@ -787,14 +787,35 @@ __device__ __forceinline__ float4 load_stream(const float4 *p) {
 // the data is in flight for as long as the kernel likes, and the kernel counts its completion itself (glds_wait) before it reads the LDS.
 // M0 holds the destination and is compiler-reserved: saved and restored inside the statement.  (hipcc does not count this load in its
 // own s_waitcnt bookkeeping; an uncounted older operation only makes the compiler's counted waits stricter, never looser: vmcnt is in order.)
+// The stage written here is one the wavefront has read before (ds_read): the statement opens with s_waitcnt lgkmcnt(0), so that every LDS read
+// issued so far has returned before the DMA can write over its source -- the "memory" clobber orders the issue only, not the completion.
 __device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
   unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 // wait until at most N vector-memory operations of this wavefront are outstanding (N an immediate), then the LDS may be read
 template <int N>
 __device__ __forceinline__ void glds_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+
+// 16 bytes per lane from global memory into a VGPR quad, non-temporal, OFF bytes beyond gsrc (an immediate), by a load that hipcc does not count:
+// the compiler puts no s_waitcnt of its own in front of the registers' readers and has no reason to park them in copies behind one, so the data
+// stay in flight until the kernel's own wait (gload_wait), which names every destination register of the unit about to be used as "+v" -- no
+// consumer can be scheduled above it.  Until then `dst` is not to be read, copied or left to die: a unit that is not used is still waited for.
+// (As with glds16: an operation hipcc does not count only makes its own counted waits stricter, vmcnt returns in order.)
+template <int OFF>
+__device__ __forceinline__ void gload16(const void *gsrc, nt_f4 &dst) {
+  asm volatile("global_load_dwordx4 %0, %1, off offset:%2 nt" : "=&v"(dst) : "v"(gsrc), "n"(OFF) : "memory");
+}
+// wait until at most N vector-memory operations are outstanding; the four quads of one row (support 16) / of two rows become readable
+template <int N>
+__device__ __forceinline__ void gload_wait(nt_f4 (&r)[4]) {
+  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void gload_wait(nt_f4 (&r)[4], nt_f4 (&s)[4]) {
+  asm volatile("s_waitcnt vmcnt(%8)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]) : "n"(N) : "memory");
+}
 __device__ __forceinline__ uint32_t lds_addr_of(const void *p) { return (uint32_t)(uintptr_t)p; }   // (a generic pointer into the LDS: aperture in the high half, LDS byte address in the low)
 
 #ifndef SVR_COEFF_STORE_NT
