@@ -374,7 +374,8 @@ __global__ void k_cell_entries(CellArgs ca, uint32_t nitems, const uint32_t *ite
 // the factors of every sorted pixel: what back_wave_kernel's "lane = pixel" part works out (RC.cu:439-447 / 278-282).
 // gauss: 0 = the SR scatter, 1 = pass 2 of the Gaussian reconstruction, 2 = NormaliseBias (normalizeBiasKernel3D_tex RC.cu:544-550, 591:
 // weight psf / sume, value the pixel's log bias minus the log of its slice's scale), 3 = a channel (svr_channel_scatter: the SR scatter's weight, the
-// value read from a.channel)
+// value read from a.channel), 4 = an SR iteration on a channel (svr_channel_sr_backproject: that weight where the channel's forward projection has a
+// sim-weight > 0, the value a.channel minus that projection)
 __global__ void k_cell_factors(PsfArgs a, int gauss, CellRec *recs, uint32_t n, unsigned char *act) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -389,6 +390,17 @@ __global__ void k_cell_factors(PsfArgs a, int gauss, CellRec *recs, uint32_t n, 
       const float x = (a.ch_flags & SVR_CHANNEL_INDICATOR) ? (c == a.ch_match ? 1.0f : 0.0f) : c;
       f1 = (a.weights[idx] * a.slice_weights[sl]) / a.psf_sums[idx];
       f0 = f1 * x;
+    }
+    recs[i].f0 = f0; recs[i].f1 = f1;    // (never the pass that writes the table: act is NULL)
+    return;
+  }
+  if (gauss == 4) {
+    // an SR iteration on a channel (svr_channel_sr_backproject): mode 3's pixel set and weight, the residual against the channel's own forward
+    // projection (a.simslices / a.simweights are the call's buffers).  The gate is the sim-weight, not the sign of the simulated value
+    const uint32_t sl = idx / (uint32_t)(a.sx * a.sy);
+    if (pixel_active(a.slices, a.psf_sums, nullptr, idx) && (!a.unit_on || a.unit_on[sl] != 0) && a.simweights[idx] > 0.0f) {
+      f1 = (a.weights[idx] * a.slice_weights[sl]) / a.psf_sums[idx];
+      f0 = f1 * (a.channel[idx] - a.simslices[idx]);
     }
     recs[i].f0 = f0; recs[i].f1 = f1;    // (never the pass that writes the table: act is NULL)
     return;

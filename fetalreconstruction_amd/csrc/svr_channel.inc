@@ -28,6 +28,9 @@
 // The channel and the per-slice switches are uploaded into buffers of the call's own and freed before it returns, like svr_slice_quality's
 // scratch: the coefficient table sizes itself by the memory that is free.  The two vote arrays live from the first vote to the fetch;
 // the invalidation map drops them with the volume grid (CH_VOLUME_GRID).
+//
+// svr_channel_sr_begin .. _end (further down) refine that average by SR iterations with the weights held fixed: the run's gather, factor
+// mode 4 of k_cell_factors, the run's scatter and the run's volume update on buffers that live from begin to end.
 
 namespace {
 
@@ -114,28 +117,36 @@ __global__ __launch_bounds__(256) void k_channel_settle(float *__restrict__ best
 inline unsigned channel_blocks(size_t nv) { return std::max(1u, nblk((nv + 3) / 4)); }
 inline bool same_16(const void *a, const void *b) { return ((reinterpret_cast<uintptr_t>(a) ^ reinterpret_cast<uintptr_t>(b)) & 15u) == 0; }
 
-int channel_scatter_run(svr_ctx *ctx, const float *channel, const unsigned char *unit_on, int flags, float match) {
+// What a channel scatter needs before its buffers: the PSF list, addon | cmap no longer the SR scatter's, the cell lists.  *empty: no PSF pixel,
+// addon | cmap are zero and there is nothing to launch
+int channel_scatter_prepare(svr_ctx *ctx, const char *who, bool *empty) {
   int r = ensure_psf_list(ctx);
   if (r) return r;
   // the SR scatter's Prep may still be owed to addon | cmap (k_regul_fused leaves it to their next reader): what lands there now is not its
   ctx->prep_pending = false;
   invalidate(ctx, CH_SCATTER_TARGETS);
-  if (!ctx->n_psf) {                                        // no PSF pixel: nothing covers any voxel
+  *empty = !ctx->n_psf;
+  if (*empty) {                                             // no PSF pixel: nothing covers any voxel
     HIPCHK(hipMemsetAsync(ctx->d_addon_cmap, 0, 2 * ctx->nv * sizeof(float), ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SVR_OK;
   }
   if ((r = cell_prepare(ctx))) return r;
   if (!ctx->cell || !ctx->cell->usable)
-    return fail(ctx, SVR_E_STATE, "svr_channel_scatter: the cell lists cannot hold this geometry, and channels have no fallback onto the atomic scatters");
-  DevBuf<float> d_channel;                                  // the channel and its per-slice switches: nothing is kept beyond the call (the
-  DevBuf<unsigned char> d_unit_on;                          // coefficient table sizes itself by the memory that is free)
+    return fail(ctx, SVR_E_STATE, std::string(who) + ": the cell lists cannot hold this geometry, and channels have no fallback onto the atomic scatters");
+  return SVR_OK;
+}
+int channel_upload(svr_ctx *ctx, const float *channel, const unsigned char *unit_on, DevBuf<float> &d_channel, DevBuf<unsigned char> &d_unit_on) {
   HIPCHK(d_channel.reserve(ctx->np));
   HIPCHK(hipMemcpyAsync(d_channel, channel, ctx->np * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (unit_on) {
     HIPCHK(d_unit_on.reserve(ctx->ns));
     HIPCHK(hipMemcpyAsync(d_unit_on, unit_on, ctx->ns, hipMemcpyHostToDevice, ctx->stream));
   }
+  return SVR_OK;
+}
+// the scatter itself, factor mode 3 (values) or 4 (residuals against the forward projection sim / simw) -> addon | cmap
+int channel_scatter_launch(svr_ctx *ctx, const float *d_channel, const unsigned char *d_unit_on, int flags, float match, int mode, float *sim, float *simw) {
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
@@ -143,11 +154,68 @@ int channel_scatter_run(svr_ctx *ctx, const float *channel, const unsigned char 
   a.unit_on = d_unit_on;
   a.ch_flags = flags;
   a.ch_match = match;
+  if (sim) { a.simslices = sim; a.simweights = simw; }
   if (table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
-  if ((r = launch_cell_scatter(ctx, a, 3, ctx->addon(), ctx->cmap()))) return r;
+  return launch_cell_scatter(ctx, a, mode, ctx->addon(), ctx->cmap());
+}
+
+int channel_scatter_run(svr_ctx *ctx, const float *channel, const unsigned char *unit_on, int flags, float match) {
+  bool empty = false;
+  int r = channel_scatter_prepare(ctx, "svr_channel_scatter", &empty);
+  if (r || empty) return r;
+  DevBuf<float> d_channel;                                  // the channel and its per-slice switches: nothing is kept beyond the call (the
+  DevBuf<unsigned char> d_unit_on;                          // coefficient table sizes itself by the memory that is free)
+  if ((r = channel_upload(ctx, channel, unit_on, d_channel, d_unit_on))) return r;
+  if ((r = channel_scatter_launch(ctx, d_channel, d_unit_on, flags, match, 3, nullptr, nullptr))) return r;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
+
+// ---- SR iterations on a channel (svr_channel_sr_begin / _seed / _backproject / _update / _end) ------------------------------------------
+// The run's SR loop on other values, the weights held fixed.  C0 = the average above (seed), cover = its den > 0; then per iteration
+//   sim = the forward projection of C (svr_simulate_slices's cell gather, the table when it is valid) into the call's own buffers,
+//   factor mode 4 of k_cell_factors + launch_cell_scatter -> addon | cmap,   C' = k_regul_fused(C, addon, cmap) with a clamp [lo, hi],
+// and at the end C = 0 outside cover.  The halves are separate entry points so that a sharded run can all-reduce addon | cmap in between.
+
+// C0 = den > 0 ? num / den : 0 (svr_channel_finish with background 0, not in place) and the cover mask
+__global__ __launch_bounds__(256) void k_channel_seed(const float *__restrict__ num, const float *__restrict__ den, float *__restrict__ vol,
+                                                      unsigned char *__restrict__ cover, size_t nv) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nv) return;
+  const float d = den[i];
+  vol[i] = channel_quot(num[i], d, 0.0f);
+  cover[i] = d > 0.0f ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void k_channel_uncover(float *__restrict__ vol, const unsigned char *__restrict__ cover, size_t nv) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nv && !cover[i]) vol[i] = 0.0f;
+}
+
+// step 1: the channel volume through svr_simulate_slices's gather over the (cell, plane) items into d_csr_sim / d_csr_simw.  Nothing of the primary's
+// forward projection is written; d_volm and the cell lists' staging are scratch that every pass refills
+int channel_sr_forward(svr_ctx *ctx) {
+  const PassPath p = pass_path(ctx, PASS_FORWARD);
+  const float *vol = ctx->d_csr_vol[ctx->csr_cur];
+  PsfArgs a = make_args(ctx);
+  a.list = ctx->d_psf_list;
+  a.n = ctx->n_psf;
+  a.vol = vol;
+  a.simslices = ctx->d_csr_sim; a.simweights = ctx->d_csr_simw;
+  a.siminside = ctx->d_csr_inside; a.slice_inside = ctx->d_csr_slice_inside;
+  // the table where svr_simulate_slices would stream it on the cells; a gather it would hand to the slice tiles evaluates here (the same bits)
+  if (p.may_stream_table && p.table_on_cells && table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
+  HIPCHK(hipMemsetAsync(ctx->d_csr_sim, 0, ctx->np * sizeof(float), ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_csr_simw, 0, ctx->np * sizeof(float), ctx->stream));
+  int r = pack_volm(ctx, a, vol);
+  if (r) return r;
+  CellState *gcs = nullptr;
+  if ((r = cell_prepare_gather(ctx, gcs))) return r;
+  if (!gcs || !gcs->usable)
+    return fail(ctx, SVR_E_STATE, "svr_channel_sr_backproject: the cell lists cannot hold this geometry, and channels have no fallback onto the tile kernels");
+  return launch_cell_gather(ctx, *gcs, a, false);
+}
+
+int channel_sr_refuse_order(svr_ctx *ctx, const char *who, const char *what) { return fail(ctx, SVR_E_ARG, std::string(who) + ": " + what); }
 
 }  // namespace
 
@@ -215,6 +283,125 @@ int svr_channel_vote_fetch(svr_ctx *ctx, float background_label, float *labels_o
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) r = fail(ctx, (int)e, std::string("svr_channel_vote_fetch: ") + hipGetErrorString(e));
   ctx->d_vote_best.reset(); ctx->d_vote_label.reset();     // the vote is over, whether the download worked or not
+  return r;
+}
+
+int svr_channel_sr_begin(svr_ctx *ctx, const float *channel, const unsigned char *unit_on, const float *slice_weights, int flags) {
+  SVR_ENTER(ctx);
+  if (!ctx) return SVR_E_ARG;
+  if (!channel) return fail(ctx, SVR_E_ARG, "svr_channel_sr_begin: no channel");
+  if (flags & SVR_CHANNEL_INDICATOR) return fail(ctx, SVR_E_ARG, "svr_channel_sr_begin: label indicators have no SR iterations (they keep their vote)");
+  if (flags) return fail(ctx, SVR_E_ARG, "svr_channel_sr_begin: unknown flag");
+  if (ctx->pvr) return fail(ctx, SVR_E_STATE, "svr_channel_sr_begin: not for a patch-based (pvr) context");
+  if (ctx->csr_stage) return channel_sr_refuse_order(ctx, "svr_channel_sr_begin", "a channel's SR iterations are in flight (svr_channel_sr_end first)");
+  NEED(ctx->np > 0 && ctx->have_slices, "slices not filled");
+  NEED(ctx->have_em, "no EM weights (svr_initialize_em_values first)");
+  int r = ready(ctx);
+  if (r) return r;
+  if (pass_path(ctx, PASS_BACK).family != FAM_CELLS || pass_path(ctx, PASS_FORWARD).family != FAM_CELLS)
+    return fail(ctx, SVR_E_STATE, "svr_channel_sr_begin: needs the cell scatter and the cell gather (back_mode 5, fwd_mode 2); channels have no fallback onto the other kernels");
+  if (ctx->reg_mode != 1) return fail(ctx, SVR_E_STATE, "svr_channel_sr_begin: needs the fused volume update (reg_mode 1)");
+  if (slice_weights && (r = svr_update_slice_weights(ctx, slice_weights))) return r;
+  bool empty = false;
+  if ((r = channel_scatter_prepare(ctx, "svr_channel_sr_begin", &empty))) return r;
+  // the call's memory, after whatever the passes of the run allocated (the coefficient table sizes itself by the memory that is free)
+  hipError_t e = hipSuccess;
+  if (e == hipSuccess) e = ctx->d_csr_vol[0].reserve(ctx->nv);
+  if (e == hipSuccess) e = ctx->d_csr_vol[1].reserve(ctx->nv);
+  if (e == hipSuccess) e = ctx->d_csr_cover.reserve(ctx->nv);
+  if (e == hipSuccess) e = ctx->d_csr_sim.reserve(ctx->np);
+  if (e == hipSuccess) e = ctx->d_csr_simw.reserve(ctx->np);
+  if (e == hipSuccess) e = ctx->d_csr_inside.reserve(ctx->np);
+  if (e == hipSuccess) e = ctx->d_csr_slice_inside.reserve(ctx->ns);
+  if (e == hipSuccess && (r = channel_upload(ctx, channel, unit_on, ctx->d_csr_channel, ctx->d_csr_unit_on))) { channel_sr_drop(ctx); return r; }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    channel_sr_drop(ctx);
+    return fail(ctx, (int)e, std::string("svr_channel_sr_begin: ") + hipGetErrorString(e));
+  }
+  ctx->csr_has_unit_on = unit_on != nullptr;
+  ctx->csr_cur = 0;
+  if (!empty && (r = channel_scatter_launch(ctx, ctx->d_csr_channel, ctx->csr_has_unit_on ? ctx->d_csr_unit_on.get() : nullptr, 0, 0.0f, 3, nullptr, nullptr))) {
+    channel_sr_drop(ctx);
+    return r;
+  }
+  e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) { channel_sr_drop(ctx); return fail(ctx, (int)e, std::string("svr_channel_sr_begin: ") + hipGetErrorString(e)); }
+  ctx->csr_stage = 1;
+  return SVR_OK;
+}
+
+int svr_channel_sr_seed(svr_ctx *ctx, const float *seed_or_null) {
+  SVR_ENTER(ctx);
+  if (!ctx) return SVR_E_ARG;
+  if (ctx->csr_stage != 1) return channel_sr_refuse_order(ctx, "svr_channel_sr_seed", "svr_channel_sr_begin first, and one seed per call");
+  float *vol = ctx->d_csr_vol[ctx->csr_cur];
+  hipLaunchKernelGGL(k_channel_seed, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->addon(), ctx->cmap(), vol, ctx->d_csr_cover, ctx->nv);
+  KCHK("k_channel_seed");
+  if (seed_or_null) HIPCHK(hipMemcpyAsync(vol, seed_or_null, ctx->nv * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->csr_stage = 2;
+  return SVR_OK;
+}
+
+int svr_channel_sr_backproject(svr_ctx *ctx) {
+  SVR_ENTER(ctx);
+  if (!ctx) return SVR_E_ARG;
+  if (ctx->csr_stage != 2) return channel_sr_refuse_order(ctx, "svr_channel_sr_backproject", "svr_channel_sr_seed first, and svr_channel_sr_update after every back-projection");
+  bool empty = false;
+  int r = channel_scatter_prepare(ctx, "svr_channel_sr_backproject", &empty);
+  if (r) return r;
+  if (!empty) {
+    if ((r = channel_sr_forward(ctx))) return r;
+    if ((r = channel_scatter_launch(ctx, ctx->d_csr_channel, ctx->csr_has_unit_on ? ctx->d_csr_unit_on.get() : nullptr, 0, 0.0f, 4, ctx->d_csr_sim, ctx->d_csr_simw))) return r;
+    ctx->cmap_from_scatter = true;                          // (the cell scatter's combine wrote every voxel, 0 outside the mask: the update may skip the rest)
+  }
+  if (!ctx->sr_no_wait) HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->csr_stage = 3;
+  return SVR_OK;
+}
+
+int svr_channel_sr_update(svr_ctx *ctx, int adaptive, float alpha, float lo, float hi, float delta, float lambda) {
+  SVR_ENTER(ctx);
+  if (!ctx) return SVR_E_ARG;
+  if (ctx->csr_stage != 3) return channel_sr_refuse_order(ctx, "svr_channel_sr_update", "svr_channel_sr_backproject first");
+  if (!(std::isfinite(delta) && delta > 0.0f) || !(std::isfinite(lambda) && lambda > 0.0f))
+    return fail(ctx, SVR_E_ARG, "svr_channel_sr_update: delta and lambda must be finite and positive");
+  if (!std::isfinite(alpha)) return fail(ctx, SVR_E_ARG, "svr_channel_sr_update: alpha must be finite");
+  if (!(lo <= hi)) return fail(ctx, SVR_E_ARG, "svr_channel_sr_update: the clamp needs lo <= hi");
+  if (ctx->reg_mode != 1) return fail(ctx, SVR_E_STATE, "svr_channel_sr_update: needs the fused volume update (reg_mode 1)");
+  if (alpha * lambda / (delta * delta) > 0.068)
+    fprintf(stderr, "Warning: regularization might not have smoothing effect! Ensure that alpha*lambda/delta^2 is below 0.068.");
+  RegulArgs ra;
+  ra.thr_lo = ra.val_lo = lo;                               // r < lo -> lo, r > hi -> hi: the channel's own range, not 0.9 min / 1.1 max
+  ra.thr_hi = ra.val_hi = hi;
+  const int r = regul_fused_launch(ctx, ra, ctx->d_csr_vol[ctx->csr_cur], ctx->d_csr_vol[ctx->csr_cur ^ 1], adaptive, alpha, delta, lambda, 0, (int)ctx->vz);
+  if (r) return r;
+  ctx->csr_cur ^= 1;                                        // the update wrote the other buffer
+  if (!ctx->sr_no_wait) HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->csr_stage = 2;
+  return SVR_OK;
+}
+
+int svr_channel_sr_end(svr_ctx *ctx, float *out_or_null) {
+  SVR_ENTER(ctx);
+  if (!ctx) return SVR_E_ARG;
+  if (!ctx->csr_stage) return channel_sr_refuse_order(ctx, "svr_channel_sr_end", "svr_channel_sr_begin first");
+  int r = SVR_OK;
+  hipError_t e = hipSuccess;
+  if (out_or_null && ctx->csr_stage < 2) r = fail(ctx, SVR_E_ARG, "svr_channel_sr_end: no volume to hand over (svr_channel_sr_seed first); the call is over");
+  if (ctx->csr_stage >= 2 && out_or_null) {
+    float *vol = ctx->d_csr_vol[ctx->csr_cur];
+    hipLaunchKernelGGL(k_channel_uncover, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, vol, ctx->d_csr_cover, ctx->nv);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out_or_null, vol, ctx->nv * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) r = fail(ctx, (int)e, std::string("svr_channel_sr_end: ") + hipGetErrorString(e));
+  // addon | cmap hold the last iteration's scatter, with Prep's changes neither applied nor owed
+  ctx->prep_pending = false;
+  invalidate(ctx, CH_SCATTER_TARGETS);
+  channel_sr_drop(ctx);                                     // the call is over, whether the download worked or not
   return r;
 }
 

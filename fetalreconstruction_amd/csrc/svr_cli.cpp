@@ -88,6 +88,9 @@ struct Options {
   std::vector<std::string> channel_names, label_names;                   // --channelStacks, --labelStacks (not reference options): a file or `none` per -i stack
   std::string channel_out, label_out, label_conf, manual_name, channels_dump;   // --channelOutput, --labelOutput, --labelConfidence, --manualMask, --dumpChannels
   bool have_channel_opt = false, have_label_opt = false;
+  int channel_iterations = 0;                                             // --channelIterations (not a reference option): SR iterations on the --channelStacks set
+  double channel_delta = 0, channel_lambda = 0;                           // --channelDelta, --channelLambda; 0 = not given (from --delta and the ranges / --lastIterLambda)
+  bool have_channel_sr_opt = false;                                       // one of the three was named
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
   size_t tmpl = 0;                                                        // the first stack whose -t is id (main.cc:452-457)
 };
@@ -139,7 +142,8 @@ void usage() {
          "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
          "       [--useLNCC] [--lnccRadius 3]\n"
          "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix] [--referenceVolume file]\n"
-         "       [--channelStacks f_1 .. f_N --channelOutput file] [--labelStacks f_1 .. f_N --labelOutput file [--labelConfidence file]]\n"
+         "       [--channelStacks f_1 .. f_N --channelOutput file [--channelIterations 0] [--channelDelta d] [--channelLambda l]]\n"
+         "       [--labelStacks f_1 .. f_N --labelOutput file [--labelConfidence file]]\n"
          "       [--manualMask file]\n"
          "       [--structural [--structuralRadius 3] [--structuralK 3] [--structuralMinDrop 0.1] [--structuralMinPixels 25]]\n"
          "  --structural            deviation from the reference, which leaves a slice out by its intensity residuals (or --force_exclude)\n"
@@ -158,8 +162,21 @@ void usage() {
          "                          is written the files, cropped and cut into slices with their stacks, are scattered into the volume with\n"
          "                          the final slice transformations and the robust weights of the run and divided by the scattered weights:\n"
          "                          the robust PSF-weighted average of the channel, in its own units (no intensity matching, no bias field,\n"
-         "                          no super-resolution iterations), 0 where no slice with a channel reaches.  Its own value never excludes\n"
-         "                          a pixel: zero and negative values count.  The -o volume is the same with and without it.\n"
+         "                          no super-resolution iterations unless --channelIterations asks for them), 0 where no slice with a channel\n"
+         "                          reaches.  Its own value never excludes a pixel: zero and negative values count.  The -o volume is the same\n"
+         "                          with and without it.\n"
+         "  --channelIterations n   deviation from the reference: refine that average by n super-resolution iterations [0] with the run's final\n"
+         "                          slice transformations and robust weights held fixed, so that the channel gets the through-plane resolution\n"
+         "                          of the -o volume instead of the slice profile's blur.  Every iteration projects the channel volume into the\n"
+         "                          slices, scatters the weighted residuals against the channel's pixels and runs the edge-preserving volume\n"
+         "                          update; nothing is estimated, no intensity scale or bias field is applied, values are clamped to the\n"
+         "                          channel's range widened by a tenth on either side.  A constant channel is returned as the average.  Voxels of\n"
+         "                          the mask that no slice with a channel reaches (stacks given as `none`) hold 0 and count as 0 for their\n"
+         "                          neighbours.  Needs --channelStacks; --labelStacks and --manualMask keep their vote / average.  Not with\n"
+         "                          --sfolder.  With 0 or without the option nothing changes.  One stderr line reports the parameters.\n"
+         "  --channelDelta d        deviation from the reference: the edge scale of that update in the channel's units [--delta times the\n"
+         "                          channel's range over the primary's intensity range].\n"
+         "  --channelLambda l       deviation from the reference: its smoothing weight [--lastIterLambda]; the step is min(1, 0.05 / l).\n"
          "  --labelStacks f_1 .. f_N --labelOutput <file> [--labelConfidence <file>]\n"
          "                          deviation from the reference: a label map per -i stack (integers in 0..65535, at most 64 different\n"
          "                          ones; 0 competes like any other label; `none` = the stack has none).  Each label's indicator image is\n"
@@ -326,7 +343,7 @@ void dump_channels(const std::string &name, const Problem &P) {
 // The second images into the reconstructed space (not in the reference's main() but for --manualMask, reconstruction.cc:1240-1250).  The
 // volume is on disk: nothing from here on can reach it.  Every rank scatters its own slices with the weights the last SR iteration
 // would scatter with, the ranks' sums are brought together (svrh_channel_reconstruct), and rank 0 divides or votes.
-void reconstruct_extras(const Problem &P, const Ranks &R, const std::vector<svrh_recon *> &hosts, bool timing) {
+void reconstruct_extras(const Options &opt, const Problem &P, const Ranks &R, const std::vector<svrh_recon *> &hosts, bool timing) {
   const size_t nvv = (size_t)P.tattr.nx * P.tattr.ny * P.tattr.nz, slice = (size_t)P.mx * P.my;
   svr_ctx *ctx = R.ctxs[0];
   char err[256] = {0};
@@ -360,7 +377,35 @@ void reconstruct_extras(const Problem &P, const Ranks &R, const std::vector<svrh
   };
   for (auto &e : P.extras) {
     std::vector<float> out(nvv), cover(nvv);
-    if (!e.labels) {
+    if (!e.labels && opt.channel_iterations > 0 && e.what == "--channelStacks") {
+      // --channelIterations: the average refined by SR iterations with the run's final motion and weights (svrh_channel_superresolve).  The
+      // channel's range over the pixels that can count -- the primary pixel is not -1, the stack has a channel --, over every rank's slices
+      double c_min = INFINITY, c_max = -INFINITY;
+      for (int s = 0; s < P.ns; ++s) {
+        if (!e.unit_on[s]) continue;
+        for (size_t i = 0; i < slice; ++i) {
+          const size_t g = (size_t)s * slice + i;
+          if (P.grid[g] == -1.0f) continue;
+          c_min = std::min(c_min, (double)e.grid[g]); c_max = std::max(c_max, (double)e.grid[g]);
+        }
+      }
+      if (!(c_max >= c_min) || !std::isfinite(c_min) || !std::isfinite(c_max)) die(e.what + ": no finite channel value lies inside the mask");
+      const double R_c = c_max - c_min, R_s = P.vmax - P.vmin;
+      const double lambda_c = opt.channel_lambda > 0 ? opt.channel_lambda : opt.last_lambda;
+      const double delta_c = opt.channel_delta > 0 ? opt.channel_delta : (R_s > 0 ? opt.delta * R_c / R_s : 0.0);
+      // a constant channel has nothing to refine (and no scale for delta): the average is the answer
+      const int n_it = R_c > 0 && delta_c > 0 ? opt.channel_iterations : 0;
+      fprintf(stderr, "--channelIterations %d%s: delta %.9g lambda %.9g alpha %.9g, channel range [%.9g, %.9g], clamp [%.9g, %.9g]\n", opt.channel_iterations,
+              n_it ? "" : " (constant channel: none run)", delta_c, lambda_c, std::min(1.0, 0.05 / lambda_c), c_min, c_max, c_min - 0.1 * R_c, c_max + 0.1 * R_c);
+      R.par([&](int r) {
+        const size_t o = (size_t)R.rlo[r];
+        HOSTR(r, svrh_channel_superresolve(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, n_it ? delta_c : 1.0, lambda_c,
+                                           (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr));
+      });
+      if (svr_nifti_write(e.out.c_str(), &P.tattr, out.data(), err)) die(e.out + ": " + err);
+      for (size_t i = 0; i < nvv; ++i) cover[i] = out[i] != 0.0f ? 1.0f : 0.0f;                          // (0 where no slice with a channel reaches)
+      say(e.what + " (non-zero voxels)", e.out, out, cover);
+    } else if (!e.labels) {
       scatter(e, 0, 0.0f);
       ENGR(R, 0, svr_channel_finish(ctx, 0.0f, out.data()));
       ENGR(R, 0, svr_debug_get(ctx, SVR_BUF_CONFIDENCE_MAP, cover.data(), nvv * sizeof(float)));        // den: where it is positive a slice reached
@@ -380,7 +425,9 @@ void reconstruct_extras(const Problem &P, const Ranks &R, const std::vector<svrh
       }
     }
   }
-  if (timing)
+  if (timing && !n_scatter)                                               // (only a channel with --channelIterations: its own line gave the iterations' time)
+    fprintf(stderr, "[timing] one SR scatter of rank 0's slices %.3f ms (host clock)\n", 1e3 * t_sr);
+  else if (timing)
     fprintf(stderr, "[timing] %d channel / label scatters, %.3f ms each (upload, scatter%s; slowest rank, host clock); one SR scatter of rank 0's slices %.3f ms\n",
             n_scatter, 1e3 * t_scatter / std::max(1, n_scatter), R.nr > 1 ? ", all-reduce" : "", 1e3 * t_sr);
 }
@@ -440,6 +487,9 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
     else if (a.is("--referenceVolume")) p.reference_name = a.one();       // main.cc:207, 253-258: read there and (outside the T1 experiment) never used
     else if (a.is("--channelStacks")) { p.have_channel_opt = true; a.multi(p.channel_names); }   // not reference options: a second image per stack through the run's motion and weights
     else if (a.is("--channelOutput")) p.channel_out = a.one();
+    else if (a.is("--channelIterations")) { p.have_channel_sr_opt = true; p.channel_iterations = a.one_int(); }   // not reference options: SR iterations on the channel
+    else if (a.is("--channelDelta")) { p.have_channel_sr_opt = true; p.channel_delta = a.one_double(); if (!(p.channel_delta > 0) || !std::isfinite(p.channel_delta)) die("--channelDelta must be positive"); }
+    else if (a.is("--channelLambda")) { p.have_channel_sr_opt = true; p.channel_lambda = a.one_double(); if (!(p.channel_lambda > 0) || !std::isfinite(p.channel_lambda)) die("--channelLambda must be positive"); }
     else if (a.is("--labelStacks")) { p.have_label_opt = true; a.multi(p.label_names); }
     else if (a.is("--labelOutput")) p.label_out = a.one();
     else if (a.is("--labelConfidence")) p.label_conf = a.one();
@@ -456,6 +506,12 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
   if (!p.sim_prefix.empty() && !p.sfolder.empty())
     die("--simulatedStacks puts every simulated slice back into the stack it was cut from; with --sfolder the slices come from files of "
         "their own and belong to no stack: use --sliceReport, or drop --sfolder");
+  if (p.channel_iterations < 0) die("--channelIterations must not be negative (0 = the robust PSF-weighted average alone)");
+  if (p.have_channel_sr_opt && !p.have_channel_opt)
+    die("--channelIterations / --channelDelta / --channelLambda refine the channel of --channelStacks f_1 .. f_N --channelOutput <file>: give them");
+  if (p.have_channel_sr_opt && !p.sfolder.empty())
+    die("--channelIterations / --channelDelta / --channelLambda belong to --channelStacks, which cuts its files into slices with the stacks; with "
+        "--sfolder the slices come from files of their own and belong to no stack: drop one or the other");
   if (p.structural && !p.sfolder.empty())
     die("--structural compares every slice with the other slices of its stack; with --sfolder the slices come from files of their own and "
         "belong to no stack: drop one or the other");
@@ -1098,7 +1154,7 @@ int main(int argc, char **argv) {
     clk.mark("slice report, simulated stacks");
   }
   if (!P.extras.empty()) {
-    reconstruct_extras(P, R, hosts, clk.on);
+    reconstruct_extras(opt, P, R, hosts, clk.on);
     clk.mark("channels, labels");
   }
   if (opt.debug) save_debug_transformations(opt, P, R);

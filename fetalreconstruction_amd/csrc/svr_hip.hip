@@ -156,7 +156,7 @@ struct PsfArgs {
   // coefficient table (COEFF instantiations): the evaluated taps of every live unit of every PSF pixel, kept in HBM
   const float4 *coeff;        // [pixel id][16 units][4 tap quads][16 rows] float4
   const uint32_t *coeff_id;   // slice-grid index -> pixel id
-  // channel scatter (k_cell_factors mode 3, svr_channel.inc): a float per slice pixel that is not the primary image
+  // channel scatter (k_cell_factors modes 3 and 4, svr_channel.inc): a float per slice pixel that is not the primary image
   const float *channel;
   const unsigned char *unit_on;   // [slice] 0 = the slice has no such channel; NULL = every slice has
   int ch_flags;                   // SVR_CHANNEL_INDICATOR: the scattered value is (channel == ch_match) ? 1 : 0
@@ -1252,6 +1252,13 @@ struct svr_ctx {
   DevBuf<unsigned> d_nmi_merge;          // merge slots of split evaluations + their counters, all zero between calls
   size_t nmi_slots = 0;
   DevBuf<float> d_vote_best, d_vote_label;                    // svr_channel_vote: the running maximum and its label, [nv] each, from the first vote to svr_channel_vote_fetch
+  // svr_channel_sr_begin .. _end (svr_channel.inc): the channel and its switches, the two channel volumes of the regulariser's flip, the channel's own
+  // forward projection {simulated, sim-weight, inside flags} and the cover mask.  All of it belongs to the call: channel_sr_drop frees it
+  DevBuf<float> d_csr_channel, d_csr_vol[2], d_csr_sim, d_csr_simw;
+  DevBuf<unsigned char> d_csr_unit_on, d_csr_cover, d_csr_inside, d_csr_slice_inside;
+  int csr_stage = 0;                     // 0 = no call in flight, 1 = begun (the seed scatter is in addon | cmap), 2 = a volume to project, 3 = back-projected
+  int csr_cur = 0;                       // which of d_csr_vol is the channel volume
+  bool csr_has_unit_on = false;
   bool have_em = false;                  // d_weights hold EM posteriors (svr_initialize_em_values or a later E-step; a test's svr_debug_set)
   int last_quality_chunks = -1;          // chunks per slice of the last svr_slice_quality (read-only option "quality_chunks"; -1 = not launched yet)
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
@@ -1328,7 +1335,8 @@ void cell_free(CellState *c);
 
 // The changes of a context's inputs: invalidate (after the cell and slab includes) is the one place that drops cached state.  A new writer
 // of an input raises the change it causes, a new cache adds its line there; whoever builds a cache marks it valid.  Buffers that
-// live for one call are locals of their entry point; the vote arrays of svr_channel_vote live from the first vote to the fetch and have a line.
+// live for one call are locals of their entry point; the vote arrays of svr_channel_vote live from the first vote to the fetch and have a line,
+// and so do the buffers of a channel's SR iterations (svr_channel_sr_begin .. _end): dropped with either grid, never reused.
 enum Change : unsigned {
   CH_SLICE_GEOMETRY = 1u << 0,    // slice dims / matrices: the slice constants, rebuilt by the next pass (prepare_slice_consts then raises CH_TAPS)
   CH_TAPS = 1u << 1,              // new slice constants, generatePSFVolume: the table and the cell lists
@@ -1860,8 +1868,16 @@ int launch_scatter(svr_ctx *ctx, int level, const PsfArgs &a_, const uint32_t *t
 
 // What each Change leaves stale.  A table written by a pass of the SR iterations holds that pass's PSF pixels only: every change that can
 // add one drops it.  Rebuilt cell lists reset their gather factors and table ids (cell_prepare_state): the lists take them along.
+// every buffer of a channel's SR iterations (svr_channel_sr_begin .. _end, svr_channel.inc): the call is over
+void channel_sr_drop(svr_ctx *ctx) {
+  ctx->d_csr_channel.reset(); ctx->d_csr_vol[0].reset(); ctx->d_csr_vol[1].reset(); ctx->d_csr_sim.reset(); ctx->d_csr_simw.reset();
+  ctx->d_csr_unit_on.reset(); ctx->d_csr_cover.reset(); ctx->d_csr_inside.reset(); ctx->d_csr_slice_inside.reset();
+  ctx->csr_stage = 0; ctx->csr_cur = 0; ctx->csr_has_unit_on = false;
+}
+
 void invalidate(svr_ctx *ctx, unsigned ch) {
   if (ch & CH_SLICE_GEOMETRY) ctx->sc_dirty = true;
+  if (ch & (CH_VOLUME_GRID | CH_SLICE_PIXELS)) channel_sr_drop(ctx);   // (a channel's SR iterations in flight were over the old grids: nothing of them is cached)
   if (ch & (CH_SLICE_PIXELS | CH_PSF_SUMS | CH_TILE_SHAPE)) ctx->psf_list_valid = false;
   if (ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_TABLE | CH_TABLE_OFF)) ctx->coeff_state = COEFF_NONE;
   if ((ch & CH_PSF_SUMS) && ctx->coeff_state == COEFF_PSF) ctx->coeff_state = COEFF_NONE;
@@ -2000,10 +2016,11 @@ int launch_pixels(svr_ctx *ctx, const PsfArgs &a, void (*kernel)(PsfArgs), const
   });
 }
 // {V m, m} per voxel for the gathers' boxes (patch-based: V through the 8-voxel average) -> a.volm
-int pack_volm(svr_ctx *ctx, PsfArgs &a) {
+// (vol: the volume the pass projects -- the reconstruction, or a channel volume of svr_channel.inc)
+int pack_volm(svr_ctx *ctx, PsfArgs &a, const float *vol) {
   HIPCHK(ctx->d_volm.reserve(ctx->nv));
-  if (ctx->pvr) hipLaunchKernelGGL(k_pack_volm_pvr, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, a.vg);
-  else hipLaunchKernelGGL(k_pack_volm, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->recon(), ctx->d_mask, ctx->d_volm, ctx->nv);
+  if (ctx->pvr) hipLaunchKernelGGL(k_pack_volm_pvr, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, vol, ctx->d_mask, ctx->d_volm, a.vg);
+  else hipLaunchKernelGGL(k_pack_volm, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, vol, ctx->d_mask, ctx->d_volm, ctx->nv);
   KCHK(ctx->pvr ? "k_pack_volm_pvr" : "k_pack_volm");
   a.volm = ctx->d_volm;
   return SVR_OK;
@@ -2748,7 +2765,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
   if (store || (p.may_stream_table && table_holds(ctx, COEFF_PSF))) give_coeff(ctx, a);
-  if (a.n && p.family != FAM_PIXELS && (r = pack_volm(ctx, a))) return r;
+  if (a.n && p.family != FAM_PIXELS && (r = pack_volm(ctx, a, ctx->recon()))) return r;
   gcs = nullptr;
   if (a.n && p.family == FAM_CELLS && (!a.coeff || store || p.table_on_cells) &&
       (r = cells_or_fallback(ctx, true, 1, "the gather left the cell path (the cell lists cannot hold this geometry): tile kernel, same bits", gcs))) return r;
@@ -3125,6 +3142,8 @@ static int regul_settle(svr_ctx *ctx) {
   return SVR_OK;
 }
 
+static int regul_fused_launch(svr_ctx *ctx, RegulArgs &ra, const float *recon, float *out, int adaptive, float alpha, float delta, float lambda, int z_lo,
+                              int z_hi);
 static int superresolution_update_planes(svr_ctx *ctx, int adaptive, float alpha, float min_intensity, float max_intensity, float delta,
                                          float lambda, int z_lo, int z_hi) {
   if (ctx->reg_mode == 0) {
@@ -3141,8 +3160,16 @@ static int superresolution_update_planes(svr_ctx *ctx, int adaptive, float alpha
     return SVR_OK;
   }
   RegulArgs ra;
-  ra.recon = ctx->recon(); ra.addon = ctx->addon(); ra.cmap = ctx->cmap();
-  ra.out = ctx->recon_cur == ctx->d_recon_volw ? ctx->d_recon_new : ctx->d_recon_volw;
+  regul_thresholds(min_intensity, max_intensity, ra);
+  return regul_fused_launch(ctx, ra, ctx->recon(), ctx->recon_cur == ctx->d_recon_volw ? ctx->d_recon_new : ctx->d_recon_volw, adaptive, alpha, delta, lambda,
+                            z_lo, z_hi);
+}
+
+// k_regul_fused on planes [z_lo, z_hi) of `recon` with the context's addon | cmap -> out; ra brings the clamp (thr / val), everything else is set here
+static int regul_fused_launch(svr_ctx *ctx, RegulArgs &ra, const float *recon, float *out, int adaptive, float alpha, float delta, float lambda, int z_lo,
+                              int z_hi) {
+  ra.recon = recon; ra.addon = ctx->addon(); ra.cmap = ctx->cmap();
+  ra.out = out;
   ra.vx = (int)ctx->vx; ra.vy = (int)ctx->vy; ra.vz = (int)ctx->vz;
   ra.z_lo = z_lo; ra.z_hi = z_hi;
   // tile of a workgroup (option reg_tile).  Measured on one MI355X (tools/exp_regul_tile.py; 64 x 8 / 32 x 16 / 32 x 8): P4 19.4 / 20.2 /
@@ -3163,7 +3190,6 @@ static int superresolution_update_planes(svr_ctx *ctx, int adaptive, float alpha
     for (int k = 0; k < 3; ++k) { ra.blo[k] = std::max(0, ctx->mbox_lo[k] - 1); ra.bhi[k] = std::min(dims[k] - 1, ctx->mbox_hi[k] + 1); }
   }
   ra.alpha = alpha;
-  regul_thresholds(min_intensity, max_intensity, ra);
   ra.k = alpha * lambda / (delta * delta);                                // RC.cu:2107 (float)
   const double d2 = (double)delta * (double)delta;
   ra.kap1 = (float)(1.0 / d2); ra.kap2 = (float)(0.5 / d2); ra.kap3 = (float)((double)(1.0f / 3.0f) / d2);

@@ -214,6 +214,42 @@ class irtkReconstruction {
     return 0;
   }
 
+  // n SR iterations on a channel (svr_channel_sr_*, include/svr_hip.h) with the weights ChannelReconstruct scatters with: the seed scatter and
+  // every iteration's addon | cmap are summed over the ranks like ChannelReconstruct's pair, the volume update runs replicated on every rank.
+  // delta_c / lambda_c become the engine's parameters the way SetSmoothingParameters makes the primary's
+  int ChannelSuperresolve(const float *channel_local, const unsigned char *unit_on_local, int n, double delta_c, double lambda_c, float clamp_lo, float clamp_hi,
+                          float *out_or_null) {
+    if (n < 0 || !std::isfinite(delta_c) || !(delta_c > 0) || !std::isfinite(lambda_c) || !(lambda_c > 0) || !(clamp_lo <= clamp_hi)) {
+      err = "svrh_channel_superresolve: n >= 0, delta and lambda finite and positive, lo <= hi";
+      return SVR_E_ARG;
+    }
+    const float *sw;
+    if (int rc = em.scatter_weights(&sw)) return rc;
+    const size_t pair = 2 * svr_volume_voxels(reconstructionGPU);
+    const float alpha = (float)std::min(1.0, 0.05 / lambda_c), lambda_eng = (float)(lambda_c * delta_c * delta_c);
+    double ms = 0;
+    auto run = [&]() -> int {
+      ENG(svr_channel_sr_begin(reconstructionGPU, channel_local, unit_on_local, sw, 0));
+      if (sh.on) ENG(sh.allreduce_pair(SVR_BUF_ADDON, pair));
+      ENG(svr_channel_sr_seed(reconstructionGPU, nullptr));
+      const auto t0 = std::chrono::steady_clock::now();
+      for (int k = 0; k < n; ++k) {
+        ENG(svr_channel_sr_backproject(reconstructionGPU));
+        if (sh.on) ENG(sh.allreduce_pair(SVR_BUF_ADDON, pair));
+        ENG(svr_channel_sr_update(reconstructionGPU, _adaptive, alpha, clamp_lo, clamp_hi, (float)delta_c, lambda_eng));
+      }
+      ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      ENG(svr_channel_sr_end(reconstructionGPU, out_or_null));
+      return 0;
+    };
+    const int rc = run();
+    if (rc) (void)svr_channel_sr_end(reconstructionGPU, nullptr);       // (the call is over either way: its buffers go, the message stays)
+    else if (n > 0 && getenv("SVR_CLI_TIMING"))                           // (every engine call blocks: the host clock around them is their cost)
+      fprintf(stderr, "[timing] channel SR iteration (gather, scatter%s, update), %d slices: %.3f ms each over %d (host clock)\n",
+              sh.on ? ", all-reduce" : "", hi - lo, ms / n, n);
+    return rc;
+  }
+
   int MaskVolumeGPU() { ENG(svr_mask_volume(reconstructionGPU)); return 0; }   // RG.cc:5319-5323
 
   int ScaleVolumeGPU() {
@@ -427,6 +463,11 @@ int svrh_normalise_bias_gpu(svrh_recon *r, int iter) { return r->impl.NormaliseB
 int svrh_channel_reconstruct(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int flags, float match) {
   if (!r) return SVR_E_ARG;
   return r->impl.ChannelReconstruct(channel_local, unit_on_local, flags, match);
+}
+int svrh_channel_superresolve(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int n, double delta_c, double lambda_c,
+                              float lo, float hi, float *out_or_null) {
+  if (!r) return SVR_E_ARG;
+  return r->impl.ChannelSuperresolve(channel_local, unit_on_local, n, delta_c, lambda_c, lo, hi, out_or_null);
 }
 int svrh_initialize_em_values_gpu(svrh_recon *r) { return r->impl.InitializeEMValuesGPU(); }
 int svrh_gaussian_reconstruction_gpu(svrh_recon *r) { return r->impl.GaussianReconstructionGPU(); }

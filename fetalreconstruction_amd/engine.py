@@ -50,6 +50,7 @@ EXPORTS = [
     "svr_slab_plan", "svr_slab_rs_pack", "svr_slab_update", "svr_slab_finish", "svr_stream_sync",
     "svr_get_scale_vector", "svr_adopt_scale_vector", "svr_get_slice_inside", "svr_mstep_estep", "svr_mstep_sums_fetch", "svr_mstep_partial", "svr_mstep_estep_ranks",
     "svr_channel_scatter", "svr_channel_finish", "svr_channel_vote", "svr_channel_vote_fetch",
+    "svr_channel_sr_begin", "svr_channel_sr_seed", "svr_channel_sr_backproject", "svr_channel_sr_update", "svr_channel_sr_end",
 ]
 
 
@@ -555,6 +556,44 @@ class Reconstruction:
         lab, conf = np.empty(n, np.float32), np.empty(n, np.float32)
         self._ck(self._lib.svr_channel_vote_fetch(self._h, C.c_float(background_label), _p(lab), _p(conf)))
         return lab, conf
+
+    # SR iterations on a channel with the run's motion and weights held fixed (svr_channel_sr_*): begin, [all-reduce], seed, then per iteration
+    # backproject, [all-reduce], update; end hands the volume over and frees the call's buffers
+    def channel_sr_begin(self, channel, unit_on=None, slice_weights=None, flags=0):
+        """svr_channel_sr_begin: uploads and keeps the channel, svr_channel_scatter's scatter -> BUF_ADDON | BUF_CONFIDENCE_MAP"""
+        if not self.sgrid:
+            raise SvrError("channel_sr_begin: initStorageVolumes first")
+        c = None if channel is None else _f32(channel)
+        if c is not None and c.size != int(np.prod(self.sgrid)):
+            raise SvrError(f"channel_sr_begin: expected {self.sgrid}, got {c.shape}")
+        u = None if unit_on is None else np.ascontiguousarray(unit_on, np.uint8)
+        if u is not None and u.size != self.sgrid[0]:
+            raise SvrError("channel_sr_begin: one unit_on byte per slice expected")
+        w = None if slice_weights is None else _f32(slice_weights)
+        self._ck(self._lib.svr_channel_sr_begin(self._h, None if c is None else _p(c), None if u is None else _p(u), None if w is None else _p(w),
+                                                int(flags)))
+
+    def channel_sr_seed(self, seed=None):
+        """svr_channel_sr_seed: C0 = num / den where den > 0, else 0; cover = den > 0.  seed: a volume that replaces C0's values"""
+        s = None if seed is None else _f32(seed)
+        if s is not None and s.size != int(np.prod(self.vsize)):
+            raise SvrError("channel_sr_seed: a value per voxel expected")
+        self._ck(self._lib.svr_channel_sr_seed(self._h, None if s is None else _p(s)))
+
+    def channel_sr_backproject(self):
+        """svr_channel_sr_backproject: forward projection of the channel volume, residuals, scatter -> BUF_ADDON | BUF_CONFIDENCE_MAP"""
+        self._ck(self._lib.svr_channel_sr_backproject(self._h))
+
+    def channel_sr_update(self, adaptive, alpha, lo, hi, delta, lam):
+        """svr_channel_sr_update: the SR volume update on the channel volume, clamped to [lo, hi]"""
+        self._ck(self._lib.svr_channel_sr_update(self._h, int(bool(adaptive)), C.c_float(alpha), C.c_float(lo), C.c_float(hi), C.c_float(delta),
+                                                 C.c_float(lam)))
+
+    def channel_sr_end(self, want_volume=True):
+        """svr_channel_sr_end -> the channel volume (flat, 0 outside cover) or None; frees the call's buffers"""
+        out = np.empty(int(np.prod(self.vsize)), np.float32) if want_volume else None
+        self._ck(self._lib.svr_channel_sr_end(self._h, None if out is None else _p(out)))
+        return out
 
     # ---- GPU slice-to-volume registration (RC.cuh:326-338) ------------------------------------
     def initRegStorageVolumes(self, W, H, ns, dim=(1.0, 1.0, 1.0)):

@@ -24,6 +24,7 @@ HOST_EXPORTS = [
     "svrh_sr_iteration", "svrh_reconstruct_iteration", "svrh_get_state", "svrh_set_bias_correction", "svrh_set_bias_options", "svrh_bias_gpu",
     "svrh_normalise_bias_gpu", "svrh_prepare_registration_slices", "svrh_slice_to_volume_registration_gpu",
     "svrh_get_registration_slices", "svrh_force_collectives", "svrh_set_slab_update", "svrh_set_unit_order", "svrh_channel_reconstruct",
+    "svrh_channel_superresolve",
     "svrh_set_structural", "svrh_structural_evaluate", "svrh_get_structural",
 ]
 PVR_HOST_EXPORTS = ["pvrh_create", "pvrh_destroy", "pvrh_last_error", "pvrh_initialize_em_values", "pvrh_initialize_robust_statistics",
@@ -292,6 +293,16 @@ class irtkReconstruction:
         u = None if unit_on_local is None else np.ascontiguousarray(unit_on_local, np.uint8)
         self._ck(self._lib.svrh_channel_reconstruct(self._h, c.ctypes.data_as(C.c_void_p), None if u is None else u.ctypes.data_as(C.c_void_p),
                                                     1 if indicator else 0, C.c_float(match)))
+
+    def ChannelSuperresolve(self, channel_local, unit_on_local, n, delta_c, lambda_c, lo, hi, nvox):
+        """svrh_channel_superresolve: the channel's average refined by n SR iterations with the run's weights -> the volume (flat, nvox floats)"""
+        c = np.ascontiguousarray(channel_local, np.float32)
+        u = None if unit_on_local is None else np.ascontiguousarray(unit_on_local, np.uint8)
+        out = np.empty(int(nvox), np.float32)
+        self._ck(self._lib.svrh_channel_superresolve(self._h, c.ctypes.data_as(C.c_void_p), None if u is None else u.ctypes.data_as(C.c_void_p),
+                                                     int(n), C.c_double(delta_c), C.c_double(lambda_c), C.c_float(lo), C.c_float(hi),
+                                                     out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def InitializeEMValuesGPU(self):
         self._ck(self._lib.svrh_initialize_em_values_gpu(self._h))

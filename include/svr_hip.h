@@ -402,6 +402,31 @@ int svr_channel_scatter(svr_ctx *ctx, const float *channel, const unsigned char 
 int svr_channel_finish(svr_ctx *ctx, float background, float *out_or_null);
 int svr_channel_vote(svr_ctx *ctx, float label, int first);
 int svr_channel_vote_fetch(svr_ctx *ctx, float background_label, float *labels_or_null, float *confidence_or_null);
+/* Super-resolution iterations on such a channel, with the run's final motion and weights held fixed (the command line's --channelIterations; no
+ * reference equivalent).  P, f1_p and unit_on as svr_channel_scatter defines them; nothing is estimated.
+ *   begin        uploads the channel and the switches, keeps them, and runs svr_channel_scatter's scatter (the same bits) into addon | cmap; a
+ *                sharded run all-reduces the pair here.
+ *   seed         C = den > 0 ? num / den : 0 (svr_channel_finish with background 0) and cover = {den > 0}, fixed for the call.  A non-NULL host
+ *                volume [nv] replaces the values of C; cover still comes from den.
+ *   backproject  sim_p = the forward projection of C (svr_simulate_slices's gather over the (cell, plane) items: the same epsilon-skip, the
+ *                coefficient table when it is valid) into buffers of the call's own -- SVR_BUF_SIMSLICES, SVR_BUF_SIMWEIGHTS and slice_inside are
+ *                not written; then, for p in P whose sim-weight of that pass is > 0 (the sign of sim_p never decides: a channel may be zero or
+ *                negative), e_p = c_p - sim_p, f0_p = f1_p e_p, else both 0 (no scale vector, bias field or stack factor), through the SR
+ *                iteration's scatter without atomics into addon | cmap; a sharded run all-reduces the pair here.
+ *   update       C <- svr_superresolution_update's arithmetic on (C, addon, cmap) with alpha, delta, lambda (the caller's lambda delta^2, as for
+ *                svr_superresolution) and the clamp [lo, hi] in place of 0.9 min / 1.1 max, which presumes positive intensities.
+ *   end          C = 0 outside cover, downloaded into out_or_null [nv]; every buffer of the call is freed, also by a new slice or volume grid.
+ * Voxels of the mask that no slice with a channel reaches hold 0 and enter the forward projection of neighbouring pixels as 0, as uncovered
+ * voxels do for the primary.  Refused with a message and a status, never a fault, and the context stays usable: a patch-based (pvr) context, a
+ * NULL channel, a call out of order (begin twice, seed / backproject / update before their predecessor, end without begin), delta or lambda
+ * that is not finite and positive, lo > hi, missing state (what svr_channel_scatter needs; back_mode 5, fwd_mode 2, reg_mode 1), a geometry the
+ * cell lists cannot hold, and SVR_CHANNEL_INDICATOR or an unknown bit in flags (label indicators keep their vote: flags must be 0).  The same bits on
+ * every call. */
+int svr_channel_sr_begin(svr_ctx *ctx, const float *channel, const unsigned char *unit_on, const float *slice_weights, int flags);
+int svr_channel_sr_seed(svr_ctx *ctx, const float *seed_or_null);
+int svr_channel_sr_backproject(svr_ctx *ctx);
+int svr_channel_sr_update(svr_ctx *ctx, int adaptive, float alpha, float lo, float hi, float delta, float lambda);
+int svr_channel_sr_end(svr_ctx *ctx, float *out_or_null);
 
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::

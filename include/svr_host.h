@@ -112,6 +112,14 @@ int svrh_normalise_bias_gpu(svrh_recon *r, int iter);
  * SVR_BUF_CONFIDENCE_MAP) are then all-reduced like the pair of the non-slab SR update, so every rank holds the same sums.  Collective.
  * The caller finishes (svr_channel_finish) or votes (svr_channel_vote) on the engine. */
 int svrh_channel_reconstruct(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int flags, float match);
+/* That average refined by n super-resolution iterations with the run's motion and weights held fixed (svr_channel_sr_*, include/svr_hip.h;
+ * the command line's --channelIterations).  Collective: begin, all-reduce of addon | cmap as above, seed; then n times backproject, the same
+ * all-reduce, and the volume update replicated on every rank (no slab update).  delta_c and lambda_c are the user's values, made into the
+ * engine's the way svrh_set_smoothing_parameters makes the primary's (lambda_c delta_c^2, alpha = min(1, 0.05 / lambda_c), the object's
+ * adaptive flag); [lo, hi] clamps the channel.  n = 0 returns the average.  out_or_null: the channel volume, 0 where no slice with a channel
+ * reaches.  Whatever fails, the engine's call is ended and its buffers are freed. */
+int svrh_channel_superresolve(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int n, double delta_c, double lambda_c,
+                              float lo, float hi, float *out_or_null);
 
 int svrh_initialize_em_values_gpu(svrh_recon *r);
 int svrh_gaussian_reconstruction_gpu(svrh_recon *r);
