@@ -30,7 +30,8 @@
 // the invalidation map drops them with the volume grid (CH_VOLUME_GRID).
 //
 // svr_channel_sr_begin .. _end (further down) refine that average by SR iterations with the weights held fixed: the run's gather, factor
-// mode 4 of k_cell_factors, the run's scatter and the run's volume update on buffers that live from begin to end.
+// mode 4 of k_cell_factors, the run's scatter and the run's volume update on buffers that live from begin to end.  svr_channel_sr_guide adds a
+// guide volume to them: the updates of that call then weigh a neighbour pair by the guide's differences too (the GUIDED kernels of svr_regul.inc).
 
 namespace {
 
@@ -344,6 +345,34 @@ int svr_channel_sr_seed(svr_ctx *ctx, const float *seed_or_null) {
   return SVR_OK;
 }
 
+int svr_channel_sr_guide(svr_ctx *ctx, const float *guide_or_null, float delta_g, int flags) {
+  SVR_ENTER(ctx);
+  if (!ctx) return SVR_E_ARG;
+  if (ctx->csr_stage != 1 && ctx->csr_stage != 2)
+    return channel_sr_refuse_order(ctx, "svr_channel_sr_guide", ctx->csr_stage ? "not between a back-projection and its update (svr_channel_sr_update first)"
+                                                                               : "svr_channel_sr_begin first");
+  if (!(std::isfinite(delta_g) && delta_g > 0.0f)) return fail(ctx, SVR_E_ARG, "svr_channel_sr_guide: delta_g must be finite and positive");
+  if (flags & ~SVR_CHANNEL_GUIDE_ONLY) return fail(ctx, SVR_E_ARG, "svr_channel_sr_guide: unknown flag");
+  if (ctx->reg_mode != 1) return fail(ctx, SVR_E_STATE, "svr_channel_sr_guide: needs the fused volume update (reg_mode 1)");
+  if (guide_or_null)
+    for (size_t i = 0; i < ctx->nv; ++i)
+      if (!std::isfinite(guide_or_null[i])) return fail(ctx, SVR_E_ARG, "svr_channel_sr_guide: the guide holds a value that is not finite");
+  // a buffer of the call's own: nothing the run does later changes the guide, and the reconstruction is only read
+  hipError_t e = ctx->d_csr_guide.reserve(ctx->nv);
+  if (e == hipSuccess)
+    e = guide_or_null ? hipMemcpyAsync(ctx->d_csr_guide, guide_or_null, ctx->nv * sizeof(float), hipMemcpyHostToDevice, ctx->stream)
+                      : hipMemcpyAsync(ctx->d_csr_guide, ctx->recon(), ctx->nv * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {                                    // no guide rather than half of one; the call in flight goes on unguided
+    (void)hipGetLastError();
+    ctx->d_csr_guide.reset();
+    return fail(ctx, (int)e, std::string("svr_channel_sr_guide: ") + hipGetErrorString(e));
+  }
+  ctx->csr_delta_g = delta_g;
+  ctx->csr_guide_only = (flags & SVR_CHANNEL_GUIDE_ONLY) != 0;
+  return SVR_OK;
+}
+
 int svr_channel_sr_backproject(svr_ctx *ctx) {
   SVR_ENTER(ctx);
   if (!ctx) return SVR_E_ARG;
@@ -375,6 +404,12 @@ int svr_channel_sr_update(svr_ctx *ctx, int adaptive, float alpha, float lo, flo
   RegulArgs ra;
   ra.thr_lo = ra.val_lo = lo;                               // r < lo -> lo, r > hi -> hi: the channel's own range, not 0.9 min / 1.1 max
   ra.thr_hi = ra.val_hi = hi;
+  ra.guide = ctx->d_csr_guide ? ctx->d_csr_guide.get() : nullptr;
+  if (ra.guide) {                                           // svr_channel_sr_guide: the GUIDED kernels; delta still defines k = alpha lambda / delta^2
+    const double g2 = (double)ctx->csr_delta_g * (double)ctx->csr_delta_g;
+    ra.gkap1 = (float)(1.0 / g2); ra.gkap2 = (float)(0.5 / g2); ra.gkap3 = (float)((double)(1.0f / 3.0f) / g2);
+    ra.omega = ctx->csr_guide_only ? 0.0f : 1.0f;
+  }
   const int r = regul_fused_launch(ctx, ra, ctx->d_csr_vol[ctx->csr_cur], ctx->d_csr_vol[ctx->csr_cur ^ 1], adaptive, alpha, delta, lambda, 0, (int)ctx->vz);
   if (r) return r;
   ctx->csr_cur ^= 1;                                        // the update wrote the other buffer

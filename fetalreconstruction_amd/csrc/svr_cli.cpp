@@ -91,6 +91,9 @@ struct Options {
   int channel_iterations = 0;                                             // --channelIterations (not a reference option): SR iterations on the --channelStacks set
   double channel_delta = 0, channel_lambda = 0;                           // --channelDelta, --channelLambda; 0 = not given (from --delta and the ranges / --lastIterLambda)
   bool have_channel_sr_opt = false;                                       // one of the three was named
+  bool channel_guide = false, channel_guide_only = false;                 // --channelGuide, --channelGuideOnly (not reference options): the -o volume's edges
+  double channel_guide_delta = 0;                                         // --channelGuideDelta; 0 = not given (from --delta and the ranges)
+  bool have_channel_guide_opt = false;                                    // --channelGuideDelta or --channelGuideOnly was named
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
   size_t tmpl = 0;                                                        // the first stack whose -t is id (main.cc:452-457)
 };
@@ -142,7 +145,8 @@ void usage() {
          "       [--enableBiasCorrection] [--sigma 12] [--global_bias_correction 0] [--low_intensity_cutoff 0.01] [--disableBiasCorrection] [--useNMI]\n"
          "       [--useLNCC] [--lnccRadius 3]\n"
          "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix] [--referenceVolume file]\n"
-         "       [--channelStacks f_1 .. f_N --channelOutput file [--channelIterations 0] [--channelDelta d] [--channelLambda l]]\n"
+         "       [--channelStacks f_1 .. f_N --channelOutput file [--channelIterations 0] [--channelDelta d] [--channelLambda l]\n"
+         "        [--channelGuide [--channelGuideDelta d] [--channelGuideOnly]]]\n"
          "       [--labelStacks f_1 .. f_N --labelOutput file [--labelConfidence file]]\n"
          "       [--manualMask file]\n"
          "       [--structural [--structuralRadius 3] [--structuralK 3] [--structuralMinDrop 0.1] [--structuralMinPixels 25]]\n"
@@ -177,6 +181,17 @@ void usage() {
          "  --channelDelta d        deviation from the reference: the edge scale of that update in the channel's units [--delta times the\n"
          "                          channel's range over the primary's intensity range].\n"
          "  --channelLambda l       deviation from the reference: its smoothing weight [--lastIterLambda]; the step is min(1, 0.05 / l).\n"
+         "  --channelGuide          deviation from the reference: the volume update of --channelIterations also weighs every pair of neighbours\n"
+         "                          by the difference of the -o volume between them (the reconstruction as the device holds it when the channel\n"
+         "                          stage starts): b = f / sqrt(1 + f (dC / delta)^2 + f (dG / delta_g)^2).  A noisy map is smoothed inside\n"
+         "                          the tissues the anatomy shows and not across their boundaries, and --channelDelta can be large.  Needs\n"
+         "                          --channelStacks and --channelIterations > 0.  The -o volume is the same with and without it; --labelStacks\n"
+         "                          and --manualMask are untouched.  A constant -o volume guides nothing: the option is dropped with a message.\n"
+         "                          One stderr line reports delta_g, the guide's range and the mode.\n"
+         "  --channelGuideDelta d   deviation from the reference: the guide's edge scale delta_g in the -o volume's units [--delta times the\n"
+         "                          written volume's range inside the mask over the run's intensity range].  Needs --channelGuide.\n"
+         "  --channelGuideOnly      deviation from the reference: the channel's own differences leave the weight (--channelDelta still scales\n"
+         "                          --channelLambda).  Needs --channelGuide.\n"
          "  --labelStacks f_1 .. f_N --labelOutput <file> [--labelConfidence <file>]\n"
          "                          deviation from the reference: a label map per -i stack (integers in 0..65535, at most 64 different\n"
          "                          ones; 0 competes like any other label; `none` = the stack has none).  Each label's indicator image is\n"
@@ -397,10 +412,35 @@ void reconstruct_extras(const Options &opt, const Problem &P, const Ranks &R, co
       const int n_it = R_c > 0 && delta_c > 0 ? opt.channel_iterations : 0;
       fprintf(stderr, "--channelIterations %d%s: delta %.9g lambda %.9g alpha %.9g, channel range [%.9g, %.9g], clamp [%.9g, %.9g]\n", opt.channel_iterations,
               n_it ? "" : " (constant channel: none run)", delta_c, lambda_c, std::min(1.0, 0.05 / lambda_c), c_min, c_max, c_min - 0.1 * R_c, c_max + 0.1 * R_c);
+      // --channelGuide: the written volume, which every rank's device still holds (NULL = a copy of it).  Its range over the mask's voxels gives
+      // delta_g the way the channel's range gives delta_c
+      bool guided = opt.channel_guide && n_it > 0;
+      double delta_g = 0.0;
+      if (guided) {
+        std::vector<float> vol(nvv);
+        ENGR(R, 0, svr_sync_cpu(ctx, vol.data()));
+        double g_min = INFINITY, g_max = -INFINITY;
+        for (size_t i = 0; i < nvv; ++i)
+          if (P.vol_mask.d[i] != 0) { g_min = std::min(g_min, (double)vol[i]); g_max = std::max(g_max, (double)vol[i]); }
+        const double R_g = g_max >= g_min && std::isfinite(g_min) && std::isfinite(g_max) ? g_max - g_min : 0.0;
+        delta_g = opt.channel_guide_delta > 0 ? opt.channel_guide_delta : (R_s > 0 ? opt.delta * R_g / R_s : 0.0);
+        if (!(R_g > 0) || !(delta_g > 0) || !std::isfinite(delta_g)) {
+          fprintf(stderr, "--channelGuide: the written volume is constant inside the mask (range %.9g) and guides nothing: dropped\n", R_g);
+          guided = false;
+        } else {
+          fprintf(stderr, "--channelGuide: delta_g %.9g, guide range %.9g [%.9g, %.9g], %s\n", delta_g, R_g, g_min, g_max,
+                  opt.channel_guide_only ? "guide only" : "joint with the channel's differences");
+        }
+      }
       R.par([&](int r) {
         const size_t o = (size_t)R.rlo[r];
-        HOSTR(r, svrh_channel_superresolve(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, n_it ? delta_c : 1.0, lambda_c,
-                                           (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr));
+        if (guided)
+          HOSTR(r, svrh_channel_superresolve_guided(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, delta_c, lambda_c,
+                                                    (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr, nullptr,
+                                                    delta_g, opt.channel_guide_only ? 1 : 0));
+        else
+          HOSTR(r, svrh_channel_superresolve(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, n_it ? delta_c : 1.0, lambda_c,
+                                             (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr));
       });
       if (svr_nifti_write(e.out.c_str(), &P.tattr, out.data(), err)) die(e.out + ": " + err);
       for (size_t i = 0; i < nvv; ++i) cover[i] = out[i] != 0.0f ? 1.0f : 0.0f;                          // (0 where no slice with a channel reaches)
@@ -490,6 +530,9 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
     else if (a.is("--channelIterations")) { p.have_channel_sr_opt = true; p.channel_iterations = a.one_int(); }   // not reference options: SR iterations on the channel
     else if (a.is("--channelDelta")) { p.have_channel_sr_opt = true; p.channel_delta = a.one_double(); if (!(p.channel_delta > 0) || !std::isfinite(p.channel_delta)) die("--channelDelta must be positive"); }
     else if (a.is("--channelLambda")) { p.have_channel_sr_opt = true; p.channel_lambda = a.one_double(); if (!(p.channel_lambda > 0) || !std::isfinite(p.channel_lambda)) die("--channelLambda must be positive"); }
+    else if (a.is("--channelGuide")) p.channel_guide = true;              // not reference options: the channel's update guided by the -o volume's edges
+    else if (a.is("--channelGuideDelta")) { p.have_channel_guide_opt = true; p.channel_guide_delta = a.one_double(); if (!(p.channel_guide_delta > 0) || !std::isfinite(p.channel_guide_delta)) die("--channelGuideDelta must be positive"); }
+    else if (a.is("--channelGuideOnly")) { p.have_channel_guide_opt = true; p.channel_guide_only = true; }
     else if (a.is("--labelStacks")) { p.have_label_opt = true; a.multi(p.label_names); }
     else if (a.is("--labelOutput")) p.label_out = a.one();
     else if (a.is("--labelConfidence")) p.label_conf = a.one();
@@ -512,6 +555,10 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
   if (p.have_channel_sr_opt && !p.sfolder.empty())
     die("--channelIterations / --channelDelta / --channelLambda belong to --channelStacks, which cuts its files into slices with the stacks; with "
         "--sfolder the slices come from files of their own and belong to no stack: drop one or the other");
+  if (p.have_channel_guide_opt && !p.channel_guide) die("--channelGuideDelta / --channelGuideOnly describe the guide of --channelGuide: give it");
+  if (p.channel_guide && (!p.have_channel_opt || p.channel_iterations <= 0))
+    die("--channelGuide guides the volume update of --channelIterations n (n > 0) on the channel of --channelStacks f_1 .. f_N --channelOutput <file>: "
+        "give them");
   if (p.structural && !p.sfolder.empty())
     die("--structural compares every slice with the other slices of its stack; with --sfolder the slices come from files of their own and "
         "belong to no stack: drop one or the other");

@@ -1259,6 +1259,9 @@ struct svr_ctx {
   int csr_stage = 0;                     // 0 = no call in flight, 1 = begun (the seed scatter is in addon | cmap), 2 = a volume to project, 3 = back-projected
   int csr_cur = 0;                       // which of d_csr_vol is the channel volume
   bool csr_has_unit_on = false;
+  DevBuf<float> d_csr_guide;             // svr_channel_sr_guide's volume, a copy of the call's own: set = every update of this begin..end is guided
+  float csr_delta_g = 0.0f;
+  bool csr_guide_only = false;
   bool have_em = false;                  // d_weights hold EM posteriors (svr_initialize_em_values or a later E-step; a test's svr_debug_set)
   int last_quality_chunks = -1;          // chunks per slice of the last svr_slice_quality (read-only option "quality_chunks"; -1 = not launched yet)
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
@@ -1872,7 +1875,8 @@ int launch_scatter(svr_ctx *ctx, int level, const PsfArgs &a_, const uint32_t *t
 void channel_sr_drop(svr_ctx *ctx) {
   ctx->d_csr_channel.reset(); ctx->d_csr_vol[0].reset(); ctx->d_csr_vol[1].reset(); ctx->d_csr_sim.reset(); ctx->d_csr_simw.reset();
   ctx->d_csr_unit_on.reset(); ctx->d_csr_cover.reset(); ctx->d_csr_inside.reset(); ctx->d_csr_slice_inside.reset();
-  ctx->csr_stage = 0; ctx->csr_cur = 0; ctx->csr_has_unit_on = false;
+  ctx->d_csr_guide.reset();
+  ctx->csr_stage = 0; ctx->csr_cur = 0; ctx->csr_has_unit_on = false; ctx->csr_delta_g = 0.0f; ctx->csr_guide_only = false;
 }
 
 void invalidate(svr_ctx *ctx, unsigned ch) {
@@ -3160,12 +3164,14 @@ static int superresolution_update_planes(svr_ctx *ctx, int adaptive, float alpha
     return SVR_OK;
   }
   RegulArgs ra;
+  ra.guide = nullptr;
   regul_thresholds(min_intensity, max_intensity, ra);
   return regul_fused_launch(ctx, ra, ctx->recon(), ctx->recon_cur == ctx->d_recon_volw ? ctx->d_recon_new : ctx->d_recon_volw, adaptive, alpha, delta, lambda,
                             z_lo, z_hi);
 }
 
-// k_regul_fused on planes [z_lo, z_hi) of `recon` with the context's addon | cmap -> out; ra brings the clamp (thr / val), everything else is set here
+// k_regul_fused on planes [z_lo, z_hi) of `recon` with the context's addon | cmap -> out; ra brings the clamp (thr / val) and the guide (NULL: the
+// unguided kernels; else gkap1..3 and omega with it), everything else is set here
 static int regul_fused_launch(svr_ctx *ctx, RegulArgs &ra, const float *recon, float *out, int adaptive, float alpha, float delta, float lambda, int z_lo,
                               int z_hi) {
   ra.recon = recon; ra.addon = ctx->addon(); ra.cmap = ctx->cmap();
@@ -3196,7 +3202,11 @@ static int regul_fused_launch(svr_ctx *ctx, RegulArgs &ra, const float *recon, f
   if (nz > 0) {
     const dim3 grid((ctx->vx + TW - 1) / TW, (ctx->vy + TH - 1) / TH, chunks);
     const dim3 block(TW * TH);
-#define REGUL_LAUNCH(AD, W, H) hipLaunchKernelGGL((k_regul_fused<AD, W, H>), grid, block, 0, ctx->stream, ra)
+#define REGUL_LAUNCH(AD, W, H)                                                                               \
+  do {                                                                                                       \
+    if (ra.guide) hipLaunchKernelGGL((k_regul_fused<AD, W, H, true>), grid, block, 0, ctx->stream, ra);      \
+    else hipLaunchKernelGGL((k_regul_fused<AD, W, H>), grid, block, 0, ctx->stream, ra);                     \
+  } while (0)
     if (adaptive) { if (pick == 0) REGUL_LAUNCH(true, 64, 8); else if (pick == 1) REGUL_LAUNCH(true, 32, 16); else REGUL_LAUNCH(true, 32, 8); }
     else { if (pick == 0) REGUL_LAUNCH(false, 64, 8); else if (pick == 1) REGUL_LAUNCH(false, 32, 16); else REGUL_LAUNCH(false, 32, 8); }
 #undef REGUL_LAUNCH

@@ -216,11 +216,16 @@ class irtkReconstruction {
 
   // n SR iterations on a channel (svr_channel_sr_*, include/svr_hip.h) with the weights ChannelReconstruct scatters with: the seed scatter and
   // every iteration's addon | cmap are summed over the ranks like ChannelReconstruct's pair, the volume update runs replicated on every rank.
-  // delta_c / lambda_c become the engine's parameters the way SetSmoothingParameters makes the primary's
+  // delta_c / lambda_c become the engine's parameters the way SetSmoothingParameters makes the primary's.  guided: svr_channel_sr_guide after the
+  // seed on every rank (guide_or_null = NULL: the rank's reconstruction, which every rank holds alike), so the replicated update stays replicated
   int ChannelSuperresolve(const float *channel_local, const unsigned char *unit_on_local, int n, double delta_c, double lambda_c, float clamp_lo, float clamp_hi,
-                          float *out_or_null) {
+                          float *out_or_null, bool guided = false, const float *guide_or_null = nullptr, double delta_g = 0, int guide_only = 0) {
     if (n < 0 || !std::isfinite(delta_c) || !(delta_c > 0) || !std::isfinite(lambda_c) || !(lambda_c > 0) || !(clamp_lo <= clamp_hi)) {
       err = "svrh_channel_superresolve: n >= 0, delta and lambda finite and positive, lo <= hi";
+      return SVR_E_ARG;
+    }
+    if (guided && (!std::isfinite(delta_g) || !(delta_g > 0) || !std::isfinite((float)delta_g))) {
+      err = "svrh_channel_superresolve_guided: delta_g finite and positive";
       return SVR_E_ARG;
     }
     const float *sw;
@@ -232,6 +237,7 @@ class irtkReconstruction {
       ENG(svr_channel_sr_begin(reconstructionGPU, channel_local, unit_on_local, sw, 0));
       if (sh.on) ENG(sh.allreduce_pair(SVR_BUF_ADDON, pair));
       ENG(svr_channel_sr_seed(reconstructionGPU, nullptr));
+      if (guided) ENG(svr_channel_sr_guide(reconstructionGPU, guide_or_null, (float)delta_g, guide_only ? SVR_CHANNEL_GUIDE_ONLY : 0));
       const auto t0 = std::chrono::steady_clock::now();
       for (int k = 0; k < n; ++k) {
         ENG(svr_channel_sr_backproject(reconstructionGPU));
@@ -245,8 +251,8 @@ class irtkReconstruction {
     const int rc = run();
     if (rc) (void)svr_channel_sr_end(reconstructionGPU, nullptr);       // (the call is over either way: its buffers go, the message stays)
     else if (n > 0 && getenv("SVR_CLI_TIMING"))                           // (every engine call blocks: the host clock around them is their cost)
-      fprintf(stderr, "[timing] channel SR iteration (gather, scatter%s, update), %d slices: %.3f ms each over %d (host clock)\n",
-              sh.on ? ", all-reduce" : "", hi - lo, ms / n, n);
+      fprintf(stderr, "[timing] channel SR iteration (gather, scatter%s, %supdate), %d slices: %.3f ms each over %d (host clock)\n",
+              sh.on ? ", all-reduce" : "", guided ? "guided " : "", hi - lo, ms / n, n);
     return rc;
   }
 
@@ -468,6 +474,11 @@ int svrh_channel_superresolve(svrh_recon *r, const float *channel_local, const u
                               float lo, float hi, float *out_or_null) {
   if (!r) return SVR_E_ARG;
   return r->impl.ChannelSuperresolve(channel_local, unit_on_local, n, delta_c, lambda_c, lo, hi, out_or_null);
+}
+int svrh_channel_superresolve_guided(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int n, double delta_c, double lambda_c,
+                                     float lo, float hi, float *out_or_null, const float *guide_or_null, double delta_g, int guide_only) {
+  if (!r) return SVR_E_ARG;
+  return r->impl.ChannelSuperresolve(channel_local, unit_on_local, n, delta_c, lambda_c, lo, hi, out_or_null, true, guide_or_null, delta_g, guide_only);
 }
 int svrh_initialize_em_values_gpu(svrh_recon *r) { return r->impl.InitializeEMValuesGPU(); }
 int svrh_gaussian_reconstruction_gpu(svrh_recon *r) { return r->impl.GaussianReconstructionGPU(); }

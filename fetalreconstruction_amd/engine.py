@@ -26,6 +26,7 @@ BUF_SIMINSIDE, BUF_VOXEL_COUNT = 20, 21
 T_BACKPROJECT, T_FORWARD, T_GAUSS, T_REGULARIZE, T_ESTEP, T_MSTEP, T_SCALE, T_REGISTER = range(8)
 RESAMPLE_INSTALL, RESAMPLE_SCALE = 1, 2                # SVR_RESAMPLE_* (include/svr_hip.h)
 CHANNEL_INDICATOR = 1                                  # SVR_CHANNEL_INDICATOR
+CHANNEL_GUIDE_ONLY = 1                                 # SVR_CHANNEL_GUIDE_ONLY
 REG_TARGETS, REG_SUM_A, REG_CNT_A, REG_SUM_B, REG_CNT_B, REG_MOMENTS, REG_SIMILARITIES, REG_GRADIENT, REG_ACTIVE = range(9)   # enum svr_reg_state
 TIMER_NAMES = ("backproject", "forward", "gauss", "regularize", "estep", "mstep", "scale", "register", "allreduce", "exchange_host", "coeff_build", "reduce_scatter", "allgather",
                "backproject_table", "forward_table", "forward_store", "backproject_store")
@@ -51,6 +52,7 @@ EXPORTS = [
     "svr_get_scale_vector", "svr_adopt_scale_vector", "svr_get_slice_inside", "svr_mstep_estep", "svr_mstep_sums_fetch", "svr_mstep_partial", "svr_mstep_estep_ranks",
     "svr_channel_scatter", "svr_channel_finish", "svr_channel_vote", "svr_channel_vote_fetch",
     "svr_channel_sr_begin", "svr_channel_sr_seed", "svr_channel_sr_backproject", "svr_channel_sr_update", "svr_channel_sr_end",
+    "svr_channel_sr_guide",
 ]
 
 
@@ -579,6 +581,15 @@ class Reconstruction:
         if s is not None and s.size != int(np.prod(self.vsize)):
             raise SvrError("channel_sr_seed: a value per voxel expected")
         self._ck(self._lib.svr_channel_sr_seed(self._h, None if s is None else _p(s)))
+
+    def channel_sr_guide(self, guide=None, delta_g=1.0, guide_only=False, flags=None):
+        """svr_channel_sr_guide: every later update of this begin..end weighs a pair by the guide's differences too (delta_g: their edge scale;
+        guide_only: without the channel's own).  guide: a value per voxel, or None = a copy of the reconstruction as the device holds it now"""
+        g = None if guide is None else _f32(guide)
+        if g is not None and g.size != int(np.prod(self.vsize)):
+            raise SvrError("channel_sr_guide: a value per voxel expected")
+        f = (CHANNEL_GUIDE_ONLY if guide_only else 0) if flags is None else int(flags)
+        self._ck(self._lib.svr_channel_sr_guide(self._h, None if g is None else _p(g), C.c_float(delta_g), f))
 
     def channel_sr_backproject(self):
         """svr_channel_sr_backproject: forward projection of the channel volume, residuals, scatter -> BUF_ADDON | BUF_CONFIDENCE_MAP"""

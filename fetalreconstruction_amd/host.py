@@ -25,6 +25,7 @@ HOST_EXPORTS = [
     "svrh_normalise_bias_gpu", "svrh_prepare_registration_slices", "svrh_slice_to_volume_registration_gpu",
     "svrh_get_registration_slices", "svrh_force_collectives", "svrh_set_slab_update", "svrh_set_unit_order", "svrh_channel_reconstruct",
     "svrh_channel_superresolve",
+    "svrh_channel_superresolve_guided",
     "svrh_set_structural", "svrh_structural_evaluate", "svrh_get_structural",
 ]
 PVR_HOST_EXPORTS = ["pvrh_create", "pvrh_destroy", "pvrh_last_error", "pvrh_initialize_em_values", "pvrh_initialize_robust_statistics",
@@ -302,6 +303,21 @@ class irtkReconstruction:
         self._ck(self._lib.svrh_channel_superresolve(self._h, c.ctypes.data_as(C.c_void_p), None if u is None else u.ctypes.data_as(C.c_void_p),
                                                      int(n), C.c_double(delta_c), C.c_double(lambda_c), C.c_float(lo), C.c_float(hi),
                                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def ChannelSuperresolveGuided(self, channel_local, unit_on_local, n, delta_c, lambda_c, lo, hi, nvox, guide=None, delta_g=1.0, guide_only=False):
+        """svrh_channel_superresolve_guided: ChannelSuperresolve with the update guided by `guide`'s edges (flat, nvox floats; None = the
+        reconstruction as the device holds it), edge scale delta_g; guide_only: without the channel's own differences"""
+        c = np.ascontiguousarray(channel_local, np.float32)
+        u = None if unit_on_local is None else np.ascontiguousarray(unit_on_local, np.uint8)
+        g = None if guide is None else np.ascontiguousarray(guide, np.float32).ravel()
+        if g is not None and g.size != int(nvox):
+            raise ValueError("ChannelSuperresolveGuided: a guide value per voxel expected")
+        out = np.empty(int(nvox), np.float32)
+        self._ck(self._lib.svrh_channel_superresolve_guided(self._h, c.ctypes.data_as(C.c_void_p), None if u is None else u.ctypes.data_as(C.c_void_p),
+                                                            int(n), C.c_double(delta_c), C.c_double(lambda_c), C.c_float(lo), C.c_float(hi),
+                                                            out.ctypes.data_as(C.c_void_p), None if g is None else g.ctypes.data_as(C.c_void_p),
+                                                            C.c_double(delta_g), 1 if guide_only else 0))
         return out
 
     def InitializeEMValuesGPU(self):

@@ -427,6 +427,20 @@ int svr_channel_sr_seed(svr_ctx *ctx, const float *seed_or_null);
 int svr_channel_sr_backproject(svr_ctx *ctx);
 int svr_channel_sr_update(svr_ctx *ctx, int adaptive, float alpha, float lo, float hi, float delta, float lambda);
 int svr_channel_sr_end(svr_ctx *ctx, float *out_or_null);
+/* Guide the channel's regulariser by a second volume's edges (the command line's --channelGuide; no reference equivalent).  After this call every
+ * svr_channel_sr_update of the begin..end in flight weighs a neighbour pair (p, q) in direction d, f = 1 / |d|_1, by
+ *     b = f / sqrt(1 + omega f ((C_q - C_p) / delta)^2 + f ((G_q - G_p) / delta_g)^2)
+ * with C the pre-update channel volume, G the guide [nv] on the reconstruction grid, omega = 1, or 0 with SVR_CHANNEL_GUIDE_ONLY.  Everything else
+ * of the update stays: b = 0 where either post-Prep confidence is <= 0 or q lies outside the volume, k = alpha lambda / delta^2 (delta still defines k
+ * with SVR_CHANNEL_GUIDE_ONLY).  The guide never gates; only its differences enter, so a constant guide gives the unguided update's bits.
+ * guide_or_null: host memory, or NULL = the context's reconstruction as it is now, copied device to device.  Either way the guide is a buffer of the
+ * call's own ([nv] floats, freed with the other buffers of the call): nothing the run does later changes it, and the reconstruction is never
+ * written.  A second call replaces the guide.  Legal after svr_channel_sr_begin until svr_channel_sr_end, except between a back-projection and its
+ * update.  Refused with a message and a status, never a fault, the context and the call in flight stay usable (a guide set before stays): no call in
+ * flight or the wrong stage, delta_g not finite and positive, an unknown flag, a guide value that is not finite (a host guide, checked before the
+ * upload), reg_mode other than 1. */
+#define SVR_CHANNEL_GUIDE_ONLY 1
+int svr_channel_sr_guide(svr_ctx *ctx, const float *guide_or_null, float delta_g, int flags);
 
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::

@@ -120,6 +120,13 @@ int svrh_channel_reconstruct(svrh_recon *r, const float *channel_local, const un
  * reaches.  Whatever fails, the engine's call is ended and its buffers are freed. */
 int svrh_channel_superresolve(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int n, double delta_c, double lambda_c,
                               float lo, float hi, float *out_or_null);
+/* The same with the update guided by a volume's edges (svr_channel_sr_guide, include/svr_hip.h; the command line's --channelGuide), collective in the
+ * same way: the guide is set after the seed on every rank -- guide_or_null [nvox] host floats, the same on every rank, or NULL = the rank's
+ * reconstruction as the device holds it, which every rank holds alike -- and the update stays replicated.  delta_g: the guide's edge scale, in the
+ * guide's units, finite and positive; guide_only != 0: the channel's own differences leave the weight (delta_c still scales lambda_c).
+ * svrh_channel_superresolve is this call without a guide. */
+int svrh_channel_superresolve_guided(svrh_recon *r, const float *channel_local, const unsigned char *unit_on_local, int n, double delta_c, double lambda_c,
+                                     float lo, float hi, float *out_or_null, const float *guide_or_null, double delta_g, int guide_only);
 
 int svrh_initialize_em_values_gpu(svrh_recon *r);
 int svrh_gaussian_reconstruction_gpu(svrh_recon *r);
