@@ -8,7 +8,7 @@ import pytest
 from tests import operator_entries as O
 from tests.util import rel_err
 
-CASES = [(name, pvr) for name in O.PROBLEMS for pvr in (False, True)]
+CASES = [(name, pvr) for name in O.PROBLEMS + O.RUNG_PROBLEMS for pvr in (False, True)]       # (the coarse problem of tests/tile_rungs.py too)
 TOL_SUM = 2e-5                                   # tests/test_parity_gpu.py
 
 
@@ -21,7 +21,8 @@ def test_pixel_sets_cover_every_class(name, pvr):
     sets, classes = O.impulse_pixel_sets(name, pvr)
     P = O.problem(name)
     pixels = [p for s in sets for p in s]
-    assert len(pixels) == len(set(pixels)) == len(classes) and len(sets) >= 2
+    # (the coarse problem's pixels lie 6 voxels apart in four slices across a 96^3 volume: one set holds them all)
+    assert len(pixels) == len(set(pixels)) == len(classes) and len(sets) >= (1 if name in O.RUNG_PROBLEMS else 2)
     assert all(P.slices[sl, py, px] != -1 for sl, px, py in pixels)
     have = set().union(*classes.values())
     assert not [c for c in O.REQUIRED[name] if c not in have], sorted(have)
