@@ -41,13 +41,16 @@
 // --structural (a deviation: the reference leaves a slice out by its intensity residuals or --force_exclude only) lets every outer
 // iteration end with the slices' mean windowed SSIM against their simulation (svr_slice_ssim, csrc/svr_ssim.inc) and treats a slice that
 // falls out of its stack (svr_structural_decide) like a --force_exclude slice during the next one; it lives in svrh_reconstruct_iteration.
+// --echoStacks <x> f_1 .. f_N (a deviation), given 2 to 16 times, carries a multi-echo or diffusion series through one run: every echo is a channel
+// set of its own (the same reading, cropping, packing and reconstruction), written as --echoOutput <prefix><k>.nii.gz, and --fitRate / --fitT /
+// --fitAmplitude / --fitResidual / --fitCount fit S(x) = A exp(-R x) to the reconstructed echoes voxel by voxel (svr_monoexp_fit, csrc/svr_fit.inc).
 // Not built, refused loudly: patch/superpixel modes, the CPU reconstruction path.
 //
 // Where things are.  Three plain structs: Options (what the command line says; const after parse_options), Problem (the host-side
 // data: stacks, mask, template, the packed slices, the second images) and Ranks (svr_launch.h) with one svrh_recon* per rank.
 //   usage
-//   second images      declare_extras, read_extras, crop_extras_with, pack_extras, dump_channels, reconstruct_extras -- all of
-//                      --channelStacks / --labelStacks / --manualMask, next to each other
+//   second images      declare_extras, read_extras, crop_extras_with, pack_extras, dump_channels, superresolve_extra, reconstruct_extras,
+//                      fit_echoes -- all of --channelStacks / --labelStacks / --manualMask / --echoStacks, next to each other
 //   options            parse_options (with every refusal that needs no file, in a fixed order)
 //   set-up             read_inputs, make_mask, select_template_by_motion, make_template, crop_and_register_stacks, pack_slices (--sfolder)
 //   engines            dump_problem, shard_slices, setup_engines, read_tfolder, seed_reference_volume
@@ -94,6 +97,15 @@ struct Options {
   bool channel_guide = false, channel_guide_only = false;                 // --channelGuide, --channelGuideOnly (not reference options): the -o volume's edges
   double channel_guide_delta = 0;                                         // --channelGuideDelta; 0 = not given (from --delta and the ranges)
   bool have_channel_guide_opt = false;                                    // --channelGuideDelta or --channelGuideOnly was named
+  std::vector<std::string> echo_x;                                       // --echoStacks <x> f_1 .. f_N (not reference options), once per echo: the abscissa as given,
+  std::vector<std::vector<std::string>> echo_names;                      // ... and a file or `none` per -i stack
+  std::string echo_out;                                                   // --echoOutput <prefix>: echo k is written as <prefix><k>.nii.gz
+  int echo_iterations = 0;                                                // --echoIterations: SR iterations on every echo, as --channelIterations on the channel
+  bool echo_guide = false;                                                // --echoGuide: as --channelGuide
+  std::string fit_rate, fit_t, fit_amplitude, fit_residual, fit_count;   // --fitRate, --fitT, --fitAmplitude, --fitResidual, --fitCount: S(x) = A exp(-R x) over the echoes
+  int fit_iterations = 0;                                                 // --fitIterations: Gauss-Newton steps after the log-linear fit
+  double fit_floor = 0, fit_max_t = 0;                                    // --fitFloor; --fitMaxT (0 = not given: ten times the largest |x|)
+  bool have_echo_dep_opt = false;                                         // an --echo* / --fit* option other than --echoStacks was named
   int coeff_table = -1;                                                   // -1: the engine's default (on since round 6), 1 / 0: --coeffTable / --noCoeffTable
   size_t tmpl = 0;                                                        // the first stack whose -t is id (main.cc:452-457)
 };
@@ -108,6 +120,8 @@ struct ExtraSet {
   std::vector<float> grid;             // [ns][my][mx], 0 outside a slice's extent
   std::vector<unsigned char> unit_on;  // [ns]
   std::vector<float> label_values;     // ascending
+  int echo = -1;                       // --echoStacks: which echo, in the order given (-1: not an echo)
+  double x = 0;                        // ... and its abscissa
 };
 
 // the host-side data.  The per-slice arrays are in the reference's order (stack after stack) until shard_slices, in the sharded
@@ -147,6 +161,9 @@ void usage() {
          "       [--useAutoTemplate] [--autoTemplateCentral] [--sliceReport file] [--simulatedStacks prefix] [--referenceVolume file]\n"
          "       [--channelStacks f_1 .. f_N --channelOutput file [--channelIterations 0] [--channelDelta d] [--channelLambda l]\n"
          "        [--channelGuide [--channelGuideDelta d] [--channelGuideOnly]]]\n"
+         "       [--echoStacks x_1 f_1 .. f_N --echoStacks x_2 f_1 .. f_N [--echoStacks ..] [--echoOutput prefix] [--echoIterations 0] [--echoGuide]\n"
+         "        [--fitRate file] [--fitT file] [--fitAmplitude file] [--fitResidual file] [--fitCount file] [--fitMaxT Tmax] [--fitIterations 0]\n"
+         "        [--fitFloor 0]]\n"
          "       [--labelStacks f_1 .. f_N --labelOutput file [--labelConfidence file]]\n"
          "       [--manualMask file]\n"
          "       [--structural [--structuralRadius 3] [--structuralK 3] [--structuralMinDrop 0.1] [--structuralMinPixels 25]]\n"
@@ -192,6 +209,27 @@ void usage() {
          "                          written volume's range inside the mask over the run's intensity range].  Needs --channelGuide.\n"
          "  --channelGuideOnly      deviation from the reference: the channel's own differences leave the weight (--channelDelta still scales\n"
          "                          --channelLambda).  Needs --channelGuide.\n"
+         "  --echoStacks <x> f_1 .. f_N\n"
+         "                          deviation from the reference, which has no such option: one acquisition of a multi-echo or diffusion series,\n"
+         "                          given 2 to 16 times in one run.  <x> is its abscissa (echo time, b-value): a finite number, all different; then a\n"
+         "                          file or `none` per -i stack under the rules of --channelStacks.  Every echo is reconstructed like a channel of its\n"
+         "                          own with the run's one motion estimate and its robust weights, after the -o volume and the other second images\n"
+         "                          are written.  Needs --echoOutput or a --fit* output.  Not with --sfolder.  The -o volume, --channelOutput and\n"
+         "                          --labelOutput are the same with and without it.  One stderr line per echo.\n"
+         "  --echoOutput <prefix>   deviation from the reference: write echo k (from 0, in the order given) as <prefix><k>.nii.gz.\n"
+         "  --echoIterations n      deviation from the reference: refine every echo by n super-resolution iterations [0], exactly as\n"
+         "                          --channelIterations n refines the channel: delta from the echo's own range, lambda from --lastIterLambda, the clamp\n"
+         "                          widened by a tenth.  --echoGuide: as --channelGuide, with delta_g by the same rule; needs --echoIterations > 0.\n"
+         "  --fitRate <file> --fitT <file> --fitAmplitude <file> --fitResidual <file> --fitCount <file>\n"
+         "                          deviation from the reference: fit S(x) = A exp(-R x) to the reconstructed echoes, voxel by voxel on the device, and\n"
+         "                          write R (R2*, R2, ADC), T = 1 / R, A, the root mean square residual of the fit and the number of echoes that\n"
+         "                          counted, on the reconstruction grid.  An echo counts in a voxel when its value is finite and above --fitFloor v\n"
+         "                          [0, not negative]; with fewer than two, or a degenerate system, every map is 0 there.  The fit is the log-linear\n"
+         "                          one weighted by the squared signal; --fitIterations n [0, at most 50] adds n Gauss-Newton steps on the signal\n"
+         "                          itself, kept where they do not raise the residual.  --fitT is 1 / R where R > 1 / Tmax, Tmax where a fitted\n"
+         "                          voxel has R <= 1 / Tmax, 0 where nothing was fitted; --fitMaxT Tmax [ten times the largest |x|].  No Rician\n"
+         "                          bias handling, no second component.  One stderr line reports the fitted voxels and their median T.\n"
+         "                          All of these need --echoStacks.\n"
          "  --labelStacks f_1 .. f_N --labelOutput <file> [--labelConfidence <file>]\n"
          "                          deviation from the reference: a label map per -i stack (integers in 0..65535, at most 64 different\n"
          "                          ones; 0 competes like any other label; `none` = the stack has none).  Each label's indicator image is\n"
@@ -272,7 +310,27 @@ void declare_extras(const Options &p, std::vector<ExtraSet> &extras) {
                                                      : p.manual_name.substr(0, cut + 1) + "PSFTransformed_" + p.manual_name.substr(cut + 1);
     add("--manualMask", false, names, out, "");
   }
-  if (!p.channels_dump.empty() && extras.empty()) die("--dumpChannels writes the packed grids of --channelStacks / --labelStacks / --manualMask: give one of them");
+  // --echoStacks: a set per echo, after the others, in the order given
+  const size_t K = p.echo_x.size();
+  if (K && (K < 2 || K > 16)) die("--echoStacks: " + std::to_string(K) + " echo sets; a run takes 2 to 16 (one --echoStacks <x> f_1 .. f_N per echo)");
+  const bool any_fit = !p.fit_rate.empty() || !p.fit_t.empty() || !p.fit_amplitude.empty() || !p.fit_residual.empty() || !p.fit_count.empty();
+  if (K && p.echo_out.empty() && !any_fit)
+    die("--echoStacks needs --echoOutput <prefix> for the reconstructed echoes or a --fitRate / --fitT / --fitAmplitude / --fitResidual / --fitCount <file>");
+  std::vector<double> xs;
+  for (size_t k = 0; k < K; ++k) {
+    char *end = nullptr;
+    const double x = strtod(p.echo_x[k].c_str(), &end);
+    if (p.echo_x[k].empty() || *end || !std::isfinite(x))
+      die("--echoStacks: `" + p.echo_x[k] + "` is not a finite number: the first value is the echo's abscissa (echo time, b-value), then a file or `none` per -i stack");
+    if (std::find(xs.begin(), xs.end(), x) != xs.end()) die("--echoStacks: the abscissa " + p.echo_x[k] + " is given twice: a duplicate x fits nothing");
+    xs.push_back(x);
+  }
+  for (size_t k = 0; k < K; ++k) {
+    add(("--echoStacks " + p.echo_x[k]).c_str(), false, p.echo_names[k], p.echo_out.empty() ? "" : p.echo_out + std::to_string(k) + ".nii.gz", "");
+    extras.back().echo = (int)k;
+    extras.back().x = xs[k];
+  }
+  if (!p.channels_dump.empty() && extras.empty()) die("--dumpChannels writes the packed grids of --channelStacks / --labelStacks / --manualMask / --echoStacks: give one of them");
 }
 
 void read_extras(const Options &opt, Problem &P) {
@@ -355,13 +413,83 @@ void dump_channels(const std::string &name, const Problem &P) {
   fclose(f);
 }
 
+// What the SR iterations on a second image are asked: --channelIterations and its companions for the channel, --echoIterations / --echoGuide with
+// every default for an echo.  The two names head the stderr lines
+struct ExtraSr {
+  const char *iterations_name, *guide_name;
+  int iterations;
+  double delta, lambda, guide_delta;     // 0 = not given
+  bool guide, guide_only;
+};
+
+// --channelIterations / --echoIterations: the average of a second image refined by SR iterations with the run's final motion and weights
+// (svrh_channel_superresolve; collective) -> out on rank 0
+void superresolve_extra(const ExtraSr &q, const Options &opt, const Problem &P, const Ranks &R, const std::vector<svrh_recon *> &hosts, const ExtraSet &e,
+                        std::vector<float> &out) {
+  const size_t nvv = (size_t)P.tattr.nx * P.tattr.ny * P.tattr.nz, slice = (size_t)P.mx * P.my;
+  svr_ctx *ctx = R.ctxs[0];
+  // the channel's range over the pixels that can count -- the primary pixel is not -1, the stack has a channel --, over every rank's slices
+  double c_min = INFINITY, c_max = -INFINITY;
+  for (int s = 0; s < P.ns; ++s) {
+    if (!e.unit_on[s]) continue;
+    for (size_t i = 0; i < slice; ++i) {
+      const size_t g = (size_t)s * slice + i;
+      if (P.grid[g] == -1.0f) continue;
+      c_min = std::min(c_min, (double)e.grid[g]); c_max = std::max(c_max, (double)e.grid[g]);
+    }
+  }
+  if (!(c_max >= c_min) || !std::isfinite(c_min) || !std::isfinite(c_max)) die(e.what + ": no finite channel value lies inside the mask");
+  const double R_c = c_max - c_min, R_s = P.vmax - P.vmin;
+  const double lambda_c = q.lambda > 0 ? q.lambda : opt.last_lambda;
+  const double delta_c = q.delta > 0 ? q.delta : (R_s > 0 ? opt.delta * R_c / R_s : 0.0);
+  // a constant channel has nothing to refine (and no scale for delta): the average is the answer
+  const int n_it = R_c > 0 && delta_c > 0 ? q.iterations : 0;
+  fprintf(stderr, "%s %d%s: delta %.9g lambda %.9g alpha %.9g, channel range [%.9g, %.9g], clamp [%.9g, %.9g]\n", q.iterations_name, q.iterations,
+          n_it ? "" : " (constant channel: none run)", delta_c, lambda_c, std::min(1.0, 0.05 / lambda_c), c_min, c_max, c_min - 0.1 * R_c, c_max + 0.1 * R_c);
+  // the guide: the written volume, which every rank's device still holds (NULL = a copy of it).  Its range over the mask's voxels gives
+  // delta_g the way the channel's range gives delta_c
+  bool guided = q.guide && n_it > 0;
+  double delta_g = 0.0;
+  if (guided) {
+    std::vector<float> vol(nvv);
+    ENGR(R, 0, svr_sync_cpu(ctx, vol.data()));
+    double g_min = INFINITY, g_max = -INFINITY;
+    for (size_t i = 0; i < nvv; ++i)
+      if (P.vol_mask.d[i] != 0) { g_min = std::min(g_min, (double)vol[i]); g_max = std::max(g_max, (double)vol[i]); }
+    const double R_g = g_max >= g_min && std::isfinite(g_min) && std::isfinite(g_max) ? g_max - g_min : 0.0;
+    delta_g = q.guide_delta > 0 ? q.guide_delta : (R_s > 0 ? opt.delta * R_g / R_s : 0.0);
+    if (!(R_g > 0) || !(delta_g > 0) || !std::isfinite(delta_g)) {
+      fprintf(stderr, "%s: the written volume is constant inside the mask (range %.9g) and guides nothing: dropped\n", q.guide_name, R_g);
+      guided = false;
+    } else {
+      fprintf(stderr, "%s: delta_g %.9g, guide range %.9g [%.9g, %.9g], %s\n", q.guide_name, delta_g, R_g, g_min, g_max,
+              q.guide_only ? "guide only" : "joint with the channel's differences");
+    }
+  }
+  R.par([&](int r) {
+    const size_t o = (size_t)R.rlo[r];
+    if (guided)
+      HOSTR(r, svrh_channel_superresolve_guided(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, delta_c, lambda_c,
+                                                (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr, nullptr,
+                                                delta_g, q.guide_only ? 1 : 0));
+    else
+      HOSTR(r, svrh_channel_superresolve(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, n_it ? delta_c : 1.0, lambda_c,
+                                         (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr));
+  });
+}
+
 // The second images into the reconstructed space (not in the reference's main() but for --manualMask, reconstruction.cc:1240-1250).  The
 // volume is on disk: nothing from here on can reach it.  Every rank scatters its own slices with the weights the last SR iteration
-// would scatter with, the ranks' sums are brought together (svrh_channel_reconstruct), and rank 0 divides or votes.
-void reconstruct_extras(const Options &opt, const Problem &P, const Ranks &R, const std::vector<svrh_recon *> &hosts, bool timing) {
+// would scatter with, the ranks' sums are brought together (svrh_channel_reconstruct), and rank 0 divides or votes.  The echoes of
+// --echoStacks come last, in the order given, and stay in `echoes` ([K][nvv]) for the fit.
+void reconstruct_extras(const Options &opt, const Problem &P, const Ranks &R, const std::vector<svrh_recon *> &hosts, bool timing, std::vector<float> &echoes) {
   const size_t nvv = (size_t)P.tattr.nx * P.tattr.ny * P.tattr.nz, slice = (size_t)P.mx * P.my;
   svr_ctx *ctx = R.ctxs[0];
   char err[256] = {0};
+  const ExtraSr channel_sr{"--channelIterations", "--channelGuide", opt.channel_iterations, opt.channel_delta, opt.channel_lambda, opt.channel_guide_delta,
+                           opt.channel_guide, opt.channel_guide_only};
+  const ExtraSr echo_sr{"--echoIterations", "--echoGuide", opt.echo_iterations, 0.0, 0.0, 0.0, opt.echo_guide, false};
+  echoes.assign(opt.echo_x.size() * nvv, 0.0f);
   double t_sr = 0.0, t_scatter = 0.0;
   int n_scatter = 0;
   if (timing) {
@@ -392,65 +520,19 @@ void reconstruct_extras(const Options &opt, const Problem &P, const Ranks &R, co
   };
   for (auto &e : P.extras) {
     std::vector<float> out(nvv), cover(nvv);
-    if (!e.labels && opt.channel_iterations > 0 && e.what == "--channelStacks") {
-      // --channelIterations: the average refined by SR iterations with the run's final motion and weights (svrh_channel_superresolve).  The
-      // channel's range over the pixels that can count -- the primary pixel is not -1, the stack has a channel --, over every rank's slices
-      double c_min = INFINITY, c_max = -INFINITY;
-      for (int s = 0; s < P.ns; ++s) {
-        if (!e.unit_on[s]) continue;
-        for (size_t i = 0; i < slice; ++i) {
-          const size_t g = (size_t)s * slice + i;
-          if (P.grid[g] == -1.0f) continue;
-          c_min = std::min(c_min, (double)e.grid[g]); c_max = std::max(c_max, (double)e.grid[g]);
-        }
-      }
-      if (!(c_max >= c_min) || !std::isfinite(c_min) || !std::isfinite(c_max)) die(e.what + ": no finite channel value lies inside the mask");
-      const double R_c = c_max - c_min, R_s = P.vmax - P.vmin;
-      const double lambda_c = opt.channel_lambda > 0 ? opt.channel_lambda : opt.last_lambda;
-      const double delta_c = opt.channel_delta > 0 ? opt.channel_delta : (R_s > 0 ? opt.delta * R_c / R_s : 0.0);
-      // a constant channel has nothing to refine (and no scale for delta): the average is the answer
-      const int n_it = R_c > 0 && delta_c > 0 ? opt.channel_iterations : 0;
-      fprintf(stderr, "--channelIterations %d%s: delta %.9g lambda %.9g alpha %.9g, channel range [%.9g, %.9g], clamp [%.9g, %.9g]\n", opt.channel_iterations,
-              n_it ? "" : " (constant channel: none run)", delta_c, lambda_c, std::min(1.0, 0.05 / lambda_c), c_min, c_max, c_min - 0.1 * R_c, c_max + 0.1 * R_c);
-      // --channelGuide: the written volume, which every rank's device still holds (NULL = a copy of it).  Its range over the mask's voxels gives
-      // delta_g the way the channel's range gives delta_c
-      bool guided = opt.channel_guide && n_it > 0;
-      double delta_g = 0.0;
-      if (guided) {
-        std::vector<float> vol(nvv);
-        ENGR(R, 0, svr_sync_cpu(ctx, vol.data()));
-        double g_min = INFINITY, g_max = -INFINITY;
-        for (size_t i = 0; i < nvv; ++i)
-          if (P.vol_mask.d[i] != 0) { g_min = std::min(g_min, (double)vol[i]); g_max = std::max(g_max, (double)vol[i]); }
-        const double R_g = g_max >= g_min && std::isfinite(g_min) && std::isfinite(g_max) ? g_max - g_min : 0.0;
-        delta_g = opt.channel_guide_delta > 0 ? opt.channel_guide_delta : (R_s > 0 ? opt.delta * R_g / R_s : 0.0);
-        if (!(R_g > 0) || !(delta_g > 0) || !std::isfinite(delta_g)) {
-          fprintf(stderr, "--channelGuide: the written volume is constant inside the mask (range %.9g) and guides nothing: dropped\n", R_g);
-          guided = false;
-        } else {
-          fprintf(stderr, "--channelGuide: delta_g %.9g, guide range %.9g [%.9g, %.9g], %s\n", delta_g, R_g, g_min, g_max,
-                  opt.channel_guide_only ? "guide only" : "joint with the channel's differences");
-        }
-      }
-      R.par([&](int r) {
-        const size_t o = (size_t)R.rlo[r];
-        if (guided)
-          HOSTR(r, svrh_channel_superresolve_guided(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, delta_c, lambda_c,
-                                                    (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr, nullptr,
-                                                    delta_g, opt.channel_guide_only ? 1 : 0));
-        else
-          HOSTR(r, svrh_channel_superresolve(hosts[r], e.grid.data() + o * slice, e.unit_on.data() + o, n_it, n_it ? delta_c : 1.0, lambda_c,
-                                             (float)(c_min - 0.1 * R_c), (float)(c_max + 0.1 * R_c), r == 0 ? out.data() : nullptr));
-      });
-      if (svr_nifti_write(e.out.c_str(), &P.tattr, out.data(), err)) die(e.out + ": " + err);
+    const bool sr = !e.labels && (e.echo >= 0 ? opt.echo_iterations > 0 : opt.channel_iterations > 0 && e.what == "--channelStacks");
+    if (sr) {
+      // --channelIterations on the channel, --echoIterations on every echo: the same refinement, the echoes with the defaults
+      superresolve_extra(e.echo >= 0 ? echo_sr : channel_sr, opt, P, R, hosts, e, out);
+      if (!e.out.empty() && svr_nifti_write(e.out.c_str(), &P.tattr, out.data(), err)) die(e.out + ": " + err);
       for (size_t i = 0; i < nvv; ++i) cover[i] = out[i] != 0.0f ? 1.0f : 0.0f;                          // (0 where no slice with a channel reaches)
-      say(e.what + " (non-zero voxels)", e.out, out, cover);
+      say(e.what + " (non-zero voxels)", e.out.empty() ? "(not written)" : e.out, out, cover);
     } else if (!e.labels) {
       scatter(e, 0, 0.0f);
       ENGR(R, 0, svr_channel_finish(ctx, 0.0f, out.data()));
       ENGR(R, 0, svr_debug_get(ctx, SVR_BUF_CONFIDENCE_MAP, cover.data(), nvv * sizeof(float)));        // den: where it is positive a slice reached
-      if (svr_nifti_write(e.out.c_str(), &P.tattr, out.data(), err)) die(e.out + ": " + err);
-      say(e.what, e.out, out, cover);
+      if (!e.out.empty() && svr_nifti_write(e.out.c_str(), &P.tattr, out.data(), err)) die(e.out + ": " + err);
+      say(e.what, e.out.empty() ? "(not written)" : e.out, out, cover);
     } else {
       for (size_t k = 0; k < e.label_values.size(); ++k) {
         scatter(e, SVR_CHANNEL_INDICATOR, e.label_values[k]);
@@ -464,12 +546,52 @@ void reconstruct_extras(const Options &opt, const Problem &P, const Ranks &R, co
         say("--labelConfidence", e.conf, cover, cover);
       }
     }
+    if (e.echo >= 0) std::copy(out.begin(), out.end(), echoes.begin() + (size_t)e.echo * nvv);         // what was (or would have been) written: the fit's input
   }
   if (timing && !n_scatter)                                               // (only a channel with --channelIterations: its own line gave the iterations' time)
     fprintf(stderr, "[timing] one SR scatter of rank 0's slices %.3f ms (host clock)\n", 1e3 * t_sr);
   else if (timing)
     fprintf(stderr, "[timing] %d channel / label scatters, %.3f ms each (upload, scatter%s; slowest rank, host clock); one SR scatter of rank 0's slices %.3f ms\n",
             n_scatter, 1e3 * t_scatter / std::max(1, n_scatter), R.nr > 1 ? ", all-reduce" : "", 1e3 * t_sr);
+}
+
+// --fitRate / --fitT / --fitAmplitude / --fitResidual / --fitCount: S(x) = A exp(-R x) over the echoes as they were (or would have been) written,
+// voxel by voxel on rank 0's device (svr_monoexp_fit, csrc/svr_fit.inc).  The echoes are on disk: nothing from here on can reach them.
+void fit_echoes(const Options &opt, const Problem &P, const Ranks &R, const std::vector<float> &echoes, bool timing) {
+  const size_t nvv = (size_t)P.tattr.nx * P.tattr.ny * P.tattr.nz;
+  std::vector<double> x;
+  for (auto &e : P.extras) if (e.echo >= 0) x.push_back(e.x);
+  const int K = (int)x.size();
+  double x_abs = 0;
+  for (double v : x) x_abs = std::max(x_abs, fabs(v));
+  const double t_max = opt.fit_max_t > 0 ? opt.fit_max_t : 10.0 * x_abs;
+  std::vector<float> rate(nvv), amplitude(nvv), rmse(nvv), count(nvv), t(nvv);
+  const auto t0 = std::chrono::steady_clock::now();
+  ENGR(R, 0, svr_monoexp_fit(R.ctxs[0], K, x.data(), echoes.data(), nvv, opt.fit_iterations, (float)opt.fit_floor, rate.data(), amplitude.data(), rmse.data(),
+                             count.data()));
+  const double t_fit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  // T = 1 / R where R > 1 / Tmax, Tmax where a fitted voxel has a smaller (or negative) rate, 0 where nothing was fitted: an amplitude is the
+  // exponential of something, so 0 only where the fit was refused
+  std::vector<float> fitted_t;
+  for (size_t i = 0; i < nvv; ++i) {
+    if (!(amplitude[i] > 0.0f)) { t[i] = 0.0f; continue; }
+    const double r = (double)rate[i];
+    t[i] = (float)(r > 1.0 / t_max ? 1.0 / r : t_max);
+    fitted_t.push_back(t[i]);
+  }
+  char err[256] = {0};
+  const std::pair<const std::string *, const std::vector<float> *> files[5] = {
+      {&opt.fit_rate, &rate}, {&opt.fit_t, &t}, {&opt.fit_amplitude, &amplitude}, {&opt.fit_residual, &rmse}, {&opt.fit_count, &count}};
+  for (auto &f : files)
+    if (!f.first->empty() && svr_nifti_write(f.first->c_str(), &P.tattr, f.second->data(), err)) die(*f.first + ": " + err);
+  std::sort(fitted_t.begin(), fitted_t.end());
+  const size_t m = fitted_t.size();
+  if (m)
+    fprintf(stderr, "--fit over %d echoes: %zu fitted voxels, median T %.9g (Tmax %.9g, %d Gauss-Newton iterations, floor %.9g)\n", K, m,
+            m % 2 ? (double)fitted_t[m / 2] : 0.5 * ((double)fitted_t[m / 2 - 1] + (double)fitted_t[m / 2]), t_max, opt.fit_iterations, opt.fit_floor);
+  else
+    fprintf(stderr, "--fit over %d echoes: no fitted voxel\n", K);
+  if (timing) fprintf(stderr, "[timing] mono-exponential fit of %d volumes of %zu voxels %.3f ms (upload, kernel, download; host clock)\n", K, nvv, 1e3 * t_fit);
 }
 
 // ---- the option loop and, in this order, every refusal that needs no file; the second images are declared on the way --------------
@@ -533,6 +655,24 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
     else if (a.is("--channelGuide")) p.channel_guide = true;              // not reference options: the channel's update guided by the -o volume's edges
     else if (a.is("--channelGuideDelta")) { p.have_channel_guide_opt = true; p.channel_guide_delta = a.one_double(); if (!(p.channel_guide_delta > 0) || !std::isfinite(p.channel_guide_delta)) die("--channelGuideDelta must be positive"); }
     else if (a.is("--channelGuideOnly")) { p.have_channel_guide_opt = true; p.channel_guide_only = true; }
+    else if (a.is("--echoStacks")) {                                      // not reference options: K echoes through the run's motion and weights, and their fit
+      std::vector<std::string> tok;
+      a.multi(tok);
+      if (tok.empty()) die("--echoStacks needs the echo's abscissa (echo time, b-value) and then a file or `none` per -i stack");
+      p.echo_x.push_back(tok[0]);
+      p.echo_names.emplace_back(tok.begin() + 1, tok.end());
+    }
+    else if (a.is("--echoOutput")) { p.have_echo_dep_opt = true; p.echo_out = a.one(); }
+    else if (a.is("--echoIterations")) { p.have_echo_dep_opt = true; p.echo_iterations = a.one_int(); }
+    else if (a.is("--echoGuide")) { p.have_echo_dep_opt = true; p.echo_guide = true; }
+    else if (a.is("--fitRate")) { p.have_echo_dep_opt = true; p.fit_rate = a.one(); }
+    else if (a.is("--fitT")) { p.have_echo_dep_opt = true; p.fit_t = a.one(); }
+    else if (a.is("--fitAmplitude")) { p.have_echo_dep_opt = true; p.fit_amplitude = a.one(); }
+    else if (a.is("--fitResidual")) { p.have_echo_dep_opt = true; p.fit_residual = a.one(); }
+    else if (a.is("--fitCount")) { p.have_echo_dep_opt = true; p.fit_count = a.one(); }
+    else if (a.is("--fitIterations")) { p.have_echo_dep_opt = true; p.fit_iterations = a.one_int(); }
+    else if (a.is("--fitFloor")) { p.have_echo_dep_opt = true; p.fit_floor = a.one_double(); }
+    else if (a.is("--fitMaxT")) { p.have_echo_dep_opt = true; p.fit_max_t = a.one_double(); if (!(p.fit_max_t > 0) || !std::isfinite(p.fit_max_t)) die("--fitMaxT must be positive"); }
     else if (a.is("--labelStacks")) { p.have_label_opt = true; a.multi(p.label_names); }
     else if (a.is("--labelOutput")) p.label_out = a.one();
     else if (a.is("--labelConfidence")) p.label_conf = a.one();
@@ -559,6 +699,12 @@ Options parse_options(int argc, char **argv, std::vector<ExtraSet> &extras) {
   if (p.channel_guide && (!p.have_channel_opt || p.channel_iterations <= 0))
     die("--channelGuide guides the volume update of --channelIterations n (n > 0) on the channel of --channelStacks f_1 .. f_N --channelOutput <file>: "
         "give them");
+  if (p.echo_x.empty() && p.have_echo_dep_opt)
+    die("--echoOutput / --echoIterations / --echoGuide / --fit* belong to the echoes of --echoStacks <x> f_1 .. f_N, given once per echo: give them");
+  if (p.echo_iterations < 0) die("--echoIterations must not be negative (0 = the robust PSF-weighted average of every echo alone)");
+  if (p.fit_iterations < 0 || p.fit_iterations > 50) die("--fitIterations must be 0 .. 50 (0 = the weighted log-linear fit alone; negative or larger counts are refused)");
+  if (!(p.fit_floor >= 0) || !std::isfinite(p.fit_floor)) die("--fitFloor must be finite and not negative");
+  if (p.echo_guide && p.echo_iterations <= 0) die("--echoGuide guides the volume update of --echoIterations n (n > 0): give it");
   if (p.structural && !p.sfolder.empty())
     die("--structural compares every slice with the other slices of its stack; with --sfolder the slices come from files of their own and "
         "belong to no stack: drop one or the other");
@@ -1201,8 +1347,13 @@ int main(int argc, char **argv) {
     clk.mark("slice report, simulated stacks");
   }
   if (!P.extras.empty()) {
-    reconstruct_extras(opt, P, R, hosts, clk.on);
+    std::vector<float> echoes;
+    reconstruct_extras(opt, P, R, hosts, clk.on, echoes);
     clk.mark("channels, labels");
+    if (!opt.fit_rate.empty() || !opt.fit_t.empty() || !opt.fit_amplitude.empty() || !opt.fit_residual.empty() || !opt.fit_count.empty()) {
+      fit_echoes(opt, P, R, echoes, clk.on);
+      clk.mark("fit of the echoes");
+    }
   }
   if (opt.debug) save_debug_transformations(opt, P, R);
   for (svrh_recon *h : hosts) svrh_destroy(h);

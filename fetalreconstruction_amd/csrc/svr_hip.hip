@@ -1263,6 +1263,7 @@ struct svr_ctx {
   float csr_delta_g = 0.0f;
   bool csr_guide_only = false;
   bool have_em = false;                  // d_weights hold EM posteriors (svr_initialize_em_values or a later E-step; a test's svr_debug_set)
+  int fit_chunk = 1 << 20;               // voxels per upload / launch / download of svr_monoexp_fit (svr_fit.inc; option "fit_chunk")
   int last_quality_chunks = -1;          // chunks per slice of the last svr_slice_quality (read-only option "quality_chunks"; -1 = not launched yet)
   int reg_tx = 0, reg_ty = 0, reg_n = 0;
   uint32_t reg_vx = 0, reg_vy = 0, reg_vz = 0;
@@ -2260,6 +2261,7 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
   }
   if (!strcmp(name, "reg_batch")) { ctx->reg_batch = value ? 1 : 0; return SVR_OK; }
   if (!strcmp(name, "bias_mode")) { if (value < 0 || value > 2) return fail(ctx, SVR_E_ARG, "bias_mode: 0, 1 or 2"); ctx->bias_mode = value; return SVR_OK; }
+  if (!strcmp(name, "fit_chunk")) { if (value < 1 || value > (1 << 24)) return fail(ctx, SVR_E_ARG, "fit_chunk: 1 .. 16777216 voxels"); ctx->fit_chunk = value; return SVR_OK; }
   if (!strcmp(name, "pvr_reg_levels")) { ctx->pvr_reg_levels = std::min(3, std::max(1, value)); return SVR_OK; }
   if (!strcmp(name, "pvr_reg_steps")) { ctx->pvr_reg_steps = std::max(1, value); return SVR_OK; }
   if (!strcmp(name, "pvr_reg_iterations")) { ctx->pvr_reg_iterations = std::max(1, value); return SVR_OK; }
@@ -2286,7 +2288,7 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value) {
       {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells},
       {"bias_field_bx", ctx->last_bias_bx}, {"bias_tail_lds", ctx->last_tail_lds}, {"bias_tail_rows", ctx->last_tail_rows},
       {"bias_tail_bxy", ctx->last_tail_bxy}, {"bias_tail_bxz", ctx->last_tail_bxz}, {"reg_zc", ctx->last_reg_zc}, {"reg_chunks", ctx->last_reg_chunks},
-      {"psf_list_valid", ctx->psf_list_valid}, {"cells_valid", cells_valid}, {"quality_chunks", ctx->last_quality_chunks}};
+      {"psf_list_valid", ctx->psf_list_valid}, {"cells_valid", cells_valid}, {"quality_chunks", ctx->last_quality_chunks}, {"fit_chunk", ctx->fit_chunk}};
   for (const auto &e : tab)
     if (!strcmp(name, e.n)) { *value = e.v; return SVR_OK; }
   return fail(ctx, SVR_E_ARG, std::string("unknown option ") + name);
@@ -3802,4 +3804,5 @@ int svr_counters(svr_ctx *ctx, uint64_t out5[8]) {
 #include "svr_ssim.inc"
 #include "svr_seed.inc"
 #include "svr_channel.inc"
+#include "svr_fit.inc"
 #include "svr_em.inc"

@@ -52,7 +52,7 @@ EXPORTS = [
     "svr_get_scale_vector", "svr_adopt_scale_vector", "svr_get_slice_inside", "svr_mstep_estep", "svr_mstep_sums_fetch", "svr_mstep_partial", "svr_mstep_estep_ranks",
     "svr_channel_scatter", "svr_channel_finish", "svr_channel_vote", "svr_channel_vote_fetch",
     "svr_channel_sr_begin", "svr_channel_sr_seed", "svr_channel_sr_backproject", "svr_channel_sr_update", "svr_channel_sr_end",
-    "svr_channel_sr_guide",
+    "svr_channel_sr_guide", "svr_monoexp_fit",
 ]
 
 
@@ -605,6 +605,25 @@ class Reconstruction:
         out = np.empty(int(np.prod(self.vsize)), np.float32) if want_volume else None
         self._ck(self._lib.svr_channel_sr_end(self._h, None if out is None else _p(out)))
         return out
+
+    # ---- S(x) = A exp(-R x) over K volumes, voxel by voxel (csrc/svr_fit.inc) ------------------------------------------------------
+    def monoexp_fit(self, vols, x, iterations=0, floor=0.0):
+        """svr_monoexp_fit: vols float32 [K][...], x the K abscissae (echo times, b-values) -> (rate, amplitude, rmse, count), float32 arrays
+        of vols[0]'s shape.  iterations: Gauss-Newton steps after the weighted log-linear fit; floor: samples at or below it do not count.
+        Needs no geometry.  None for vols or x reaches the library as NULL (refused there)."""
+        v = None if vols is None else _f32(vols)
+        xs = None if x is None else np.ascontiguousarray(x, np.float64).reshape(-1)
+        if v is not None and v.ndim < 1:
+            raise SvrError("monoexp_fit: vols [K][...] expected")
+        k = 0 if v is None else v.shape[0]
+        if v is not None and xs is not None and xs.size != k:
+            raise SvrError(f"monoexp_fit: {xs.size} abscissae for {k} volumes")
+        shape = () if v is None else v.shape[1:]
+        n = int(np.prod(shape)) if v is not None else 0
+        out = [np.zeros(shape, np.float32) for _ in range(4)]
+        self._ck(self._lib.svr_monoexp_fit(self._h, C.c_int(k), None if xs is None else _p(xs), None if v is None else _p(v), C.c_size_t(n),
+                                           C.c_int(int(iterations)), C.c_float(floor), *[_p(o) for o in out]))
+        return tuple(out)
 
     # ---- GPU slice-to-volume registration (RC.cuh:326-338) ------------------------------------
     def initRegStorageVolumes(self, W, H, ns, dim=(1.0, 1.0, 1.0)):

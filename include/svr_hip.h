@@ -442,6 +442,26 @@ int svr_channel_sr_end(svr_ctx *ctx, float *out_or_null);
 #define SVR_CHANNEL_GUIDE_ONLY 1
 int svr_channel_sr_guide(svr_ctx *ctx, const float *guide_or_null, float delta_g, int flags);
 
+/* The mono-exponential fit S(x) = A exp(-R x) over K co-registered volumes, voxel by voxel (csrc/svr_fit.inc; the command line's --echoStacks /
+ * --fit*; no reference equivalent).  x = echo time gives R2* / R2 (T = 1 / R), x = b-value gives the ADC.  vols: K volumes of n values each, host
+ * memory, [K][n]; x: their K abscissae, finite and distinct.  Per voxel, over k = 0 .. K-1 in that order, in double on the device:
+ *     sample k is usable when C_k is finite and C_k > floor;   count = the number of usable samples
+ *     fewer than 2 usable samples: rate = amplitude = rmse = 0
+ *     y = ln C_k, w = C_k^2;   Sw, Swx, Swxx, Swy, Swxy;   D = Sw Swxx - Swx^2;   D not positive: rate = amplitude = rmse = 0
+ *     R = -(Sw Swxy - Swx Swy) / D,   A = exp((Swxx Swy - Swx Swxy) / D);   not finite: rate = amplitude = rmse = 0
+ *     iterations > 0: that many plain Gauss-Newton steps from (A, R) on the signal-domain residuals C_k - a exp(-r x_k) of the usable samples
+ *       (J1 = e_k = exp(-r x_k), J2 = -a x_k e_k; the 2 x 2 normal equations in closed form; stopped when their determinant is not above
+ *       1e-30 a11 a22; back to (A, R) when a parameter stops being finite), kept only if their sum of squares is not above (A, R)'s
+ *     rmse = sqrt(sum (C_k - A exp(-R x_k))^2 / count) over the usable samples, for the pair returned
+ * Every output is rounded to float once; where rate, amplitude or rmse is not finite as a float the three are 0.  count is always the number of
+ * usable samples.  rate / amplitude / rmse / count: [n] floats of host memory each, or NULL = not wanted.  n = 0 writes nothing.
+ * Needs a created context and nothing else: no geometry, legal on a patch-based context.  [0, n) is cut into chunks of at most "fit_chunk"
+ * voxels (svr_set_option, 1 .. 2^24, default 2^20); the device buffers ((K + outputs) x chunk floats) live for the call.  The chunking does not
+ * change a bit of the result.  Refused with SVR_E_ARG and a message, never a fault, and the context stays usable: NULL x or vols, K outside
+ * 2 .. 16, an x that is not finite or appears twice, iterations outside 0 .. 50, a floor that is negative or not finite. */
+int svr_monoexp_fit(svr_ctx *ctx, int K, const double *x, const float *vols, size_t n, int iterations, float floor, float *rate, float *amplitude,
+                    float *rmse, float *count);
+
 /* ---- GPU slice-to-volume registration (the reference's --useGPUReg path) -------
  * One entry point per public method of `class Reconstruction` used by irtkReconstruction::
  * PrepareRegistrationSlices / SliceToVolumeRegistrationGPU (irtkReconstructionGPU.cc:2104-2290).
