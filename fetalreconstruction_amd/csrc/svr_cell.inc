@@ -1738,63 +1738,7 @@ int cell_prepare_state(svr_ctx *ctx, CellState *&slot, int cell_w, int cell_h, b
   return SVR_OK;
 }
 
-// ---- the order of the coefficient table (ensure_coeff) -------------------------------------------------------------------
-__global__ void k_coeff_order_sorted(const CellRec *recs, uint32_t n, uint32_t *order, unsigned char *mark) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t idx = recs[i].idx;
-  order[i] = idx;
-  mark[idx] = 1;
-}
-__global__ void k_coeff_order_rest(const uint32_t *active, uint32_t n, const unsigned char *mark, uint32_t *order, uint32_t first, uint32_t *counter) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool rest = i < n && !mark[active[i]];
-  const unsigned long long b = __ballot(rest);
-  const int lane = threadIdx.x & 63;
-  uint32_t base = 0;
-  if (lane == 0 && b) base = atomicAdd(counter, (uint32_t)__popcll(b));
-  base = __shfl(base, 0, 64);
-  if (rest) order[first + base + __popcll(b & ((1ull << lane) - 1ull))] = active[i];
-}
-// *list = ctx->d_coeff_order[n_active]: the sorted pixels of the scatter's cell lists, then the active pixels the lists
-// dropped; left as it is when the geometry has no usable cell lists
-int coeff_order(svr_ctx *ctx, uint32_t n_active, const uint32_t **list) {
-  int r = cell_prepare(ctx);
-  if (r) return r;
-  if (!ctx->cell || !ctx->cell->usable || !ctx->cell->n_sorted) return SVR_OK;
-  CellState &cs = *ctx->cell;
-  HIPCHK(ctx->d_coeff_order.reserve(n_active));
-  DevBuf<unsigned char> mark;
-  HIPCHK(mark.reserve(ctx->np));
-  HIPCHK(hipMemsetAsync(mark, 0, ctx->np, ctx->stream));
-  hipLaunchKernelGGL(k_coeff_order_sorted, dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, cs.d_recs, cs.n_sorted, ctx->d_coeff_order, mark);
-  KCHK("k_coeff_order_sorted");
-  if (cs.n_sorted < n_active) {
-    HIPCHK(hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_coeff_order_rest, dim3(nblk(n_active)), dim3(256), 0, ctx->stream, ctx->d_active, n_active, mark, ctx->d_coeff_order, cs.n_sorted, ctx->d_counter);
-    KCHK("k_coeff_order_rest");
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  *list = ctx->d_coeff_order;
-  return SVR_OK;
-}
-
-// the table ids of a cell state's sorted records, for the COEFF launches (after ensure_coeff; again when either the lists or the table are new)
-__global__ void k_cell_pids(const CellRec *recs, uint32_t n, const uint32_t *coeff_id, uint32_t *pid) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) pid[i] = coeff_id[recs[i].idx];
-}
-int cell_pids(svr_ctx *ctx, CellState &cs, const PsfArgs &a, CellArgs &ca) {
-  if (!a.coeff) return SVR_OK;
-  if (!cs.pid_valid) {
-    HIPCHK(cs.d_pid.reserve(cs.n_sorted));
-    hipLaunchKernelGGL(k_cell_pids, dim3(nblk(cs.n_sorted)), dim3(256), 0, ctx->stream, cs.d_recs, cs.n_sorted, a.coeff_id, cs.d_pid);
-    KCHK("k_cell_pids");
-    cs.pid_valid = true;
-  }
-  ca.pid = cs.d_pid;
-  return SVR_OK;
-}
+int cell_pids(svr_ctx *ctx, CellState &cs, const PsfArgs &a, CellArgs &ca);   // the records' table ids for a COEFF launch (svr_table.inc)
 
 // the scatter of one pass: factors, items, combine.  out0 | out1 = addon | cmap (or recon | volw in the Gaussian pass).
 // store: the pass evaluates every tap of every PSF pixel and writes the coefficient table (support 16; a.coeff = the table to fill, a.coeff_id filled)

@@ -156,8 +156,9 @@ int channel_scatter_launch(svr_ctx *ctx, const float *d_channel, const unsigned 
   a.ch_flags = flags;
   a.ch_match = match;
   if (sim) { a.simslices = sim; a.simweights = simw; }
-  if (table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
-  return launch_cell_scatter(ctx, a, mode, ctx->addon(), ctx->cmap());
+  TableUse use;
+  const int r = table_begin(ctx, table_plan_for(ctx, PASS_CHANNEL_SCATTER, pass_path(ctx, PASS_CHANNEL_SCATTER), true), a, &use);
+  return r ? r : launch_cell_scatter(ctx, a, mode, ctx->addon(), ctx->cmap());
 }
 
 int channel_scatter_run(svr_ctx *ctx, const float *channel, const unsigned char *unit_on, int flags, float match) {
@@ -195,7 +196,6 @@ __global__ __launch_bounds__(256) void k_channel_uncover(float *__restrict__ vol
 // step 1: the channel volume through svr_simulate_slices's gather over the (cell, plane) items into d_csr_sim / d_csr_simw.  Nothing of the primary's
 // forward projection is written; d_volm and the cell lists' staging are scratch that every pass refills
 int channel_sr_forward(svr_ctx *ctx) {
-  const PassPath p = pass_path(ctx, PASS_FORWARD);
   const float *vol = ctx->d_csr_vol[ctx->csr_cur];
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
@@ -204,11 +204,12 @@ int channel_sr_forward(svr_ctx *ctx) {
   a.simslices = ctx->d_csr_sim; a.simweights = ctx->d_csr_simw;
   a.siminside = ctx->d_csr_inside; a.slice_inside = ctx->d_csr_slice_inside;
   // the table where svr_simulate_slices would stream it on the cells; a gather it would hand to the slice tiles evaluates here (the same bits)
-  if (p.may_stream_table && p.table_on_cells && table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
+  TableUse use;
+  int r = table_begin(ctx, table_plan_for(ctx, PASS_CHANNEL_GATHER, pass_path(ctx, PASS_CHANNEL_GATHER), true), a, &use);
+  if (r) return r;
   HIPCHK(hipMemsetAsync(ctx->d_csr_sim, 0, ctx->np * sizeof(float), ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_csr_simw, 0, ctx->np * sizeof(float), ctx->stream));
-  int r = pack_volm(ctx, a, vol);
-  if (r) return r;
+  if ((r = pack_volm(ctx, a, vol))) return r;
   CellState *gcs = nullptr;
   if ((r = cell_prepare_gather(ctx, gcs))) return r;
   if (!gcs || !gcs->usable)
@@ -232,7 +233,7 @@ int svr_channel_scatter(svr_ctx *ctx, const float *channel, const unsigned char 
   NEED(ctx->have_em, "no EM weights (svr_initialize_em_values first)");
   int r = ready(ctx);
   if (r) return r;
-  if (pass_path(ctx, PASS_BACK).family != FAM_CELLS)
+  if (pass_path(ctx, PASS_CHANNEL_SCATTER).family != FAM_CELLS)
     return fail(ctx, SVR_E_STATE, "svr_channel_scatter: needs the cell scatter (back_mode 5); channels have no fallback onto the atomic scatters");
   if (slice_weights && (r = svr_update_slice_weights(ctx, slice_weights))) return r;
   return channel_scatter_run(ctx, channel, unit_on, flags, match);
@@ -299,7 +300,7 @@ int svr_channel_sr_begin(svr_ctx *ctx, const float *channel, const unsigned char
   NEED(ctx->have_em, "no EM weights (svr_initialize_em_values first)");
   int r = ready(ctx);
   if (r) return r;
-  if (pass_path(ctx, PASS_BACK).family != FAM_CELLS || pass_path(ctx, PASS_FORWARD).family != FAM_CELLS)
+  if (pass_path(ctx, PASS_CHANNEL_SCATTER).family != FAM_CELLS || pass_path(ctx, PASS_CHANNEL_GATHER).family != FAM_CELLS)
     return fail(ctx, SVR_E_STATE, "svr_channel_sr_begin: needs the cell scatter and the cell gather (back_mode 5, fwd_mode 2); channels have no fallback onto the other kernels");
   if (ctx->reg_mode != 1) return fail(ctx, SVR_E_STATE, "svr_channel_sr_begin: needs the fused volume update (reg_mode 1)");
   if (slice_weights && (r = svr_update_slice_weights(ctx, slice_weights))) return r;

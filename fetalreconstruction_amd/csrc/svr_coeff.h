@@ -1,4 +1,4 @@
-// The coefficient table's layout (svr_ctx::d_coeff): the one definition for its writers, its readers and the host allocation.
+// The coefficient table's layout (CoeffTable::d_coeff, svr_hip.hip): the one definition for its writers, its readers and the host allocation.
 //
 // The table holds, for every pixel that has a place in it (its id: d_coeff_id), the evaluated PSF taps of its NS units -- a unit = one
 // plane of the pixel's NS x NS x NS footprint along the axis the slice's cells own, NS rows of NS taps, what eval_row_t returns per row,

@@ -25,6 +25,7 @@
 
 #include "../../include/svr_hip.h"
 #include "svr_devbuf.h"
+#include "svr_plan.h"      // which kernel family runs a PSF pass and what it does with the coefficient table: plain C++ (pass_path, table_plan)
 
 // csrc/svr_sort.hip: radix sort / prefix sum of the vendor's primitives library for the work lists of svr_cell.inc
 int svr_sort_keys_u64(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, size_t n, int end_bit, hipStream_t stream);
@@ -1078,9 +1079,37 @@ __global__ __launch_bounds__(64) void k_probe_pixel(PsfArgs a, uint32_t idx, flo
 // ==========================================================================================
 struct RegState;   // GPU slice-to-volume registration state (svr_reg.inc)
 namespace { struct CellState; struct SlabPlan; struct SliceEm; void slice_em_free(SliceEm *); void slice_em_invalidate(SliceEm *); }  // sorted pixels, runs, items and staging of the scatter without atomics (svr_cell.inc)
-// what the coefficient table holds (svr_ctx::coeff_state): nothing, the PSF pixels of the pass that wrote it (coeff_lazy: a gather or
-// scatter of the SR iterations, pass 2 of a Gaussian reconstruction), or every pixel with s != -1 (k_coeff_build)
-enum CoeffState { COEFF_NONE = 0, COEFF_PSF = 1, COEFF_FULL = 2 };
+namespace {
+// The coefficient table: what irtkReconstruction::CoeffInit keeps as _volcoeffs on the CPU path (RG.cc:2305-2673) --
+// every PSF pixel's evaluated taps, 16 KiB per pixel, written once per slice geometry by k_coeff_build and streamed by
+// the COEFF instantiations of the scatter and the gather instead of being re-evaluated in every SR iteration.  The
+// reference's GPU path recomputes them (a 2015 GPU had 6-12 GB); 288 GB of HBM hold them for every workload of
+// BASELINE.json (P4: 19 GB, S8: 174 GB).  Values are bit-identical to the on-the-fly evaluation by construction.
+// svr_table.inc owns it: nobody else writes a field.
+struct CoeffTable {
+  DevBuf<float4> d_coeff;
+  DevBuf<uint32_t> d_coeff_id;
+  DevBuf<uint32_t> d_coeff_order;   // the active pixels in the order of their places in the table (coeff_order)
+  CoeffState coeff_state = COEFF_NONE;
+  int coeff_mode = 1;          // option "coeff_table": 0 = evaluate on the fly, 1 = stream the table (falls back to 0 if it does not fit).  Round 6: ON by
+                               // default for slice-to-volume runs (written by the first gather of the SR iterations, coeff_lazy: P4 +7 %, S8 +5 % with one
+                               // table per four SR iterations INSIDE the timed region), off for the patch-based path (no gain there: DESIGN 5.1b)
+  bool coeff_user = false;     // svr_set_option("coeff_table") was called: the "pvr" option leaves the mode alone
+  int coeff_lazy = 1;          // option "coeff_lazy" (round 6): 1 = the table is written by the first gather of the SR iterations after a new slice geometry
+                               // (fwd_cell_kernel<.., 3>: the evaluation that pass needs anyway) instead of by k_coeff_build; passes before it evaluate
+  const uint32_t *coeff_list = nullptr;   // (alias) the active pixels in table order (d_coeff_order, or d_active), while coeff_ids_valid
+  bool coeff_ids_valid = false;   // d_coeff_order / d_coeff_id match the current cell lists (dropped with them): a table thrown away without a new
+                                  // geometry (svr_set_option coeff_invalidate) keeps its pixels' places
+  void want(bool on);             // option "coeff_table"
+  void want_by_default(bool on);  // ... what the "pvr" option makes of it, unless the caller chose
+  void set_lazy(bool on);         // option "coeff_lazy"
+  void drop();                    // holds nothing any more
+  void drop_psf_pixels();         // the PSF pixels changed: a table that holds only them holds nothing any more
+  void free_rows();               // the table's memory
+  void free_ids();                // ... and the ids' (a new slice grid)
+  void ids_stale();               // the cell lists that gave the pixels their places are gone
+};
+}  // namespace
 
 struct svr_ctx {
   int device = 0;
@@ -1196,25 +1225,8 @@ struct svr_ctx {
   bool back_mode_user = false;   // svr_set_option("back_mode") was called: no automatic choice between 5 and 4
   bool fwd_mode_user = false;    // likewise "fwd_mode"
   bool sr_no_wait = false;       // inside svr_superresolution: its two halves do not wait for the device
-  // The coefficient table: what irtkReconstruction::CoeffInit keeps as _volcoeffs on the CPU path (RG.cc:2305-2673) --
-  // every PSF pixel's evaluated taps, 16 KiB per pixel, written once per slice geometry by k_coeff_build and streamed by
-  // the COEFF instantiations of the scatter and the gather instead of being re-evaluated in every SR iteration.  The
-  // reference's GPU path recomputes them (a 2015 GPU had 6-12 GB); 288 GB of HBM hold them for every workload of
-  // BASELINE.json (P4: 19 GB, S8: 174 GB).  Values are bit-identical to the on-the-fly evaluation by construction.
-  DevBuf<float4> d_coeff;
-  DevBuf<uint32_t> d_coeff_id;
-  DevBuf<uint32_t> d_coeff_order;   // the active pixels in the order of their places in the table (coeff_order)
-  CoeffState coeff_state = COEFF_NONE;   // (table_holds)
-  int coeff_mode = 1;          // option "coeff_table": 0 = evaluate on the fly, 1 = stream the table (falls back to 0 if it does not fit).  Round 6: ON by
-                               // default for slice-to-volume runs (written by the first gather of the SR iterations, coeff_lazy: P4 +7 %, S8 +5 % with one
-                               // table per four SR iterations INSIDE the timed region), off for the patch-based path (no gain there: DESIGN 5.1b)
+  CoeffTable table;            // the coefficient table (svr_table.inc)
   bool legacy_ok = false;      // option "legacy_kernels": back_mode 0 / 1 / 3 and fwd_mode 0 may be asked for (tests)
-  bool coeff_user = false;     // svr_set_option("coeff_table") was called: the "pvr" option leaves the mode alone
-  int coeff_lazy = 1;          // option "coeff_lazy" (round 6): 1 = the table is written by the first gather of the SR iterations after a new slice geometry
-                               // (fwd_cell_kernel<.., 3>: the evaluation that pass needs anyway) instead of by k_coeff_build; passes before it evaluate
-  const uint32_t *coeff_list = nullptr;   // (alias) the active pixels in table order (d_coeff_order, or d_active), while coeff_ids_valid
-  bool coeff_ids_valid = false;   // d_coeff_order / d_coeff_id match the current cell lists (dropped with them): a table thrown away without a new
-                                  // geometry (svr_set_option coeff_invalidate) keeps its pixels' places
   int wave_groups = 1, wave_cap = 2096;      // back_wave_kernel: wavefronts per tile, box voxels of a wavefront's four planes (14 LDS granules of 1280 B with the static part: 9 wavefronts per CU)
 
   // reductions
@@ -1598,8 +1610,6 @@ PsfArgs make_args(svr_ctx *ctx) {
   return a;
 }
 
-void give_coeff(const svr_ctx *ctx, PsfArgs &a) { a.coeff = ctx->d_coeff; a.coeff_id = ctx->d_coeff_id; }   // the table goes to a pass's arguments
-
 // bias-path buffers: slice-grid {bias, wb, wresidual, buffer} (RC.cu:1510-1539) and volume
 // {bias, volume_weights, maskC} (RC.cu:1203-1214, 1129-1157); created on first use after
 // svr_set_flags(ctx, disable_bias_correction = 0, ...)
@@ -1685,94 +1695,6 @@ int ensure_psf_list(svr_ctx *ctx) {
 // workgroup kernel (8 wavefronts, the largest box the CU can hold); what fits neither -- strongly oblique tiles of very fine
 // volumes -- takes LDS atomics (SVR: back_tiled_kernel) or device atomics per tap (PVR: pvr_tiles_kernel).
 // level: 4 = start with the wave-owned kernel, 3 = with the workgroup kernel, 1 = the last resort for every tile.
-int coeff_order(svr_ctx *ctx, uint32_t n_active, const uint32_t **list);
-__global__ void k_coeff_ids(const uint32_t *list, uint32_t n, uint32_t *coeff_id) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) coeff_id[list[i]] = i;
-}
-// Can the table be left to the first gather of the SR iterations (coeff_lazy)?  Support 16 on the cell gather.  Pending: wanted, not there,
-// and left to the evaluating pass that writes it -- every other pass evaluates meanwhile.
-bool coeff_lazy_ok(const svr_ctx *ctx) { return ctx->coeff_lazy && !ctx->pvr && ctx->fwd_mode == 2; }
-bool coeff_lazy_pending(const svr_ctx *ctx) { return ctx->coeff_mode && ctx->coeff_state == COEFF_NONE && coeff_lazy_ok(ctx); }
-// May a pass stream the table?  `need` = the pixels it reads: COEFF_PSF for the passes of the SR iterations (either written state holds
-// them), COEFF_FULL for the Gaussian pass (every pixel with s != -1).
-bool table_holds(const svr_ctx *ctx, CoeffState need) { return ctx->coeff_mode && ctx->coeff_state >= need; }
-// The table's memory and the pixels' places in it (*list = the active pixels in table order).  Returns with ctx->d_coeff set, or with the mode
-// switched off when the table does not fit the free memory.
-int coeff_prepare(svr_ctx *ctx, const uint32_t **list) {
-  // every pixel with s != -1: the Gaussian pass walks them all, the PSF pixels of the SR iterations are a subset
-  const size_t npx = ctx->n_active;
-  const size_t bytes = npx * (ctx->pvr ? CoeffLayout<PVR_N>::PIXEL_BYTES : CoeffLayout<PSF_SUPPORT>::PIXEL_BYTES);   // (whole float4s)
-  if (bytes / sizeof(float4) > ctx->d_coeff.capacity()) {      // more pixels than the allocation holds (one layout per allocation: the "pvr" option raises CH_TABLE_OFF)
-    ctx->d_coeff.reset();
-    size_t fr = 0, tot = 0;
-    const char *cap_gb = getenv("SVR_COEFF_MAX_GB");     // optional ceiling on the table (GiB): a deployment knob, and how the tests reach the fallback
-    const bool over = cap_gb && (double)bytes > atof(cap_gb) * 1073741824.0;
-    // the bias buffers are allocated before the first pass (svr_set_flags / ready); any still missing count in the headroom
-    const size_t bias_later = ctx->disable_bias ? 0 : (ctx->d_bias ? 0 : 4 * ctx->np * sizeof(float)) + (ctx->d_bias_vol ? 0 : 4 * ctx->nv * sizeof(float));
-    if (over || hipMemGetInfo(&fr, &tot) != hipSuccess || bytes + bias_later + (size_t(2) << 30) > fr || ctx->d_coeff.reserve(bytes / sizeof(float4)) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->coeff_mode = 0;                                 // does not fit: evaluate on the fly (svr_get_option tells)
-      return SVR_OK;
-    }
-  }
-  HIPCHK(ctx->d_coeff_id.reserve(ctx->np));   // (freed by svr_init_storage_volumes, whose changes drop the ids)
-  if (ctx->coeff_ids_valid && ctx->coeff_list) { *list = ctx->coeff_list; return SVR_OK; }
-  *list = ctx->d_active;
-  // The pixels get their places in the table in the order of the scatter's cell lists (cell, slice, band, position): what a
-  // (cell, plane) item of the scatter or a slice tile of the gather reads next then lies within a few megabytes instead of one
-  // KiB per slice all over the table (a TLB miss per unit); pixels the cell lists dropped (footprint beyond the volume) follow.
-  if (!getenv("SVR_COEFF_UNSORTED")) {
-    const int r = coeff_order(ctx, (uint32_t)npx, list);
-    if (r) return r;
-  }
-  ctx->coeff_list = *list;
-  return SVR_OK;
-}
-// (Re)build the coefficient table if the option is on and there is none.
-// Returns with ctx->coeff_state COEFF_FULL, or with the mode switched off when the table does not fit the free memory.
-int ensure_coeff(svr_ctx *ctx) {
-  if (!ctx->coeff_mode || ctx->coeff_state != COEFF_NONE) return SVR_OK;
-  const size_t npx = ctx->n_active;
-  if (!npx) return SVR_OK;
-  PsfArgs a = make_args(ctx);
-  a.n = (uint32_t)npx;
-  { const int r = coeff_prepare(ctx, &a.list); if (r) return r; }
-  if (!ctx->coeff_mode) return SVR_OK;
-  ScopedTimer tb(ctx, SVR_T_COEFF_BUILD);
-  {
-    const int rr = pixel_list_in_pieces(a, [&](const PsfArgs &ap, uint32_t off) {
-      if (ctx->pvr) hipLaunchKernelGGL((k_coeff_build<PVR_N, true>), dim3(nblk(ap.n, 4)), dim3(256), 0, ctx->stream, ap, ctx->d_coeff, ctx->d_coeff_id, off);
-      else hipLaunchKernelGGL((k_coeff_build<PSF_SUPPORT, false>), dim3(nblk(ap.n, 4)), dim3(256), 0, ctx->stream, ap, ctx->d_coeff, ctx->d_coeff_id, off);
-      KCHK("k_coeff_build");
-      return (int)SVR_OK;
-    });
-    if (rr) return rr;
-  }
-  tb.stop();
-  ctx->coeff_state = COEFF_FULL;
-  if (!ctx->coeff_ids_valid) invalidate(ctx, CH_TABLE_IDS);   // (k_coeff_build gave the pixels their places: svr_cell.inc cell_pids)
-  ctx->coeff_ids_valid = true;
-  return SVR_OK;
-}
-// The evaluating cell pass that is about to run writes the table (coeff_lazy): memory, the pixels' places and ids.  *store = the pass should store.
-int coeff_begin_store(svr_ctx *ctx, bool *store) {
-  *store = false;
-  if (!coeff_lazy_pending(ctx) || !ctx->n_active) return SVR_OK;
-  const uint32_t *order = nullptr;
-  int r = coeff_prepare(ctx, &order);
-  if (r) return r;
-  if (!ctx->coeff_mode) return SVR_OK;                     // (the table does not fit)
-  if (!ctx->coeff_ids_valid) {
-    hipLaunchKernelGGL(k_coeff_ids, dim3(nblk(ctx->n_active)), dim3(256), 0, ctx->stream, order, (uint32_t)ctx->n_active, ctx->d_coeff_id);
-    KCHK("k_coeff_ids");
-    invalidate(ctx, CH_TABLE_IDS);
-    ctx->coeff_ids_valid = true;
-  }
-  *store = true;
-  return SVR_OK;
-}
-
 int launch_slot(svr_ctx *ctx, bool pvr, const PsfArgs &a, const TileArgs &ta_, uint32_t *fb, uint32_t *cnt) {
   const size_t lds = (size_t)ta_.cap * 2 * sizeof(float);
   return in_pieces(ta_.ntiles, 8 * 64, [&](uint32_t off, uint32_t cntp) {
@@ -1868,6 +1790,7 @@ int launch_scatter(svr_ctx *ctx, int level, const PsfArgs &a_, const uint32_t *t
 }
 
 #include "svr_cell.inc"
+#include "svr_table.inc"   // the coefficient table's owner: its memory, order and ids, and a pass's begin / end on a table_plan
 #include "svr_slab.inc"
 
 // What each Change leaves stale.  A table written by a pass of the SR iterations holds that pass's PSF pixels only: every change that can
@@ -1884,11 +1807,11 @@ void invalidate(svr_ctx *ctx, unsigned ch) {
   if (ch & CH_SLICE_GEOMETRY) ctx->sc_dirty = true;
   if (ch & (CH_VOLUME_GRID | CH_SLICE_PIXELS)) channel_sr_drop(ctx);   // (a channel's SR iterations in flight were over the old grids: nothing of them is cached)
   if (ch & (CH_SLICE_PIXELS | CH_PSF_SUMS | CH_TILE_SHAPE)) ctx->psf_list_valid = false;
-  if (ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_TABLE | CH_TABLE_OFF)) ctx->coeff_state = COEFF_NONE;
-  if ((ch & CH_PSF_SUMS) && ctx->coeff_state == COEFF_PSF) ctx->coeff_state = COEFF_NONE;
-  if (ch & CH_TABLE_OFF) ctx->d_coeff.reset();
+  if (ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_TABLE | CH_TABLE_OFF)) ctx->table.drop();
+  if (ch & CH_PSF_SUMS) ctx->table.drop_psf_pixels();
+  if (ch & CH_TABLE_OFF) ctx->table.free_rows();
   const bool cells = ch & (CH_TAPS | CH_SLICE_PIXELS | CH_VOLUME_GRID | CH_CELL_SHAPE | CH_TABLE_OFF);
-  if (cells) ctx->cellc_valid = ctx->coeff_ids_valid = false;   // (the pixels' places in the table follow the scatter's lists)
+  if (cells) { ctx->cellc_valid = false; ctx->table.ids_stale(); }   // (the pixels' places in the table follow the scatter's lists)
   for (CellState *cs : {ctx->cell, ctx->cell_g}) {
     if (!cs) continue;
     if (cells) cs->valid = false;
@@ -1937,66 +1860,13 @@ int set_scatter_tile(svr_ctx *ctx, int w, int h) {
   return SVR_OK;
 }
 
-// Which kernel family runs a PSF pass: the one place that reads pvr, pvr_mode, back_mode, fwd_mode, gauss_mode and bias_mode for it.  Device-free:
-// the options and the geometry in, a plain value out.  What only the built cell lists can tell (CellState::usable) is cells_or_fallback's.
-enum Family {
-  FAM_CELLS,    // svr_cell.inc: (cell, plane) items, no atomics -- the default
-  FAM_TILES,    // svr_tile.inc: slice tiles -- the audible fallback, and the table's gather on coarse slices
-  FAM_PIXELS,   // psf_kernel / pvr_kernel: a wavefront per pixel, kept for the parity tests
-};
-enum Pass { PASS_GAUSS1, PASS_GAUSS2, PASS_FORWARD, PASS_BACK, PASS_BIAS };   // (the Gaussian reconstruction: pass 1 gathers, pass 2 scatters)
-struct PassPath {
-  Family family;           // what the options ask for
-  int scatter_level;       // launch_scatter's level for a scatter on FAM_TILES: 4 = wave-owned planes first, 3 = the workgroup kernel, 1 = LDS atomics
-  bool may_stream_table;   // the family's kernels have a COEFF instantiation: the pass streams the table when it holds the pass's pixels
-  bool table_on_cells;     // a gather on FAM_CELLS stays there when it streams the table (else it takes FAM_TILES, silently; a pass that writes
-                           // the table is the cell gather)
-};
-PassPath pass_path(const svr_ctx *ctx, Pass pass) {
-  const bool pvr = ctx->pvr != 0;
-  const bool pvr_units = ctx->pvr_mode == 1;             // patch-based runs: the unit-based kernels of either family, else pvr_kernel
-  PassPath p = {FAM_PIXELS, 0, false, false};
-  switch (pass) {
-    case PASS_GAUSS1:      // pass 1 follows the gather: over the (cell, plane) items when that is the gather's mode (fwd_mode 2; round 4), per slice
-    case PASS_GAUSS2:      // tile otherwise; pass 2 follows the scatter.  The same bits
-      if (ctx->gauss_mode != 1 || (pvr && !pvr_units)) break;
-      p.may_stream_table = true;
-      if (pass == PASS_GAUSS1) p.family = ctx->fwd_mode == 2 ? FAM_CELLS : FAM_TILES;
-      else p.family = ctx->back_mode == 5 ? FAM_CELLS : FAM_TILES;
-      p.scatter_level = pvr ? 4 : std::min(4, std::max(1, ctx->back_mode));
-      break;
-    case PASS_FORWARD:
-      if (pvr ? !pvr_units : ctx->fwd_mode < 1) break;
-      p.may_stream_table = true;
-      p.family = ctx->fwd_mode == 2 ? FAM_CELLS : FAM_TILES;
-      // fwd_mode 2 (the default for SVR on the fly): the gather over the (cell, plane) items of the scatter without atomics
-      // (with the coefficient table: the cell gather for support 12 only -- PVR8spx 24.5 -> 20.7 ms; for support 16 its ring and its 16
-      // box values do not fit the registers and the unit gather streams the table faster: P4 2.76 against 3.04 ms)
-      // ... and there only on large cells, i.e. fine volumes: PVR4 (9 x 6) 8.1 ms on tiles against 8.5 ms on cells)
-      // Round 6: support 16 takes the cell gather too -- the table's rows land in the LDS by LDS-DMA instead of in a ring of registers (fwd_cell_kernel,
-      // COEFF == 2): P4 2.39 against 2.84 ms; option fwd_mode 1 keeps the tile kernel reachable
-      // ... where the slices' pixels are not much coarser than the voxels (the density of tile_shape_rule): S8 (d 0.56, a 174 GB table) 28.1 ms on the
-      // cells whatever their size (6 x 4 .. 12 x 6) against 26.9 ms on 6 x 5 slice tiles
-      if (pvr) {
-        int sw, sh, gw, gh;
-        cell_sizes(ctx, sw, sh, gw, gh);
-        p.table_on_cells = gw * gh >= 96 || ctx->fwd_mode_user;
-      } else {
-        p.table_on_cells = ctx->fwd_mode_user || pixel_density(ctx) >= 0.65;
-      }
-      break;
-    case PASS_BACK:
-      if (pvr ? !pvr_units : ctx->back_mode < 1) break;
-      p.family = ctx->back_mode == 5 ? FAM_CELLS : FAM_TILES;
-      p.scatter_level = pvr ? 4 : std::min(4, ctx->back_mode);
-      p.may_stream_table = pvr || ctx->back_mode >= 4;     // (back_tiled_kernel and back_slot_kernel evaluate)
-      break;
-    case PASS_BIAS:        // the NormaliseBias scatter: the SR scatter's cell kernels, or round 1's psf_kernel<MODE_BIAS>
-      if (ctx->bias_mode >= 1 && !pvr && ctx->back_mode == 5) { p.family = FAM_CELLS; p.may_stream_table = true; }
-      break;
-  }
-  return p;
+// pass_path's inputs (svr_plan.h) from the context
+PassOptions pass_options(const svr_ctx *ctx) {
+  int sw, sh, gw, gh;
+  cell_sizes(ctx, sw, sh, gw, gh);
+  return {ctx->pvr, ctx->pvr_mode, ctx->back_mode, ctx->fwd_mode, ctx->gauss_mode, ctx->bias_mode, ctx->fwd_mode_user, pixel_density(ctx), gw * gh};
 }
+PassPath pass_path(const svr_ctx *ctx, Pass pass) { return pass_path(pass_options(ctx), pass); }
 // The cell lists for a pass on FAM_CELLS (gather: the gather's own when it works on another cell size) -> cs; nullptr where they cannot
 // hold the geometry (CellState::usable), with the fallback counted and, the first time, said.
 int cells_or_fallback(svr_ctx *ctx, bool gather, int kind, const char *what, CellState *&cs) {
@@ -2224,12 +2094,11 @@ int svr_set_option(svr_ctx *ctx, const char *name, int value) {
     if (value) return fail(ctx, SVR_E_ARG, "fwd_autotune: the timed trial launches were removed; the tile shapes follow from the geometry (0 is accepted and changes nothing)");
     return SVR_OK;
   }
-  if (!strcmp(name, "pvr")) { ctx->pvr = value ? 1 : 0; if (!ctx->coeff_user) ctx->coeff_mode = value ? 0 : 1; invalidate(ctx, CH_SLICE_GEOMETRY | CH_TILE_SHAPE | CH_TABLE_OFF); return SVR_OK; }
-  if (!strcmp(name, "coeff_lazy")) { ctx->coeff_lazy = value ? 1 : 0; return SVR_OK; }
+  if (!strcmp(name, "pvr")) { ctx->pvr = value ? 1 : 0; ctx->table.want_by_default(!value); invalidate(ctx, CH_SLICE_GEOMETRY | CH_TILE_SHAPE | CH_TABLE_OFF); return SVR_OK; }
+  if (!strcmp(name, "coeff_lazy")) { ctx->table.set_lazy(value != 0); return SVR_OK; }
   if (!strcmp(name, "coeff_invalidate")) { invalidate(ctx, CH_TABLE); return SVR_OK; }   // (what a new slice geometry does to the table: bench.py's outer iterations)
   if (!strcmp(name, "coeff_table")) {
-    ctx->coeff_mode = value ? 1 : 0;
-    ctx->coeff_user = true;
+    ctx->table.want(value != 0);
     if (!value) invalidate(ctx, CH_TABLE_OFF);
     return SVR_OK;
   }
@@ -2282,7 +2151,7 @@ int svr_get_option(svr_ctx *ctx, const char *name, int *value) {
   const bool cells_valid = ctx->cell && ctx->cell->valid && ((cgw == csw && cgh == csh) || !ctx->cell_g || ctx->cell_g->valid);   // (+ the gather's own)
   const struct { const char *n; int v; } tab[] = {
       {"back_mode", ctx->back_mode}, {"reg_mode", ctx->reg_mode}, {"fwd_mode", ctx->fwd_mode}, {"gauss_mode", ctx->gauss_mode}, {"pvr_mode", ctx->pvr_mode},
-      {"pvr", ctx->pvr}, {"coeff_table", ctx->coeff_mode}, {"coeff_lazy", ctx->coeff_lazy}, {"coeff_valid", ctx->coeff_state != COEFF_NONE}, {"coeff_state", ctx->coeff_state}, {"tile_w", ctx->tile_w}, {"tile_h", ctx->tile_h},
+      {"pvr", ctx->pvr}, {"coeff_table", ctx->table.coeff_mode}, {"coeff_lazy", ctx->table.coeff_lazy}, {"coeff_valid", ctx->table.coeff_state != COEFF_NONE}, {"coeff_state", ctx->table.coeff_state}, {"tile_w", ctx->tile_w}, {"tile_h", ctx->tile_h},
       {"fwd_tile_w", ctx->fwd_tw}, {"fwd_tile_h", ctx->fwd_th}, {"wave_cap", ctx->wave_cap}, {"tile_cap", ctx->tile_cap}, {"cell_w", csw}, {"cell_h", csh}, {"cell_gw", cgw}, {"cell_gh", cgh}, {"cell_split", ctx->cell_split}, {"cell_order", ctx->cell_order}, {"cell_balance", ctx->cell_balance}, {"cell_combine", ctx->cell_combine}, {"fwd_autotune", 0}, {"cell_qx", ctx->cell_qx}, {"fwd_unit_cap", ctx->fwd_unit_cap}, {"reg_batch", ctx->reg_batch}, {"reg_blind", ctx->reg_blind},
       {"bias_mode", ctx->bias_mode}, {"bias_corrections", ctx->bias_corrections}, {"bias_normalisations", ctx->bias_normalisations},
       {"bias_scatters", ctx->bias_scatters}, {"bias_scatters_on_cells", ctx->bias_scatters_on_cells},
@@ -2472,7 +2341,7 @@ int svr_init_storage_volumes(svr_ctx *ctx, const uint32_t size[3], const float d
   ctx->have_em = false;
   ctx->n_active = ctx->n_psf = 0;
   invalidate(ctx, CH_SLICE_GEOMETRY | CH_SLICE_PIXELS | CH_TABLE_OFF);
-  ctx->d_coeff_id.reset();
+  ctx->table.free_ids();
   const size_t fb = np * sizeof(float);
   HIPCHK(ctx->d_slices.reserve(np));
   HIPCHK(ctx->d_weights.reserve(np));
@@ -2660,15 +2529,13 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
   ctx->recon_cur = ctx->d_recon_volw;      // recon | volw as one allocation again (the pair a sharded run all-reduces); the old volume is not read
   HIPCHK(hipMemsetAsync(ctx->d_recon_volw, 0, 2 * ctx->nv * sizeof(float), ctx->stream));
   const PassPath p1 = pass_path(ctx, PASS_GAUSS1), p2 = pass_path(ctx, PASS_GAUSS2);
-  if (p1.may_stream_table) {
-    r = coeff_lazy_pending(ctx) ? SVR_OK : ensure_coeff(ctx);   // (coeff_lazy: pass 2 writes the table below)
-    if (r) return r;
-  }
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_active;
   a.n = ctx->n_active;
-  if (p1.may_stream_table && table_holds(ctx, COEFF_FULL)) give_coeff(ctx, a);
-  bool stored = false;
+  // one plan for both passes.  Both stream, or pass 2 stores what pass 1 evaluated too -- if its cell lists, built below, hold the geometry
+  TablePlan tp = table_plan_for(ctx, PASS_GAUSS2, p2, true);
+  TableUse use = TABLE_EVALUATE;
+  if (tp.use != TABLE_STORE && (r = table_begin(ctx, tp, a, &use))) return r;
   ScopedTimer t(ctx, SVR_T_GAUSS);
   if (a.n && p1.family != FAM_PIXELS) {
     // pass 1 = the unit-based walk of the gather (sume, gate, v_PSF_sums, voxel-count flag), pass 2 = the scatter of the
@@ -2683,7 +2550,7 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
     uint32_t n1 = 0, n2 = 0;
     a.flag = nullptr; a.flag_out = ctx->d_gauss_flag;
     CellState *gcs = nullptr;
-    if (p1.family == FAM_CELLS && (!a.coeff || p1.table_on_cells) &&
+    if (p1.family == FAM_CELLS && gather_stays_on_cells(p1, use) &&
         (r = cells_or_fallback(ctx, true, 2, "pass 1 of the Gaussian reconstruction left the cell path (the cell lists cannot hold this geometry): tile kernel, same bits", gcs))) return r;
     if (gcs) {
       if ((r = launch_cell_gauss1(ctx, *gcs, a))) return r;
@@ -2698,11 +2565,13 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
     a.addon = ctx->recon(); a.cmap = ctx->volw();       // scatter targets of pass 2 (RC.cu:279-282)
     CellState *scs = nullptr;
     if (p2.family == FAM_CELLS && (r = cells_or_fallback(ctx, false, 0, SCATTER_LEFT_CELLS, scs))) return r;
-    if (scs) {
+    if (tp.use == TABLE_STORE) {
       // (coeff_lazy: pass 2 evaluates every unit the SR iterations will read -- it writes the table, and the SimulateSlices that follows streams it)
-      if (!a.coeff && (r = coeff_begin_store(ctx, &stored))) return r;
-      if (stored) give_coeff(ctx, a);
-      r = launch_cell_scatter(ctx, a, 1, ctx->recon(), ctx->volw(), stored);
+      if (!scs) tp = table_plan_for(ctx, PASS_GAUSS2, p2, false);
+      if ((r = table_begin(ctx, tp, a, &use))) return r;
+    }
+    if (scs) {
+      r = launch_cell_scatter(ctx, a, 1, ctx->recon(), ctx->volw(), use == TABLE_STORE);
     } else {
       // the tiles of the pixels that passed the gate (the tiled scatters only)
       HIPCHK(hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
@@ -2717,7 +2586,7 @@ int svr_gaussian_reconstruction_local(svr_ctx *ctx) {
   }
   t.stop();
   invalidate(ctx, CH_PSF_SUMS);
-  if (stored) ctx->coeff_state = COEFF_PSF;                // (written by pass 2 for the new v_PSF_sums)
+  table_end(ctx, use);                                     // (written by pass 2 for the new v_PSF_sums)
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
@@ -2757,23 +2626,21 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   const PassPath p = pass_path(ctx, PASS_FORWARD);
   // Round 6 (coeff_lazy): with the table wanted and not there, THIS pass writes it -- it evaluates every tap of every PSF pixel anyway
   // (fwd_cell_kernel<.., 3>); needs the cell gather.  Otherwise k_coeff_build, as before.
-  bool store = false;
   CellState *gcs = nullptr;
-  if (coeff_lazy_pending(ctx) && ctx->n_psf && ctx->n_active) {
+  TablePlan tp = table_plan_for(ctx, PASS_FORWARD, p, true);
+  if (tp.use == TABLE_STORE) {
     if ((r = cell_prepare_gather(ctx, gcs))) return r;
-    if (gcs->usable && (r = coeff_begin_store(ctx, &store))) return r;
-  }
-  if (!store) {
-    r = ensure_coeff(ctx);
-    if (r) return r;
+    if (!gcs->usable) tp = table_plan_for(ctx, PASS_FORWARD, p, false);
   }
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
-  if (store || (p.may_stream_table && table_holds(ctx, COEFF_PSF))) give_coeff(ctx, a);
+  TableUse use;
+  if ((r = table_begin(ctx, tp, a, &use))) return r;
+  const bool store = use == TABLE_STORE;
   if (a.n && p.family != FAM_PIXELS && (r = pack_volm(ctx, a, ctx->recon()))) return r;
   gcs = nullptr;
-  if (a.n && p.family == FAM_CELLS && (!a.coeff || store || p.table_on_cells) &&
+  if (a.n && p.family == FAM_CELLS && gather_stays_on_cells(p, use) &&
       (r = cells_or_fallback(ctx, true, 1, "the gather left the cell path (the cell lists cannot hold this geometry): tile kernel, same bits", gcs))) return r;
   if (a.n && p.family != FAM_PIXELS && !gcs && !ctx->fwd_tile_user) {
     int w, h;
@@ -2789,7 +2656,6 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
   if (store) t.also(SVR_T_FORWARD_STORE); else if (a.coeff) t.also(SVR_T_FORWARD_TABLE);
   if (gcs) {
     if ((r = launch_cell_gather(ctx, *gcs, a, store))) return r;
-    if (store) ctx->coeff_state = COEFF_PSF;               // (the PSF pixels' live units: what the SR iterations' passes read)
   } else if (a.n && p.family != FAM_PIXELS) {
     if ((r = ensure_tiles_fwd(ctx))) return r;
     if ((r = launch_unit_gather<false>(ctx, a, ctx->d_tiles_fwd, ctx->n_tiles_fwd, ctx->fwd_tiles_x, ctx->fwd_tiles_y, ctx->fwd_tw, ctx->fwd_th))) return r;
@@ -2797,6 +2663,7 @@ int svr_simulate_slices(svr_ctx *ctx, uint8_t *slice_inside) {
     if ((r = launch_pixels(ctx, a, ctx->pvr ? pvr_kernel<MODE_FWD> : psf_kernel<MODE_FWD>, "psf_kernel / pvr_kernel<FWD>"))) return r;
   }
   t.stop();
+  table_end(ctx, use);
   ctx->have_sim = true;
   if (!gcs) {                                              // (the cell gather's finish raises the slices' flags itself)
     hipLaunchKernelGGL(k_slice_inside, dim3(ctx->ns), dim3(256), 0, ctx->stream, ctx->d_siminside,
@@ -3096,29 +2963,28 @@ int svr_superresolution_backproject(svr_ctx *ctx, const float *slice_weight) {
   }
   r = ensure_psf_list(ctx);
   if (r) return r;
-  // (coeff_lazy: a scatter that finds no table evaluates -- and, on the cell path, writes it: whichever PSF pass comes first after a new geometry does)
-  r = coeff_lazy_pending(ctx) ? SVR_OK : ensure_coeff(ctx);
-  if (r) return r;
-  ctx->prep_pending = false;
-  ctx->cmap_from_scatter = true;
   PsfArgs a = make_args(ctx);
   a.list = ctx->d_psf_list;
   a.n = ctx->n_psf;
-  if (p.may_stream_table && table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
+  // (coeff_lazy: a scatter that finds no table evaluates -- and, on the cell path, writes it: whichever PSF pass comes first after a new geometry does)
+  TablePlan tp = table_plan_for(ctx, PASS_BACK, p, true);
+  TableUse use = TABLE_EVALUATE;
+  if (tp.use != TABLE_STORE && (r = table_begin(ctx, tp, a, &use))) return r;
+  ctx->prep_pending = false;
+  ctx->cmap_from_scatter = true;
   CellState *cs = nullptr;
   if (a.n && p.family == FAM_CELLS && (r = cells_or_fallback(ctx, false, 0, SCATTER_LEFT_CELLS, cs))) return r;
-  bool store = false;
-  if (cs && !a.coeff) {
-    if ((r = coeff_begin_store(ctx, &store))) return r;
-    if (store) give_coeff(ctx, a);
+  if (tp.use == TABLE_STORE) {                             // (the cell lists have spoken)
+    if (!cs) tp = table_plan_for(ctx, PASS_BACK, p, false);
+    if ((r = table_begin(ctx, tp, a, &use))) return r;
   }
+  const bool store = use == TABLE_STORE;
   ScopedTimer t(ctx, SVR_T_BACKPROJECT);
   if (store) t.also(SVR_T_BACKPROJECT_STORE); else if (a.coeff) t.also(SVR_T_BACKPROJECT_TABLE);
   // RC.cu:2202-2203 -- not needed where the cell scatter runs: its combine writes EVERY voxel of addon | cmap (0 outside the mask)
   if (!cs) HIPCHK(hipMemsetAsync(ctx->d_addon_cmap, 0, 2 * ctx->nv * sizeof(float), ctx->stream));
   if (cs) {
     if ((r = launch_cell_scatter(ctx, a, 0, ctx->addon(), ctx->cmap(), store))) return r;
-    if (store) ctx->coeff_state = COEFF_PSF;               // (the PSF pixels' live units: what the SR iterations' passes read)
   } else if (a.n && p.family != FAM_PIXELS) {
     if ((r = ensure_tiles_back(ctx))) return r;
     if ((r = launch_scatter(ctx, p.scatter_level, a, ctx->d_tiles, ctx->n_tiles, MODE_BACK))) return r;
@@ -3126,6 +2992,7 @@ int svr_superresolution_backproject(svr_ctx *ctx, const float *slice_weight) {
     if ((r = launch_pixels(ctx, a, ctx->pvr ? pvr_kernel<MODE_BACK> : psf_kernel<MODE_BACK>, "psf_kernel / pvr_kernel<BACK>"))) return r;
   }
   t.stop();
+  table_end(ctx, use);
   if (!ctx->sr_no_wait) HIPCHK(hipStreamSynchronize(ctx->stream));   // (svr_superresolution: the update follows on the same stream)
   return SVR_OK;
 }
@@ -3574,11 +3441,13 @@ int svr_normalise_bias_local(svr_ctx *ctx) {
   // factors f1 = 1 / sume, f0 = f1 (bias - log scale) over the PSF pixels, back_cell_kernel (streaming the table when it is valid:
   // NormaliseBias follows SuperresolutionGPU on the same geometry), the combine writes bias_vol and this call's weights, which are
   // then added to the never-cleared dev_volume_weights_.  A sharded rank scatters its own slices through its own cell lists.
+  const PassPath p = pass_path(ctx, PASS_BIAS);
   CellState *cs = nullptr;
-  if (a.n && pass_path(ctx, PASS_BIAS).family == FAM_CELLS &&
+  if (a.n && p.family == FAM_CELLS &&
       (r = cells_or_fallback(ctx, false, 0, "the NormaliseBias scatter left the cell path (the cell lists cannot hold this geometry): float atomics, last bits depend on the run", cs))) return r;
   if (cs) {
-    if (table_holds(ctx, COEFF_PSF)) give_coeff(ctx, a);
+    TableUse use;
+    if ((r = table_begin(ctx, table_plan_for(ctx, PASS_BIAS, p, true), a, &use))) return r;
     if ((r = launch_cell_scatter(ctx, a, 2, ctx->d_bias_vol, ctx->d_mbuf))) return r;
     hipLaunchKernelGGL(k_add_to, dim3(nblk(ctx->nv)), dim3(256), 0, ctx->stream, ctx->d_volume_weights, ctx->d_mbuf, ctx->nv);
     KCHK("k_add_to");

@@ -186,6 +186,56 @@ def test_channel_scatter_refuses_beyond_the_limit_and_the_context_goes_on():
     rec.close()
 
 
+def test_the_first_psf_pass_where_the_lazy_store_is_impossible():
+    """The table wanted, not there and left to the first evaluating cell pass (table_plan, csrc/svr_plan.h), on a geometry whose cell lists
+    cannot be built: the scatter evaluates on the tiles and leaves the table unwritten; the gather builds it with k_coeff_build and
+    streams it, and gives the bits of a context that evaluates every tap.  (The expectations were read from the code before the table's
+    decisions moved into table_plan, and agree with a transcription of that code over every input combination.)"""
+    from fetalreconstruction_amd import engine as E
+    case = C.build("centres-x-beyond")
+    assert not case.split_gather                                       # (neither the scatter's lists nor the gather's hold the geometry)
+    P = case.problem
+    ones = np.ones(P.ns, np.float32)
+
+    def after_the_gaussian(**options):
+        rec = _engine(case, **options)
+        rec.timer_enable(True)
+        rec.UpdateScaleVector(ones, ones)
+        rec.InitializeEMValues()
+        rec.GaussianReconstruction()
+        return rec
+
+    rec = after_the_gaussian()
+    assert rec.get_option("coeff_table") == 1 and rec.get_option("coeff_state") == 0
+    volume = _flat(rec.syncCPU()).copy()                               # (pass 2 ran on the atomics: one volume for the gathers below)
+    w, ss, sw = C.em_inputs(P)
+    rec.debug_set(E.BUF_WEIGHTS, w)
+    rec.debug_set(E.BUF_SIMSLICES, ss)
+    rec.SuperresolutionBackproject(sw)
+    t = rec.timers()
+    print(f"scatter first: coeff_state {rec.get_option('coeff_state')}, coeff_build {t['coeff_build']}, backproject_store {t['backproject_store']}, backproject_table {t['backproject_table']}")
+    assert rec.get_option("coeff_state") == 0 and t["coeff_build"][1] == 0
+    assert t["backproject"][1] == 1 and t["backproject_store"] == (0.0, 0) and t["backproject_table"][1] == 0
+    rec.close()
+
+    res = []
+    for table in (1, 0):
+        rec = after_the_gaussian(coeff_table=table)
+        assert rec.get_option("coeff_state") == 0
+        rec.debug_set(E.BUF_RECONSTRUCTED, volume)
+        rec.debug_set(E.BUF_SIMSLICES, np.zeros(P.slices.shape, np.float32))
+        rec.SimulateSlices()
+        t = rec.timers()
+        print(f"gather first, coeff_table {table}: coeff_state {rec.get_option('coeff_state')}, coeff_build {t['coeff_build']}, forward_store {t['forward_store']}, forward_table {t['forward_table']}")
+        assert rec.get_option("coeff_state") == (2 if table else 0) and t["coeff_build"][1] == table
+        assert t["forward"][1] == 1 and t["forward_store"][1] == 0 and t["forward_table"][1] == table
+        res.append([_flat(rec.debug_get(b)).copy() for b in (E.BUF_SIMSLICES, E.BUF_SIMWEIGHTS, E.BUF_SIMINSIDE)])
+        rec.close()
+    assert np.abs(res[0][0]).max() > 0
+    for a, b in zip(*res):
+        assert np.array_equal(a, b, equal_nan=True)
+
+
 def test_normalise_bias_scatter_falls_back_onto_the_atomics():
     """NormaliseBias where the scatter's lists cannot be built (case 7 beyond): the sequence of test_bias_steps_against_the_oracle"""
     from fetalreconstruction_amd import engine as E
